@@ -1,9 +1,21 @@
 #!/usr/bin/env python
 """bench.py — headline benchmark of the sort + rasterize hot path (contract in the task brief).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run measures the headline only: set-up, warm-up (a frame per lane, the W steps, then WARM_FRAMES more
+untimed frames), ONE timed region of exactly K steps, the outputs of its last step if --dump-outputs is given, and
+the result line (`value` = whole-job frames/s, `ms_per_step` = milliseconds per timed step). Everything else below
+(the repeated timed regions, the side legs, the roofline, the CPU baseline and the whole-frame parity check, the
+native-gather self-check) runs only with --full, after the same headline region.
+
+--dump-outputs DIR writes what the last timed step computed, as the caller of that path receives it, in float32:
+DIR/frame_rgba_f32.npy, the [H, W, 4] linear RGBA frame (one GPU), or DIR/frames_srgb8.npy, the last
+Rgba8UnormSrgb frame of every rank as gathered on rank 0 (N > 1; a fixed, seeded sample of its pixels, with their
+flat indices in DIR/frames_srgb8_pixel_index.npy, where the whole would exceed DUMP_LIMIT_BYTES). The inputs are
+seeded: the same arguments give the same inputs in every run.
 
 A "step" is one pass of the hot path over one view: keygen (+ stable cull partition) -> depth
 radix sort -> project + ordered supertile binning -> tile raster of a 1920x1080 frame, with the cloud
@@ -16,7 +28,8 @@ pixel (coverage per sample, shading per pixel, resolved frame); `msaa_off` has t
 headless camera yawed g*45 degrees) of the replicated cloud and rank 0 gathers every rank's frames
 over RCCL, asynchronously, 8 frames per collective (weak scaling: per-GPU work fixed).
 
-Prints ONE JSON line on rank 0. `value` = whole-job frames/s. Extra objects:
+Prints ONE JSON line on rank 0. `value` = whole-job frames/s. Extra objects (--full):
+  repeated_regions  the headline configuration timed as the median of many regions of K steps (>= 0.5 s in all)
   roofline      dominant kernel of the hot path, algorithmic bytes per launch / average launch duration
                 measured live with HIP events on the library's own stream (bgs_get_stats) on frames
                 that are not overlapped with other frames; `in_flight` has the same for the pipelined
@@ -53,6 +66,8 @@ N_SPLATS = 1_000_000
 SEED = 2
 WIDTH, HEIGHT = 1920, 1080
 GATHER_BATCH = 8  # frames per framebuffer gather (N > 1)
+WARM_FRAMES, WARM_CHUNK = 3000, 500  # untimed frames before the headline region (~0.15 s: clocks, learnt state)
+DUMP_LIMIT_BYTES = 60 << 20  # --dump-outputs: at most this many bytes of arrays (64 MB with the .npy headers)
 
 
 def kernel_source_sha256() -> str:
@@ -191,7 +206,7 @@ def quad_size_histogram(cloud, view, settings, sample=200_000, seed=0):
 
 
 def measure(plugin, handle, view, settings, steps, warmup, gather=None, barrier=None, depth=1, trials=1,
-            busy_warm_frames=0, views=None):
+            busy_warm_frames=0, views=None, warm_chunk=None):
     """W untimed + K timed steps. A step ENQUEUES one frame: the scan pipeline needs no host round
     trip, and the context keeps `depth` frames in flight (lanes, multiplexed onto a few HIP streams). With a
     `gather` callback (N > 1 ranks) the oldest frame is popped and handed to it as soon as `depth`
@@ -200,7 +215,8 @@ def measure(plugin, handle, view, settings, steps, warmup, gather=None, barrier=
     region (barrier, K steps, barrier) is repeated and the list of durations returned as well: K = 20 frames
     are 1.5 ms of GPU time, which one clock ramp or one late lane moves by 10 %, so the headline reports the
     median trial. `busy_warm_frames`: that many more untimed frames before the first trial (clocks, adaptive
-    state) — a frame COUNT, not a duration, so that every rank of a multi-GPU run issues the same collectives.
+    state) — a frame COUNT, not a duration, so that every rank of a multi-GPU run issues the same collectives —, run
+    in chunks of `warm_chunk` frames (default: max(steps, 4 * depth)).
     Returns (seconds of the median trial, per-stage ms averaged by the library over the timed frames' HIP
     events, stats[, every trial's seconds])."""
     prepared = plugin.prepare(view, settings)  # marshal the C structs once, like a caller's per-view cache
@@ -231,7 +247,7 @@ def measure(plugin, handle, view, settings, steps, warmup, gather=None, barrier=
     # --warmup (fewer steps than lanes) does not leave allocations inside the timed region
     run(depth)
     run(warmup)
-    chunk = max(steps, 4 * depth)
+    chunk = warm_chunk or max(steps, 4 * depth)
     for _ in range((busy_warm_frames + chunk - 1) // chunk):
         run(chunk)
     dts = []
@@ -366,6 +382,41 @@ def cpu_baseline(cloud, view, settings, gpu_frame=None, gpu_entries=None):
     }
 
 
+def gathered_last_frames(plugin, batcher, world):
+    """Rank 0 of the gather path, after the timed region: the last timed frame of every rank as it arrived on rank 0,
+    [world, H, W, 4] uint8 (Rgba8UnormSrgb). The frame was rendered into a slot of rank 0's staging batch, and rank r's
+    copy of that slot sits in the receive buffer of the same batch (bgs.h, bgs_comm_gather)."""
+    from bevy_gaussian_splatting_amd.multiview import NativeFrameGather
+    fb = WIDTH * HEIGHT * 4
+    own, _ = plugin.framebuffer_srgb8_device_ptr()
+    native = isinstance(batcher, NativeFrameGather)
+    starts = list(batcher.stage) if native else [t.data_ptr() for t in batcher.stage]
+    s = next(i for i, p in enumerate(starts) if p <= own < p + batcher.batch * fb)
+    slot = (own - starts[s]) // fb
+    out = np.empty((world, HEIGHT, WIDTH, 4), np.uint8)
+    for r in range(world):
+        if native:
+            plugin.download(batcher.recv[s] + (r * batcher.batch + slot) * fb, out[r])
+        else:
+            out[r] = (batcher.recv[s][r][slot] if batcher.active else batcher.stage[s][slot]).cpu().numpy()
+    return out
+
+
+def write_output(dirname, name, frames):
+    """--dump-outputs: `frames` (trailing axes H, W, 4) as DIR/<name>.npy in float32. Beyond DUMP_LIMIT_BYTES, a fixed,
+    seeded sample of pixel positions (the same for every leading index) and DIR/<name>_pixel_index.npy, their flat
+    indices (float64)."""
+    os.makedirs(dirname, exist_ok=True)
+    a = np.asarray(frames)
+    *lead, h, w, c = a.shape
+    if a.size * 4 > DUMP_LIMIT_BYTES:
+        keep = DUMP_LIMIT_BYTES // (int(np.prod(lead)) * c * 4 + 8)
+        idx = np.sort(np.random.default_rng(0).choice(h * w, size=keep, replace=False))
+        np.save(os.path.join(dirname, f"{name}_pixel_index.npy"), idx.astype(np.float64))
+        a = a.reshape(*lead, h * w, c)[..., idx, :]
+    np.save(os.path.join(dirname, f"{name}.npy"), a.astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -377,7 +428,13 @@ def main():
     ap.add_argument("--streams", type=int, default=4,
                     help="HIP streams the lanes are multiplexed onto (0 = one per lane): frames competing for the chip")
     ap.add_argument("--trials", type=int, default=0,
-                    help="timed regions of --steps frames; the median is reported (default: 5, 3 from 2000 steps up)")
+                    help="--full: timed regions of --steps frames in `repeated_regions`, the median reported "
+                         "(default: 5, 3 from 2000 steps up, and as many as put >= 0.5 s inside them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the side measurements and checks (repeated regions, side legs, roofline, CPU baseline, "
+                         "whole-frame parity); a plain run times the headline only")
     args = ap.parse_args()
 
     if os.environ.get("BGS_LIB_OVERRIDE"):
@@ -498,45 +555,72 @@ def main():
     # the headline region runs without stage events (each record is a packet on the stream; timing every
     # 16th frame cost ~5 % of the rate being measured); the per-stage numbers come from separate passes
     plugin.set_profiling(0)
-    # Trials: at least 5 (3 from 2000 steps up), and as many as it takes to put >= 0.5 s of GPU time inside timed
-    # regions (20 steps are ~1 ms: the driver's utilisation sampling cannot see five of those). The count comes from
-    # a pilot region and is agreed between the ranks (max over ranks), so every rank issues the same collectives.
-    trials = args.trials if args.trials > 0 else (5 if args.steps < 2000 else 3)
-    if args.trials <= 0:
-        pilot, _, _ = measure(plugin, handle, view, settings, args.steps, args.warmup, gather, barrier, lanes,
-                              busy_warm_frames=3000)
-        if dist is not None:
-            t = torch.tensor([pilot], dtype=torch.float64, device="cuda")
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            pilot = float(t.item())
-        trials = int(max(trials, min(1000, math.ceil(0.5 / max(pilot, 1e-6)))))
-    _, _, _, dts = measure(plugin, handle, view, settings, args.steps, args.warmup, gather, barrier, lanes,
-                           trials=max(trials, 2), busy_warm_frames=0 if args.trials <= 0 else 3000)
-    issued_main = FRAMES_ISSUED[0]
-    plugin.set_profiling(2)
-    plugin.set_packed_only(False)
+    # ---- headline: ONE timed region of exactly --steps frames -----------------------------------------------
+    # Before it, untimed: a frame per lane, the --warmup frames and WARM_FRAMES more, in chunks of a fixed size (frame
+    # COUNTS, so that every rank issues the same collectives, and a warm-up that does not grow with --steps).
+    dt, _, _ = measure(plugin, handle, view, settings, args.steps, args.warmup, gather, barrier, lanes,
+                       busy_warm_frames=WARM_FRAMES, warm_chunk=WARM_CHUNK)
     per_rank = None
-    if dist is not None:  # a trial lasts as long as its slowest rank
-        t = torch.tensor(dts, dtype=torch.float64, device="cuda")
-        mine = torch.tensor([statistics.median(dts)], dtype=torch.float64, device="cuda")
+    if dist is not None:  # the region lasts as long as its slowest rank
+        mine = torch.tensor([dt], dtype=torch.float64, device="cuda")
         every = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(every, mine)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dts = [float(x) for x in t.tolist()]
+        dt = max(float(e.item()) for e in every)
         frame_bytes8 = WIDTH * HEIGHT * 4
         per_rank = [{"rank": r, "frames_per_s": round(args.steps / float(e.item()), 2),
                      "gather_bytes_per_trial": args.steps * frame_bytes8 if r != 0 else 0,
-                     # what the rank's link carried while it rendered: its frames' bytes over ITS OWN median region
+                     # what the rank's link carried while it rendered: its frames' bytes over ITS OWN timed region
                      "link_GBps": round(args.steps * frame_bytes8 / float(e.item()) / 1e9, 2) if r != 0 else None}
                     for r, e in enumerate(every)]
-        if rank == 0 and batcher is not None:
-            # every frame every rank issued on this path has arrived on rank 0 (flush() waits for all collectives)
-            want = world * issued_main
-            if batcher.frames_received != want:
-                raise SystemExit(f"gather check failed: rank 0 received {batcher.frames_received} frames, "
-                                 f"{world} ranks issued {want}")
+    fps = world * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        # the frames are complete (measure() ends with a synchronise and, on the gather path, a flush)
+        if dist is None:
+            ptr, _ = plugin.framebuffer_device_ptr()
+            write_output(args.dump_outputs, "frame_rgba_f32", plugin.download(ptr, np.empty((HEIGHT, WIDTH, 4), np.float32)))
+        else:
+            write_output(args.dump_outputs, "frames_srgb8", gathered_last_frames(plugin, batcher, world))
+
+    repeated = None
+    if args.full:
+        # The same configuration timed as the median of many regions of --steps frames: at least 5 (3 from 2000 steps
+        # up), and as many as it takes to put >= 0.5 s of GPU time inside timed regions (20 steps are ~1 ms: a monitor
+        # that samples the device a few times per second cannot see five of those). The count comes from a pilot region and is agreed between the
+        # ranks (max over ranks), so every rank issues the same collectives.
+        trials = args.trials if args.trials > 0 else (5 if args.steps < 2000 else 3)
+        if args.trials <= 0:
+            pilot, _, _ = measure(plugin, handle, view, settings, args.steps, args.warmup, gather, barrier, lanes,
+                                  busy_warm_frames=3000)
+            if dist is not None:
+                t = torch.tensor([pilot], dtype=torch.float64, device="cuda")
+                dist.all_reduce(t, op=dist.ReduceOp.MAX)
+                pilot = float(t.item())
+            trials = int(max(trials, min(1000, math.ceil(0.5 / max(pilot, 1e-6)))))
+        _, _, _, dts = measure(plugin, handle, view, settings, args.steps, args.warmup, gather, barrier, lanes,
+                               trials=max(trials, 2), busy_warm_frames=0 if args.trials <= 0 else 3000)
+        if dist is not None:  # a trial lasts as long as its slowest rank
+            t = torch.tensor(dts, dtype=torch.float64, device="cuda")
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            dts = [float(x) for x in t.tolist()]
+        dt_med = statistics.median(dts)
+        repeated = {"value": round(world * args.steps / dt_med, 2), "unit": "frames/s",
+                    "ms_per_step": round(1e3 * dt_med / args.steps, 4), "trials": len(dts),
+                    "trials_ms_min_median_max": [round(1e3 * min(dts), 4), round(1e3 * dt_med, 4), round(1e3 * max(dts), 4)],
+                    "trials_ms_first_10": [round(1e3 * x, 4) for x in dts[:10]], "reported": "median trial",
+                    "gpu_seconds_in_timed_regions": round(sum(dts), 3),
+                    "note": "every trial is a barrier + sync, --steps frames, barrier + sync; 3000 untimed frames (~0.2 s) and "
+                            "a pilot region precede the first one; the number of trials puts >= 0.5 s inside timed regions"}
+    issued_main = FRAMES_ISSUED[0]
+    plugin.set_profiling(2)
+    plugin.set_packed_only(False)
+    if dist is not None and rank == 0 and batcher is not None:
+        # every frame every rank issued on this path has arrived on rank 0 (flush() waits for all collectives)
+        want = world * issued_main
+        if batcher.frames_received != want:
+            raise SystemExit(f"gather check failed: rank 0 received {batcher.frames_received} frames, "
+                             f"{world} ranks issued {want}")
     gather_selfcheck = None
-    if dist is not None and batcher is not None and native_gather:
+    if args.full and dist is not None and batcher is not None and native_gather:
         # outside the timed region: one more native gather of a known pattern — rank r's batch holds the byte r + 1 —
         # checked on rank 0 block by block (the frame COUNT above says every collective completed, this says the bytes
         # landed where bgs.h says they land)
@@ -551,12 +635,32 @@ def main():
             gather_selfcheck = bool((got == want).all().item())
             if not gather_selfcheck:
                 raise SystemExit("native gather self-check failed: a rank's block does not hold that rank's bytes")
-    dt = statistics.median(dts)
-    fps = world * args.steps / dt
 
-    # ---- side measurements on rank 0 (outside the timed region) -----------------------------
     out = None
     if rank == 0:
+        out = {
+            "metric": "frames/sec @1080p, 1M-splat 3DGS (sort + rasterize every frame)",
+            "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 4),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+            "data": "synthetic",
+            "timing": {"trials": 1, "timed_steps": args.steps, "region_ms": round(1e3 * dt, 4),
+                       "reported": "one timed region of --steps frames",
+                       "note": f"barrier + sync, --steps frames, barrier + sync; a frame per lane, the --warmup frames and "
+                               f"{WARM_FRAMES} more untimed frames precede it"},
+            "config": {"workload": f"{args.splats}-splat 3DGS f32 planar cloud (seed {SEED}, reference random_gaussians_3d "
+                                   "distributions), 1920x1080, SH degree 3, CloudSettings::default(), "
+                                   "examples/headless.rs camera incl. its Msaa (Bevy's default Sample4: 4 samples per pixel, "
+                                   "resolved frame); one camera per GPU",
+                       "sample_count": view.msaa_samples,
+                       "parallelism": f"views{world}", "sort": "radix32", "global_scale": 1.0,
+                       "frames_in_flight": lanes, "lanes": lanes, "streams": streams},
+            "build_id": plugin.build_id(),
+            "per_rank": per_rank,
+        }
+
+    # ---- side measurements on rank 0 (--full; outside the timed region) ---------------------
+    if rank == 0 and args.full:
         # per-stage times with the frames overlapped as in the headline region (every STRIDE-th frame timed)
         _, stage_ms, st = measure(plugin, handle, view, settings, max(args.steps // 2, 4 * STRIDE), 4, depth=lanes)
         table = stage_table(st, 240)
@@ -923,32 +1027,14 @@ def main():
         dt4, stage4, st4, _ = measure(plugin, handle, view, s2, max(args.steps // 3, 3), 2, trials=3)
         plugin.set_binning("scan")
 
-        out = {
-            "metric": "frames/sec @1080p, 1M-splat 3DGS (sort + rasterize every frame)",
-            "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-            "data": "synthetic",
-            "timing": {"trials": len(dts), "trials_ms_min_median_max": [round(1e3 * min(dts), 4), round(1e3 * dt, 4), round(1e3 * max(dts), 4)],
-                       "trials_ms_first_10": [round(1e3 * x, 4) for x in dts[:10]], "reported": "median trial",
-                       "gpu_seconds_in_timed_regions": round(sum(dts), 3),
-                       "note": "every trial is a barrier + sync, --steps frames, barrier + sync; 3000 untimed frames (~0.2 s) and a "
-                               "pilot region precede the first one; the number of trials puts >= 0.5 s inside timed regions"},
-            "config": {"workload": f"{args.splats}-splat 3DGS f32 planar cloud (seed {SEED}, reference random_gaussians_3d "
-                                   "distributions), 1920x1080, SH degree 3, CloudSettings::default(), "
-                                   "examples/headless.rs camera incl. its Msaa (Bevy's default Sample4: 4 samples per pixel, "
-                                   "resolved frame); one camera per GPU",
-                       "sample_count": view.msaa_samples,
-                       "parallelism": f"views{world}", "sort": "radix32", "global_scale": 1.0,
-                       "frames_in_flight": lanes, "lanes": lanes, "streams": streams},
-            "build_id": plugin.build_id(),
+        out.update({
+            "repeated_regions": repeated,
             "single_stream": single,
             "msaa_off": msaa_off,
             "latency": latency,
             "orbit": orbit,
             "sustained": sustained,
             "trained_like": trained_like,
-            "per_rank": per_rank,
             "roofline": roofline_main,
             "frame": {"device_ms": round(frame_ms, 4), "algorithmic_GB": round(frame_bytes / 1e9, 4),
                       "GBps": round(frame_gbs, 1), "pct_hbm_peak": round(100 * frame_gbs / HBM_PEAK_GBS, 2),
@@ -987,7 +1073,7 @@ def main():
                 "GBps": round(st3["algorithmic_bytes"] / (max(sum(stage3.values()), 1e-9) * 1e-3) / 1e9, 1),
                 "scene_like_value": round(max(args.steps // 3, 3) / dt4, 2),
                 "scene_like_stage_ms": {k: round(v, 4) for k, v in stage4.items()}},
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cloud, view, settings, gpu_frame, gpu_entries)
             out["parity"] = out["cpu_baseline"].pop("parity")

@@ -20,7 +20,7 @@ cp $R/gpurun_out/tolerance_accounting_band_2.5e-4.json $OUT/tolerance_accounting
 echo "== sweeps"; SMALL=2000 MEDIUM=350 SURFEL=120 bash scripts/gpu_sweeps.sh $TAG 2>&1 | tail -8
 if [ -n "$EXPLORE" ]; then echo "== exploratory sweeps (seeds $EXPLORE .., edge band ${EXPLORE_BAND:-5e-4} px)"; BGS_ORACLE_EDGE_BAND_PX=${EXPLORE_BAND:-5e-4} BGS_RANDOM_SEED_BASE=$EXPLORE SMALL=${EXPLORE_SMALL:-4000} MEDIUM=${EXPLORE_MEDIUM:-700} SURFEL=${EXPLORE_SURFEL:-300} bash scripts/gpu_sweeps.sh $TAG/explore_$EXPLORE 2>&1 | tail -8; cp $R/gpurun_out/tolerance_accounting_band_${EXPLORE_BAND:-5e-4}.json $OUT/explore_$EXPLORE/ 2>/dev/null; fi
 echo "== sort rates"; timeout 600 python scripts/sort_rates.py 2>&1 | grep -v amdgpu.ids | tee $OUT/sort_rates.txt | cut -c1-170
-echo "== bench"; timeout 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err; cut -c1-600 $OUT/bench.json; tail -2 $OUT/bench.err
+echo "== bench"; timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; cut -c1-600 $OUT/bench.json; tail -2 $OUT/bench.err
 for i in 1 2; do timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_driver_flags_$i.json 2>/dev/null; cut -c1-160 $OUT/bench_driver_flags_$i.json; done
 echo "== msaa on / off, same process"; BGS_AB_MSAA=4,1 timeout 600 python scripts/ab_flags.py "dense scene trained surfel 5m_dense 5m_scene" 0 1 2>&1 | grep -v amdgpu.ids | tee $OUT/ab_msaa_4_vs_1.txt | cut -c1-200
 echo "== other configs"; timeout 900 python scripts/bench_configs.py > $OUT/bench_other_configs.json 2> $OUT/bench_other.err; grep -E "frames_per_s" $OUT/bench_other_configs.json | head -20
@@ -33,7 +33,7 @@ for w in surfel 5m_scene; do
   for f in $(find /tmp/p_$w -name "*kernel_stats.csv"); do cp $f $OUT/${w}_kernel_stats.csv; done
   cd $R
 done
-echo "== bench with the PMC stamp"; cp $OUT/pmc_traffic.json $R/profiles/pmc_traffic.json; timeout 900 python bench.py --no-cpu-baseline > $OUT/bench_stamped.json 2>/dev/null; python -c "
+echo "== bench with the PMC stamp"; cp $OUT/pmc_traffic.json $R/profiles/pmc_traffic.json; timeout 900 python bench.py --full --no-cpu-baseline > $OUT/bench_stamped.json 2>/dev/null; python -c "
 import json,sys
 d=json.load(open('$OUT/bench_stamped.json')); print(d['value'], json.dumps(d['roofline'].get('valu'))[:700], d['roofline'].get('traffic'))"
 echo "== timelines"; bash scripts/gpu_timeline.sh 2>&1 | tail -4; cp $R/gpurun_out/timeline_depth*.json $OUT/ 2>/dev/null

@@ -7,7 +7,7 @@ OUT=$R/gpurun_out/prof
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp
 rm -rf /tmp/p_trace
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_trace -o trace -- python $R/bench.py --steps 40 --warmup 5 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> /tmp/trace.err
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_trace -o trace -- python $R/bench.py --steps 40 --warmup 5 --full --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> /tmp/trace.err
 for f in $(find /tmp/p_trace -name "*kernel_stats.csv"); do cp $f $OUT/bench_kernel_stats.csv; done
 for f in $(find /tmp/p_trace -name "*kernel_trace.csv"); do python - "$f" "$OUT/bench_kernel_trace_summary.txt" <<'PY'
 import csv, sys, collections
@@ -16,7 +16,7 @@ agg = collections.defaultdict(list)
 for r in rows:
     agg[r["Kernel_Name"].split("(")[0][:70]].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"]), r.get("VGPR_Count"), r.get("LDS_Block_Size"), r.get("Grid_Size"), r.get("Workgroup_Size")))
 with open(sys.argv[2], "w") as f:
-    f.write("rocprofv3 --kernel-trace --stats -- python bench.py --steps 40 --warmup 5 --no-cpu-baseline\n")
+    f.write("rocprofv3 --kernel-trace --stats -- python bench.py --steps 40 --warmup 5 --full --no-cpu-baseline\n")
     f.write("(bench.py runs, in order: headline dense scan-binning frames, bgs_sort calls, scene-like frames, instance-sort frames)\n")
     f.write(f"{'kernel':72s} {'calls':>6s} {'avg_us':>9s} {'min_us':>9s} {'max_us':>9s} vgpr lds\n")
     for k, v in sorted(agg.items(), key=lambda kv: -sum(x[0] for x in kv[1])):

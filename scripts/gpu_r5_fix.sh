@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/r5_v1
 cd $R
-timeout 900 python bench.py --no-cpu-baseline > $OUT/bench_stamped.json 2>/dev/null; python -c "
+timeout 900 python bench.py --full --no-cpu-baseline > $OUT/bench_stamped.json 2>/dev/null; python -c "
 import json
 d=json.load(open('$OUT/bench_stamped.json')); print(d['value'], json.dumps(d['roofline'].get('valu'))[:900], d['roofline'].get('traffic'))"
 SMALL=2000 MEDIUM=350 SURFEL=120 bash scripts/gpu_sweeps.sh r5_v1 2>&1 | tail -n 8

@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -76,7 +77,7 @@ def test_committed_counter_file_follows_from_the_committed_raw_counters(tmp_path
 
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_keys():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "16", "--warmup", "4"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "16", "--warmup", "4", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -102,8 +103,10 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
         assert k in cb, k
     assert cb["kind"] == "port" and cb["cores"] >= 1 and cb["value"] > 0
     assert d["value"] > 1000.0     # BASELINE.json's target on this config, with a wide margin to the measured 12 k
-    assert d["timing"]["trials"] >= 5 and "traffic_source" in rf
-    assert d["timing"]["gpu_seconds_in_timed_regions"] >= 0.45          # enough for the driver's utilisation sampling
+    assert d["timing"]["trials"] == 1 and d["timing"]["timed_steps"] == 16   # the headline: one region of --steps frames
+    assert d["repeated_regions"]["trials"] >= 5 and "traffic_source" in rf
+    assert d["repeated_regions"]["gpu_seconds_in_timed_regions"] >= 0.45     # enough for a monitor sampling the device
+    assert d["repeated_regions"]["value"] > 1000.0
     from bevy_gaussian_splatting_amd import _build_id
     assert d["build_id"] == _build_id.kernel_source_sha256()             # the library that ran = this tree's sources
     # the whole benchmarked frame was checked against the oracle frame the CPU baseline renders anyway
@@ -131,15 +134,54 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
 
 
 @pytest.mark.gpu
-def test_bench_gather_path_runs_with_one_rank():
+def test_plain_bench_times_exactly_the_steps_and_dumps_the_last_frame(tmp_path, plugin):
+    """A plain run (no --full) measures the headline only: one timed region of exactly --steps frames, the contract keys,
+    none of the side legs. --dump-outputs writes the last timed frame, which must be bit-identical to a blocking render
+    of the same seeded cloud and camera (rendering is deterministic, test_render_is_deterministic_and_views_are_independent)."""
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "16", "--warmup", "4",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config", "timing", "build_id"):
+        assert k in d, k
+    for k in ("repeated_regions", "roofline", "cpu_baseline", "parity", "single_stream", "orbit", "sustained"):
+        assert k not in d, k
+    assert d["steps"] == 16 and d["warmup"] == 4 and d["timing"]["trials"] == 1 and d["timing"]["timed_steps"] == 16
+    assert d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert abs(d["value"] - 1e3 / d["ms_per_step"]) / d["value"] < 0.01
+    assert abs(d["timing"]["region_ms"] - 16 * d["ms_per_step"]) <= 0.01 * d["timing"]["region_ms"] + 1e-3
+    assert d["value"] > 1000.0
+    assert sorted(os.listdir(out)) == ["frame_rgba_f32.npy"]
+    got = np.load(out / "frame_rgba_f32.npy")
+    assert got.dtype == np.float32 and got.shape == (1080, 1920, 4)
+    import bench
+    from bevy_gaussian_splatting_amd import CloudSettings, random_gaussians_3d_seeded
+    from bevy_gaussian_splatting_amd.multiview import headless_view
+    h = plugin.upload(random_gaussians_3d_seeded(bench.N_SPLATS, bench.SEED))
+    try:
+        want = plugin.render(h, headless_view(0, bench.WIDTH, bench.HEIGHT), CloudSettings())
+    finally:
+        h.free()
+    assert np.array_equal(got, want)
+    assert np.isfinite(want).all() and (want[..., 3] > 0).any()        # a frame with content, not a cleared target
+
+
+@pytest.mark.gpu
+def test_bench_gather_path_runs_with_one_rank(tmp_path):
     """The N > 1 code path of bench.py (process group on RCCL, packed-only sRGB8 frames rendered straight into
     the staging batch, asynchronous batched gather, max over ranks) with a single rank
     (BGS_BENCH_FORCE_DIST=1): every timed and untimed frame must arrive on rank 0."""
     env = dict(os.environ, BGS_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29531")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
+    out = tmp_path / "outputs"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "24", "--warmup", "4",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                        "--no-cpu-baseline", "--full", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=900,
+                       cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -148,12 +190,39 @@ def test_bench_gather_path_runs_with_one_rank():
     assert "Rgba8UnormSrgb" in d["frame"]["gathered_format"] and d["frame"]["gather_batch_frames"] in (8, None)
     lanes = d["config"]["lanes"]
     chunk = max(24, 4 * lanes)
-    # pilot region (lanes + warm-up + ~3000 busy-warm frames + 24) and the timed trials (lanes + warm-up + 24 each)
-    expected = (lanes + 4 + -(-3000 // chunk) * chunk + 24) + (lanes + 4 + d["timing"]["trials"] * 24)
+    # the headline region (lanes + warm-up + 3000 untimed frames in chunks of 500 + 24), then --full's pilot region
+    # (lanes + warm-up + ~3000 busy-warm frames + 24) and its timed trials (lanes + warm-up + 24 each)
+    expected = ((lanes + 4 + 3000 + 24) + (lanes + 4 + -(-3000 // chunk) * chunk + 24)
+                + (lanes + 4 + d["repeated_regions"]["trials"] * 24))
     assert d["frame"]["frames_issued_per_rank"] == expected
     assert d["frame"]["frames_gathered_on_rank0"] == d["n_gpus"] * expected
     pr = d["per_rank"]
     assert len(pr) == 1 and pr[0]["rank"] == 0 and pr[0]["frames_per_s"] > 1000.0 and pr[0]["link_GBps"] is None
+    # --dump-outputs on this path: the last timed frame of every rank as gathered on rank 0, Rgba8UnormSrgb bytes in float32
+    assert sorted(os.listdir(out)) == ["frames_srgb8.npy"]
+    f = np.load(out / "frames_srgb8.npy")
+    assert f.dtype == np.float32 and f.shape == (1, 1080, 1920, 4)
+    assert f.min() >= 0.0 and f.max() <= 255.0 and np.array_equal(f, np.round(f)) and (f[..., 3] > 0).any()
+
+
+def test_dumped_outputs_stay_within_64_mb(tmp_path):
+    """bench.write_output: an output that fits is written whole, in float32; a larger one as a fixed, seeded sample of
+    pixel positions (the same in every run and for every frame), with the sampled flat indices beside it."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    one = np.arange(1080 * 1920 * 4, dtype=np.float32).reshape(1080, 1920, 4)
+    bench.write_output(tmp_path, "one", one)
+    assert sorted(os.listdir(tmp_path)) == ["one.npy"] and np.array_equal(np.load(tmp_path / "one.npy"), one)
+    two = np.stack([one % 251, 250 - one % 251]).astype(np.uint8)
+    bench.write_output(tmp_path, "two", two)
+    bench.write_output(tmp_path / "again", "two", two)
+    a, idx = np.load(tmp_path / "two.npy"), np.load(tmp_path / "two_pixel_index.npy")
+    assert a.dtype == np.float32 and idx.dtype == np.float64 and a.shape == (2, len(idx), 4)
+    assert len(idx) > 1080 * 1920 // 2 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(a, two.reshape(2, -1, 4).astype(np.float32)[:, idx.astype(np.int64)])
+    assert np.array_equal(np.load(tmp_path / "again" / "two.npy"), a)
+    assert (tmp_path / "two.npy").stat().st_size + (tmp_path / "two_pixel_index.npy").stat().st_size <= 64 * 10**6
 
 
 def test_the_benchs_parity_checker_can_fail():
