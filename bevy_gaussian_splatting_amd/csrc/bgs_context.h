@@ -68,7 +68,7 @@ struct GraphKey {
     const void* keygen_func;
     uint32_t keygen_threads;
     uint32_t wide_bin;         // bin_kernel<16> (1024 threads) or <4>: follows the pipeline depth, not the grid sizes
-    uint32_t raster_variant;   // sample_count | (a depth buffer is bound) << 8: which rasteriser instantiation the graph holds
+    uint32_t raster_variant;   // the launched rasteriser instantiation: samples | depth << 8 | overlay << 9 | mode (graph_key)
     uint32_t split_sub;        // FrameCleanup::split_sub, a rasteriser argument: how many quantile keys the captured clean-up leaves
 };
 struct FrameGraph {
@@ -76,6 +76,46 @@ struct FrameGraph {
     hipGraphExec_t exec = nullptr;
     hipGraphNode_t keygen_node = nullptr;
     GraphKey key{};
+};
+
+// What one frame depends on apart from the context's learnt state. run() fills it once; a frame whose data-dependent
+// capacities turn out too small (coarse lists, bucket sort, tile instances) is re-run from its lane's copy, so that it
+// produces the SAME outputs even if a setter (bgs_set_output_srgb8 / _rgba16f / _packed_only / _debug_flags /
+// _srgb8_target) was called while it was in flight.
+struct FrameInputs {
+    const bgs_cloud* cloud = nullptr;   // (cleared by bgs_cloud_free)
+    bgs_view view{};
+    bgs_settings settings{};
+    bool render = false, allow_graph = false;
+    uint32_t* srgb8_target = nullptr;   // bgs_set_srgb8_target: the frame's own packed-image destination (renders only)
+    bool output_srgb8 = false, output_rgba16f = false, packed_only = false;
+    uint32_t debug_flags = 0;
+    uint64_t kind = 0;                  // frame_kind() (0: a bgs_sort)
+    bool force_passes = false;          // the digit passes, not the bucket sort: a re-run of a frame whose bucket sort gave up
+};
+
+// Every choice of one frame (plan_frame, bgs_frame.hip): enqueue_frame allocates, binds and issues it, finish_lane reads
+// it back when the frame is complete.
+struct FramePlan {
+    FrameParams fp{};               // what keygen hands the frame's kernels (debug flags, sRGB8 target, sort path included)
+    bool render = false, scan = false, surfel = false, culled_tail = true;   // (culled_tail: keygen writes the culled tail)
+    uint32_t n = 0, places = 0, rec_bytes = 0, cloud_format = 0;
+    // depth sort: bucket or digit passes; 256 * bucket_sub buckets (the sub of the splitter slot's table); the quantile
+    // table the frame LEAVES has 256 * split_sub_out - 1 keys; the slot (-1: none, or a guessed table) and its epoch
+    bool bucket = false, wide = false;
+    uint32_t bucket_sub = 1, split_sub_out = 1;
+    int split_slot = -1;
+    uint64_t split_epoch = 0;
+    uint32_t edges[4] = {6, 8, 16, 32}, level = 1, sup_edge = 8, num_st = 0;   // supertiles
+    bool large = false, wide_bin = false, want_srgb8 = false;
+    int sort_blocks = 0, bin_blocks = 0, binning_blocks = 0;
+    uint32_t out_format = 0, ntiles = 0;
+    bool raster_cleans = false;     // the rasteriser zeroes the scratch region and reports the Control block (FrameCleanup)
+    RasterInst raster{};            // the instantiation launch_raster_scan launches
+    // heavy-tile strips; leaves tile costs / draws in cost order / makes that order anew; the kind of the cost plane
+    // behind its order, whose saturation counts the frame reports (0: none); may replay a captured graph
+    bool heavy = false, cost = false, ordered = false, refresh = false, graph_ok = false;
+    uint64_t sat_kind = 0;
 };
 
 // Everything one in-flight frame owns.
@@ -116,7 +156,6 @@ struct Lane {
     // frames of other lanes can still be reading the one this lane's previous frame completed
     uint8_t* heavy[2] = {nullptr, nullptr};
     uint32_t heavy_tiles = 0, heavy_parity = 0;  // heavy[heavy_parity] is what the lane's NEXT frame writes; flipped when a frame COMPLETES
-    uint8_t* pending_heavy_out = nullptr;  // what the pending frame's rasteriser writes (null: no feedback from this frame)
     // The feedback the lane's next dense frame consumes: the buffer its most recently COMPLETED dense frame wrote (any
     // view: a stale list costs balance, never pixels — every tile is drawn exactly once, by its regular wave or by a
     // strip workgroup, whichever the list it reads says). Per LANE: a lane's frames run one after the other, so the
@@ -127,12 +166,10 @@ struct Lane {
     // per-tile cost feedback (kernels.h TileCost), the same life cycle as the heavy-tile lists: cost[cost_parity] is what
     // the lane's next frame writes, cost_done what its most recently completed frame wrote; `order` is made of
     // cost_done at the start of a frame and read by that frame's rasteriser only
-    uint64_t in_kind = 0;  // frame_kind() of the lane's frame
     bool ready = false;   // the lane's frame is complete but nobody has taken it yet (bgs_pipeline_pop): a frame finished early, see bgs_ctx::kinds
     uint16_t* cost[2] = {nullptr, nullptr};
     uint16_t* order = nullptr;
     uint32_t cost_tiles = 0, cost_parity = 0;
-    uint16_t* pending_cost_out = nullptr;
     const uint16_t* cost_done = nullptr;
     uint32_t cost_done_grid = 0;
     uint32_t order_grid = 0xFFFFFFFFu, order_age = 0;   // the grid `order` is a permutation for; frames drawn with it since it was made
@@ -153,31 +190,11 @@ struct Lane {
     uint32_t frames_timed = 0;  // timed frames since the last stats read-back
 
     bool pending = false;  // a frame is enqueued whose Control block has not been checked yet
-    bool pending_render = false, pending_scan = false, pending_bucket = false;
-    bool pending_culled_written = true;  // keygen wrote the culled tail (bgs_sort, RasterizeMode::Depth)
-    uint32_t pending_coarse_cap = 0, pending_level = 1, pending_edges[4] = {6, 8, 16, 32};
-    bool force_onesweep = false;       // the pending frame is a re-run of one whose bucket sort gave up
-    int pending_split_slot = -1;       // splitter slot the pending bucket-sort frame used (-1: a guessed table)
-    uint32_t pending_split_sub = 1;    // the quantile table the pending frame LEAVES has 256 * sub - 1 keys
+    FrameInputs in;        // what the lane's frame was enqueued with (a re-run enqueues it again)
+    FramePlan plan;        // ... and the choices it was enqueued with
+    uint32_t pending_coarse_cap = 0;   // entries per supertile list the pending frame was given
     uint64_t cost_done_kind = 0;       // kind of the frame that left cost_done
     uint64_t order_kind = 0;           // kind of the frame whose cost plane the lane's order (and its saturation counts) was made of
-    bool pending_midround = false;     // the pending frame ran the mid-round-exit rasteriser
-    uint64_t pending_sat_kind = 0;     // = order_kind when the pending frame's clean-up reports those counts (0: it does not)
-    uint64_t pending_split_epoch = 0;
-    // what the pending frame was enqueued with: a frame whose data-dependent capacities turn out too
-    // small (coarse lists, bucket sort, tile instances) is re-run on its lane when it is completed
-    const bgs_cloud* in_cloud = nullptr;
-    bgs_view in_view{};
-    bgs_settings in_settings{};
-    uint32_t* in_srgb8_target = nullptr;
-    bool in_allow_graph = false;
-    // ... and the context state it was enqueued under: a re-run must produce the SAME outputs even if a setter
-    // (bgs_set_output_srgb8 / _rgba16f / _packed_only / _debug_flags) was called while the frame was in flight —
-    // a caller's bgs_set_srgb8_target buffer is sized for the format the frame was enqueued with
-    bool in_output_srgb8 = false, in_output_rgba16f = false, in_packed_only = false;
-    uint32_t in_debug_flags = 0;
-    uint32_t pending_n = 0, pending_places = 0, pending_num_st = 0, pending_rec_bytes = 0, pending_cloud_format = 0;
-    uint32_t pending_w = 0, pending_h = 0, pending_tx = 0, pending_ty = 0;
     uint64_t seq = 0;  // enqueue sequence number (to find the oldest pending lane)
 
     const uint2* last_sorted = nullptr;
@@ -222,7 +239,7 @@ struct bgs_ctx {
     uint32_t draw_hint = 0;
     bool draw_hint_valid = false;
     uint32_t draw_shrink_votes = 0;
-    uint32_t sup_level = 1;  // supertile edge level of the next frames (see enqueue_frame)
+    uint32_t sup_level = 1;  // supertile edge level of the next frames (see plan_frame)
     // Bucket sort (one launch instead of four digit passes) is used while a completed frame's quantile keys
     // are known, the draw count fits the bucket geometry, and it has not just failed.
     // Splitter tables: the quantile keys of completed frames' sorted lists, kept per "view slot" — a context that
@@ -251,7 +268,6 @@ struct bgs_ctx {
     uint32_t bucket_block = 0;        // frames to stay on the onesweep passes after a bucket-sort overflow
     uint32_t bucket_fail_streak = 0;  // tables in a row that overflowed on their first use
     uint32_t list_shrink_votes = 0;   // completed frames in a row whose lists would fit a much smaller capacity
-    bool rerun_onesweep = false;      // set while finish_lane re-enqueues a frame whose bucket sort gave up
     uint64_t bucket_frames = 0, onesweep_frames = 0;  // frames enqueued on either sort path (incl. re-runs)
     uint64_t reruns_sort = 0, reruns_lists = 0, reruns_instances = 0, level_changes = 0;
     // entries per supertile list the next frames allocate (grown from the longest list seen; a frame whose
@@ -303,6 +319,7 @@ int finish_lane(bgs_ctx* ctx, Lane& L);                        // completes the 
 int finish_all(bgs_ctx* ctx);                                  // ... every lane's
 int collect_stats(bgs_ctx* ctx);
 int ensure_scratch(bgs_ctx* ctx, Lane& L, uint32_t n, uint64_t inst_cap);
+int enqueue_frame(bgs_ctx* ctx, Lane& L, const FrameInputs& in);
 int ensure_entries(bgs_ctx* ctx, Lane& L, uint32_t n);
 int run(bgs_ctx* ctx, const bgs_cloud* cloud, const bgs_view* view, const bgs_settings* s, bool render);   // bgs_sort / bgs_render
 extern int g_queue_holders_mode;           // bgs_set_queue_holders

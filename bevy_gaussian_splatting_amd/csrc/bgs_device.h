@@ -181,6 +181,8 @@ constexpr uint32_t CONTROL_HEADER_WORDS = 12;  // draw_count .. saturated_tiles_
 constexpr uint32_t RECT_EMPTY = 0x000000FFu;
 constexpr uint32_t MAX_SUPERTILES = 256;  // coarse bins ride the 256-wide chained scan
 constexpr uint32_t MAX_SUPERTILES_PER_AXIS = 32;  // column / row masks of project_bin
+// the rasteriser's variants (render_kernels.hip): oriented quads, 3D-gaussian bounding boxes, surfels
+constexpr int RV_OBB = 0, RV_AABB3D = 1, RV_SURFEL = 2;
 // Supertiles are squares of E x E tiles, E any integer (6 at 1080p: 20 x 12 = 240 bins): tile / E as
 // (tile * M) >> 16 with M = 65536 / E + 1, exact for tile < 256 and E <= 32.
 inline uint32_t supertile_mul(uint32_t edge) { return 65536u / edge + 1u; }

@@ -209,10 +209,10 @@ uint32_t pow2_ceil(uint64_t v) { return pow2_ceil_u32(v); }
 // Supertile lists: `num_st` lists of `cap` (rank, tile rect) entries each. `cap` follows the longest list
 // seen so far (ctx->coarse_cap_hint, never more than n: a list holds each rank at most once); a frame
 // that overflows a list is detected when it completes (coarse_total > cap) and re-run with larger lists.
-int ensure_coarse(bgs_ctx* ctx, Lane& L, uint32_t n, uint32_t num_st, uint32_t* cap_out) {
+int ensure_coarse(bgs_ctx* ctx, Lane& L, uint32_t n, uint32_t num_st, uint32_t debug_flags, uint32_t* cap_out) {
     const uint32_t n1 = std::max<uint32_t>(n, 1);
     if (ctx->coarse_cap_hint == 0)
-        ctx->coarse_cap_hint = (ctx->debug_flags & 0x100000u) ? 64u : std::max<uint32_t>(pow2_ceil(n1 / 64u), 4096u);  // a first guess: a frame that outgrows it is re-run
+        ctx->coarse_cap_hint = (debug_flags & BGS_DEBUG_SMALL_LISTS) ? 64u : std::max<uint32_t>(pow2_ceil(n1 / 64u), 4096u);  // a first guess: a frame that outgrows it is re-run
     const uint32_t want = std::min<uint32_t>(n1, ctx->coarse_cap_hint);
     const size_t need = (size_t)num_st * want;
     // (grown when too small; a lane keeps what it has when the hint falls — a context that alternates between
@@ -230,8 +230,8 @@ int ensure_coarse(bgs_ctx* ctx, Lane& L, uint32_t n, uint32_t num_st, uint32_t* 
         L.coarse_entries = need;
     }
     // everything that is allocated is used (a lane that grew for an earlier frame keeps its longer lists;
-    // not under debug flag 0x100000, which exists to exercise the overflow path)
-    *cap_out = (ctx->debug_flags & 0x100000u) ? want : (uint32_t)std::min<size_t>(L.coarse_entries / num_st, n1);
+    // not under BGS_DEBUG_SMALL_LISTS, which exists to exercise the overflow path)
+    *cap_out = (debug_flags & BGS_DEBUG_SMALL_LISTS) ? want : (uint32_t)std::min<size_t>(L.coarse_entries / num_st, n1);
     return BGS_OK;
 }
 
@@ -342,9 +342,6 @@ int validate(bgs_ctx* ctx, const bgs_cloud* cloud, const bgs_view* view, const b
     return BGS_OK;
 }
 
-int enqueue_frame(bgs_ctx* ctx, Lane& L, const bgs_cloud* cloud, const bgs_view* view, const bgs_settings* s,
-                  bool render, bool allow_graph);
-
 // camera pose of a view: world position and viewing direction (-Z of the view frame)
 void view_pose(const bgs_view* v, float pos[3], float fwd[3]) {
     for (int k = 0; k < 3; ++k) { pos[k] = v->world_from_view[12 + k]; fwd[k] = -v->world_from_view[8 + k]; }
@@ -354,7 +351,7 @@ void view_pose(const bgs_view* v, float pos[3], float fwd[3]) {
 
 // The splitter slot that fits a frame (same cloud, sort mode and model transform, camera within 5 % of the
 // slot's reach and 10 degrees of its direction), or -1.
-int find_splitter_slot(bgs_ctx* ctx, const bgs_cloud* cloud, const bgs_view* view, const bgs_settings* s) {
+int find_splitter_slot(const bgs_ctx* ctx, const bgs_cloud* cloud, const bgs_view* view, const bgs_settings* s) {
     float pos[3], fwd[3];
     view_pose(view, pos, fwd);
     int best = -1;
@@ -403,6 +400,253 @@ void switch_kind(bgs_ctx* ctx, uint64_t kind) {
     ctx->cur_kind = kind;
 }
 
+// What a completed frame's Control block says about the size of its work: tile instances (BINNING_SCAN: the
+// supertile lists' entries) and the longest supertile list.
+struct FrameTotals { uint64_t instances = 0; uint32_t longest = 0; };
+
+FrameTotals frame_totals(const FramePlan& p, const Control& h) {
+    FrameTotals t;
+    t.instances = (uint64_t)h.instance_total_lo | ((uint64_t)h.instance_total_hi << 32);
+    if (p.render && p.scan) {
+        t.instances = 0;
+        for (uint32_t i = 0; i < p.num_st; ++i) {
+            t.instances += h.coarse_total[i];
+            t.longest = std::max(t.longest, h.coarse_total[i]);
+        }
+    }
+    return t;
+}
+
+// finish_lane, step 1: nothing a frame that tripped the device watchdog left behind is trusted: not its counters, not
+// the scratch region
+int check_watchdog(bgs_ctx* ctx, Lane& L) {
+    const Control& h = *L.h_ctl;
+    if (!h.error) return BGS_OK;
+    L.scratch_clean = false;
+    ctx->draw_hint_valid = false;
+    for (auto& sl : ctx->split_slots) sl.epoch = 0;
+    return fail(ctx, BGS_EINTERNAL, "device watchdog tripped (look-back spin bound), code " + std::to_string(h.error));
+}
+
+// finish_lane, step 2: the capacities that depend on the data. *rerun: the frame must be run again.
+int check_capacities(bgs_ctx* ctx, Lane& L, const FrameTotals& t, int attempt, bool* rerun) {
+    const FramePlan& p = L.plan;
+    const Control& h = *L.h_ctl;
+    *rerun = false;
+    if (p.bucket && h.sort_overflow) {
+        // A bucket over capacity (1): the view changed faster than the splitters follow; the table is dropped
+        // and the re-run (always on the digit passes) delivers a fresh one. Frames already in flight
+        // with the same stale table fail for the same reason, so only a table NEWER than the last failed one
+        // counts towards the back-off (three such tables in a row: 7, 15, ... 255 frames on the passes).
+        // One key value far too often (2): no table can split that; 256 frames on the passes.
+        if (p.split_slot >= 0 && ctx->split_slots[p.split_slot].epoch == p.split_epoch)
+            ctx->split_slots[p.split_slot].epoch = 0;  // drop the table
+        if (h.sort_overflow & 2u) {
+            ctx->bucket_block = 256u;
+        } else if (p.split_epoch > ctx->split_failed_epoch) {
+            ctx->bucket_fail_streak = std::min(ctx->bucket_fail_streak + 1u, 8u);
+            if (ctx->bucket_fail_streak >= 3u) ctx->bucket_block = (1u << ctx->bucket_fail_streak) - 1u;
+        }
+        ctx->split_failed_epoch = std::max(ctx->split_failed_epoch, p.split_epoch);
+        ctx->reruns_sort += 1;
+        L.in.force_passes = true;   // stays for every further attempt of this frame
+        *rerun = true;
+    } else if (p.bucket) {
+        ctx->bucket_fail_streak = 0;
+    }
+    if (p.render && p.scan) {
+        // the capacity the next allocations aim at follows the longest list SEEN (25 % head-room, power of
+        // two): up at once, down only after 64 completed frames in a row that would fit an eighth of it
+        const uint32_t want = std::max<uint32_t>(pow2_ceil((uint64_t)t.longest + t.longest / 4), 4096u);
+        if (p.level == ctx->sup_level) {
+            if (want > ctx->coarse_cap_hint) {
+                ctx->coarse_cap_hint = want;
+                ctx->list_shrink_votes = 0;
+            } else if ((uint64_t)want * 8u <= ctx->coarse_cap_hint) {
+                if (++ctx->list_shrink_votes >= 64u) { ctx->coarse_cap_hint = want * 2u; ctx->list_shrink_votes = 0; }
+            } else {
+                ctx->list_shrink_votes = 0;
+            }
+        }
+        if (t.longest > L.pending_coarse_cap) {  // this frame dropped entries
+            if (want > ctx->coarse_cap_hint) ctx->coarse_cap_hint = want;
+            *rerun = true;
+            ctx->reruns_lists += 1;
+        }
+    }
+    if (p.render && !p.scan && h.overflow) {
+        // BINNING_SORT overflow: grow to the next power of two with 25 % headroom
+        if (t.instances > MAX_INSTANCE_CAPACITY)
+            return fail(ctx, BGS_ECAPACITY,
+                        "frame needs " + std::to_string(t.instances) + " tile instances, above the 2^30 limit");
+        uint64_t cap = MIN_INSTANCE_CAPACITY;
+        while (cap < t.instances + t.instances / 4) cap <<= 1;
+        cap = std::min(cap, MAX_INSTANCE_CAPACITY);
+        int rc = ensure_instances(ctx, L, cap);
+        if (rc != BGS_OK) return rc;
+        ctx->reruns_instances += 1;
+        *rerun = true;
+    }
+    // test hook: every BINNING_SCAN frame is run twice, as if a capacity had been too small — exercises the re-run path
+    // (same lane, same inputs, the buffers of the first attempt) under any pipeline state
+    if ((L.in.debug_flags & BGS_DEBUG_RERUN_EVERY_FRAME) && attempt == 0 && p.render && p.scan) *rerun = true;
+    return BGS_OK;
+}
+
+// finish_lane, step 3a: the completed frame's heavy-tile and cost feedback is what the lane's next dense frames read
+// (null after a frame that left none); its saturation counts move its kind's mid-round-exit choice
+void learn_feedback(bgs_ctx* ctx, Lane& L) {
+    const FramePlan& p = L.plan;
+    const Control& h = *L.h_ctl;
+    const uint32_t grid = (uint32_t)p.fp.tiles_x | ((uint32_t)p.fp.tiles_y << 16);
+    // only now does the lane's next frame write the OTHER buffer: a re-run wrote the one its failed attempt wrote,
+    // never the completed frame's list it was reading
+    L.heavy_done = p.heavy ? L.heavy[L.heavy_parity] : nullptr;
+    L.heavy_done_grid = grid;
+    if (p.heavy) L.heavy_parity ^= 1u;
+    L.cost_done = p.cost ? L.cost[L.cost_parity] : nullptr;
+    L.cost_done_kind = L.in.kind;
+    L.cost_done_grid = grid;
+    // what the cost plane behind the lane's tile order said: the share of the frame's tile work that was in tiles which
+    // ended saturated (tile_order_kernel sums, this frame's clean-up block reports; x 0x7FFF)
+    if (p.sat_kind && h.saturated_tiles_prev != 0xFFFFFFFFu) {
+        const auto kit = ctx->kinds.find(p.sat_kind);
+        if (kit != ctx->kinds.end()) {
+            const double share = (double)h.saturated_tiles_prev / (double)0x7FFF;
+            if (share >= bgs_ctx::MIDROUND_ON) kit->second.midround = true;
+            else if (share <= bgs_ctx::MIDROUND_OFF) kit->second.midround = false;
+        }
+    }
+    if (p.cost) L.cost_parity ^= 1u;
+}
+
+// finish_lane, step 3b: the draw-count hint (up at once; down only after 64 completed frames in a row at under a quarter
+// of it: a context that cycles through cameras seeing different shares of the cloud keeps one hint — and one captured
+// graph per lane)
+void learn_draw_hint(bgs_ctx* ctx, uint32_t draw_count) {
+    if (!ctx->draw_hint_valid || draw_count > ctx->draw_hint) {
+        ctx->draw_hint = (uint32_t)std::min<uint64_t>((uint64_t)draw_count + draw_count / 8 + 1024, 0xFFFFFFFFull);
+        ctx->draw_hint_valid = true;
+        ctx->draw_shrink_votes = 0;
+    } else if ((uint64_t)draw_count * 4 < ctx->draw_hint) {
+        if (++ctx->draw_shrink_votes >= 64u) {
+            ctx->draw_hint = (uint32_t)std::min<uint64_t>((uint64_t)draw_count * 2 + 1024, 0xFFFFFFFFull);
+            ctx->draw_shrink_votes = 0;
+        }
+    } else {
+        ctx->draw_shrink_votes = 0;
+    }
+}
+
+// finish_lane, step 3c: the frame's sorted list is good: its quantile keys balance the buckets of the next frames of its
+// view. bucket() is only monotone for an ascending table, so that is checked, not assumed
+void learn_splitters(bgs_ctx* ctx, const Lane& L) {
+    const FramePlan& p = L.plan;
+    const Control& h = *L.h_ctl;
+    const uint32_t nkeys = BUCKET_COUNT * p.split_sub_out - 1u;
+    if (p.places != 4 || h.draw_count < BUCKET_COUNT || !splitters_ascending(h.splitters, nkeys) || !L.in.cloud) return;
+    int slot = find_splitter_slot(ctx, L.in.cloud, &L.in.view, &L.in.settings);
+    if (slot < 0) {  // a view not seen lately: take an empty slot, else the least recently used one
+        slot = 0;
+        for (int i = 0; i < bgs_ctx::SPLITTER_SLOTS; ++i) {
+            if (!ctx->split_slots[i].epoch) { slot = i; break; }
+            if (ctx->split_slots[i].last_used < ctx->split_slots[slot].last_used) slot = i;
+        }
+    }
+    auto& sl = ctx->split_slots[slot];
+    std::memcpy(sl.table.key, h.splitters, nkeys * sizeof(uint32_t));   // what the clean-up wrote
+    sl.table.sub = p.split_sub_out;   // (256 * sub - 1 quantile keys: what the frame's clean-up was asked for)
+    sl.cloud = L.in.cloud;
+    sl.n = p.n;
+    sl.sort_mode = L.in.settings.sort_mode;
+    std::memcpy(sl.transform, L.in.settings.transform, sizeof sl.transform);
+    view_pose(&L.in.view, sl.pos, sl.fwd);
+    std::memcpy(sl.clip_from_view, L.in.view.clip_from_view, sizeof sl.clip_from_view);
+    sl.viewport_wh[0] = L.in.view.viewport[2];
+    sl.viewport_wh[1] = L.in.view.viewport[3];
+    // the median key is ~bits(dist^2) of the median drawable splat (keys are 0xFFFFFFFF - bits)
+    const uint32_t mid_bits = 0xFFFFFFFFu - h.splitters[BUCKET_COUNT * p.split_sub_out / 2 - 1];
+    float d2;
+    std::memcpy(&d2, &mid_bits, 4);
+    sl.reach = (d2 > 0.0f && d2 < 3.0e38f) ? std::sqrt(d2) : 1.0f;
+    sl.epoch = ++ctx->split_epoch;
+    sl.last_used = ctx->seq;
+}
+
+// finish_lane, step 3d: list entries per visible splat (~1.2 when splats are smaller than a supertile, 15-20 when they
+// span many) -> the supertile level of the next frames (next_supertile_level, frame_params.h; relative to the level THIS
+// frame ran at, not to ctx->sup_level, which frames completed in the meantime may already have moved). Returns whether
+// the level moved.
+bool learn_level(bgs_ctx* ctx, const Lane& L, const FrameTotals& t) {
+    const FramePlan& p = L.plan;
+    const uint32_t lv = p.level;
+    double longer = 1.0;
+    // (a level whose edge equals a lower level's is that lower level: moving between them is not a change — no new
+    // capacity prediction, no vote reset, no level_changes)
+    const uint32_t target = canonical_supertile_level(
+        next_supertile_level((double)t.instances / (double)L.h_ctl->visible_count, lv, p.edges, &longer), p.edges);
+    const auto kit = ctx->kinds.find(L.in.kind);
+    // (a settled kind remembers its level for the next time the context comes back to it)
+    if (kit != ctx->kinds.end()) kit->second.sup_level = target;
+    // a frame of ANOTHER kind than the one the context is on by now (kinds alternate while frames are in flight): its
+    // verdict belongs to its own kind, not to ctx->sup_level
+    if (L.in.kind != ctx->cur_kind || target == lv) return target != lv;
+    if (ctx->sup_level != target) {
+        // lists of another level: predicted from THIS frame's longest list (coarser supertiles hold longer lists:
+        // entries scale with the ratio, lists with the area), never from the old hint
+        const double predicted = (double)t.longest * (target > lv ? longer : 1.0) * 1.25;
+        ctx->coarse_cap_hint = std::max<uint32_t>(pow2_ceil((uint64_t)std::min(predicted, 1.0e9)), 4096u);
+        ctx->list_shrink_votes = 0;
+        ctx->level_changes += 1;
+        ctx->sup_level = target;
+    }
+    return true;
+}
+
+// finish_lane, step 4: the lane's counters of the completed frame
+void fill_stats(const bgs_ctx* ctx, Lane& L, const FrameTotals& t) {
+    const FramePlan& p = L.plan;
+    const Control& h = *L.h_ctl;
+    const bool render = p.render, scan = p.scan;
+    bgs_stats& stt = L.result;
+    std::memset(&stt, 0, sizeof stt);
+    stt.regrow_count = ctx->regrow_count;
+    stt.splat_count = p.n;
+    stt.visible_count = render ? h.visible_count : h.draw_count;
+    stt.draw_count = h.draw_count;
+    stt.sort_path = p.bucket ? 1u : 0u;
+    stt.list_capacity = (render && scan) ? L.pending_coarse_cap : 0u;
+    stt.instance_count = render ? t.instances : 0;
+    stt.instance_capacity = L.inst_cap;
+    stt.list_entries_allocated = (render && scan) ? (uint64_t)L.coarse_entries : 0;
+    stt.strip_tiles = (render && scan) ? h.strip_tiles : 0u;
+    stt.tile_saturation = (render && scan && p.sat_kind && h.saturated_tiles_prev != 0xFFFFFFFFu)
+                              ? (0x10000u | (h.saturated_tiles_prev & 0x7FFFu) | (p.raster.mode != 0 ? 0x80000000u : 0u)) : 0u;
+    stt.tiles_x = render ? (uint32_t)p.fp.tiles_x : 0;
+    stt.tiles_y = render ? (uint32_t)p.fp.tiles_y : 0;
+    stt.depth_passes = p.places;
+    stt.tile_passes = (render && !scan) ? 2 : 0;
+    stt.binning_mode = scan ? BINNING_SCAN : BINNING_SORT;
+    // SURVEY 8(d) algorithmic bytes. SURVEY's bytes_sort is N*16 + N*8 + k*N*16; the partition
+    // in keygen means only the D drawable pairs go through the k passes, so that is counted
+    // (the bucket sort moves each drawable pair twice: scatter + gather, sorted write: k = 1.5).
+    const uint64_t N = p.n, k = p.places, D = h.draw_count;
+    // (keygen reads N positions and writes the D drawable pairs; the N - D culled pairs only in frames that
+    // have a reader for them)
+    uint64_t bytes = N * 16 + D * 8 + (p.culled_tail ? (N - D) * 8 : 0) + (p.bucket ? D * 24 : k * D * 16);
+    if (render) {
+        const uint64_t B = p.cloud_format == CLOUD_F16 ? 128 : 240, R = p.rec_bytes, V = h.visible_count, I = t.instances;
+        const uint64_t P = (uint64_t)(uint32_t)p.fp.width * (uint32_t)p.fp.height;
+        if (scan)  // coarse entries (rank + tile rect, 8 B): written once, read by the tiles of their supertile
+            bytes += V * (B - 16) + V * R + V * 8 + V * 8 + I * 8 + I * 8 + P * 16;   // (+ the 4-byte tile rect per rank, written by project_kernel and read by bin_kernel)
+        else
+            bytes += V * (B - 16) + V * R + I * 8 + 2 * I * 16 + I * (4 + R) + P * 16;
+    }
+    stt.algorithmic_bytes = bytes;
+    L.has_result = true;
+    L.result_kind = (uint8_t)(!render ? 1 : (scan ? 2 : 3));
+}
+
 // Complete the frame pending on a lane: wait for it, check the watchdog word of the Control copy that
 // travelled with the frame, and RE-RUN the frame on its lane if a data-dependent capacity turned out too
 // small (a supertile list, the bucket sort's geometry, the tile-instance buffer): nobody has seen the
@@ -410,271 +654,42 @@ void switch_kind(bgs_ctx* ctx, uint64_t kind) {
 int finish_lane(bgs_ctx* ctx, Lane& L) {
     L.ready = false;
     for (int attempt = 0; L.pending; ++attempt) {
-        hipStream_t st = L.stream;
         HIP_TRY(ctx, hipEventSynchronize(L.done));  // not the stream: a sibling lane's frame may be queued behind
         L.pending = false;
-        const bool render = L.pending_render, scan = L.pending_scan;
-        const uint32_t n = L.pending_n, places = L.pending_places, num_st = L.pending_num_st;
-        const size_t rec_bytes = L.pending_rec_bytes;
-
+        int rc = check_watchdog(ctx, L);
+        if (rc != BGS_OK) return rc;
+        const FramePlan& p = L.plan;
         const Control& h = *L.h_ctl;
-        if (h.error) {
-            // nothing a tripped frame left behind is trusted: not its counters, not the scratch region
-            L.scratch_clean = false;
-            ctx->draw_hint_valid = false;
-            for (auto& sl : ctx->split_slots) sl.epoch = 0;
-            return fail(ctx, BGS_EINTERNAL,
-                        "device watchdog tripped (look-back spin bound), code " + std::to_string(h.error));
-        }
-        // ---- capacities that depend on the data ----
-        bool rerun = false, sort_gave_up = false;
-        if (L.pending_bucket && h.sort_overflow) {
-            sort_gave_up = true;
-            // A bucket over capacity (1): the view changed faster than the splitters follow; the table is dropped
-            // and the re-run below (always on the digit passes) delivers a fresh one. Frames already in flight
-            // with the same stale table fail for the same reason, so only a table NEWER than the last failed one
-            // counts towards the back-off (three such tables in a row: 7, 15, ... 255 frames on the passes).
-            // One key value far too often (2): no table can split that; 256 frames on the passes.
-            if (L.pending_split_slot >= 0 && ctx->split_slots[L.pending_split_slot].epoch == L.pending_split_epoch)
-                ctx->split_slots[L.pending_split_slot].epoch = 0;  // drop the table
-            if (h.sort_overflow & 2u) {
-                ctx->bucket_block = 256u;
-            } else if (L.pending_split_epoch > ctx->split_failed_epoch) {
-                ctx->bucket_fail_streak = std::min(ctx->bucket_fail_streak + 1u, 8u);
-                if (ctx->bucket_fail_streak >= 3u) ctx->bucket_block = (1u << ctx->bucket_fail_streak) - 1u;
-            }
-            ctx->split_failed_epoch = std::max(ctx->split_failed_epoch, L.pending_split_epoch);
-            ctx->reruns_sort += 1;
-            rerun = true;
-        } else if (L.pending_bucket) {
-            ctx->bucket_fail_streak = 0;
-        }
-        uint64_t total = (uint64_t)h.instance_total_lo | ((uint64_t)h.instance_total_hi << 32);
-        uint32_t pending_longest = 0;
-        if (render && scan) {
-            total = 0;
-            uint32_t longest = 0;
-            for (uint32_t i = 0; i < num_st; ++i) {
-                total += h.coarse_total[i];
-                longest = std::max(longest, h.coarse_total[i]);
-            }
-            // the capacity the next allocations aim at follows the longest list SEEN (25 % head-room, power of
-            // two): up at once, down only after 64 completed frames in a row that would fit an eighth of it
-            const uint32_t want = std::max<uint32_t>(pow2_ceil((uint64_t)longest + longest / 4), 4096u);
-            if (L.pending_level == ctx->sup_level) {
-                if (want > ctx->coarse_cap_hint) {
-                    ctx->coarse_cap_hint = want;
-                    ctx->list_shrink_votes = 0;
-                } else if ((uint64_t)want * 8u <= ctx->coarse_cap_hint) {
-                    if (++ctx->list_shrink_votes >= 64u) { ctx->coarse_cap_hint = want * 2u; ctx->list_shrink_votes = 0; }
-                } else {
-                    ctx->list_shrink_votes = 0;
-                }
-            }
-            if (longest > L.pending_coarse_cap) {  // this frame dropped entries
-                if (want > ctx->coarse_cap_hint) ctx->coarse_cap_hint = want;
-                rerun = true;
-                ctx->reruns_lists += 1;
-            }
-            pending_longest = longest;
-        }
-        if (render && !scan && h.overflow) {
-            // BINNING_SORT overflow: grow to the next power of two with 25 % headroom
-            if (total > MAX_INSTANCE_CAPACITY)
-                return fail(ctx, BGS_ECAPACITY,
-                            "frame needs " + std::to_string(total) + " tile instances, above the 2^30 limit");
-            uint64_t cap = MIN_INSTANCE_CAPACITY;
-            while (cap < total + total / 4) cap <<= 1;
-            cap = std::min(cap, MAX_INSTANCE_CAPACITY);
-            int rc = ensure_instances(ctx, L, cap);
-            if (rc != BGS_OK) return rc;
-            ctx->reruns_instances += 1;
-            rerun = true;
-        }
-        // test hook (debug flag 0x8000000): every BINNING_SCAN frame is run twice, as if a capacity had been too small —
-        // exercises the re-run path (same lane, same inputs, the buffers of the first attempt) under any pipeline state
-        if ((L.in_debug_flags & 0x8000000u) && attempt == 0 && render && scan) rerun = true;
+        const FrameTotals t = frame_totals(p, h);
+        bool rerun = false;
+        if ((rc = check_capacities(ctx, L, t, attempt, &rerun)) != BGS_OK) return rc;
         if (rerun) {
             if (attempt >= 8) return fail(ctx, BGS_ECAPACITY, "frame kept overflowing its buffers");
             ctx->regrow_count += 1;
-            uint32_t* const next_target = ctx->next_srgb8_target;  // belongs to a frame not enqueued yet
-            ctx->next_srgb8_target = L.in_srgb8_target;
-            if (sort_gave_up) L.force_onesweep = true;  // stays for every further attempt of this frame
-            ctx->rerun_onesweep = L.force_onesweep;
-            // the re-run sees the output state the frame was ENQUEUED with, not whatever the setters say by now
-            const bool now_srgb8 = ctx->output_srgb8, now_f16 = ctx->output_rgba16f, now_packed = ctx->packed_only;
-            const uint32_t now_flags = ctx->debug_flags;
-            ctx->output_srgb8 = L.in_output_srgb8;
-            ctx->output_rgba16f = L.in_output_rgba16f;
-            ctx->packed_only = L.in_packed_only;
-            ctx->debug_flags = L.in_debug_flags;
-            int rc = enqueue_frame(ctx, L, L.in_cloud, &L.in_view, &L.in_settings, render, L.in_allow_graph);
-            ctx->output_srgb8 = now_srgb8;
-            ctx->output_rgba16f = now_f16;
-            ctx->packed_only = now_packed;
-            ctx->debug_flags = now_flags;
-            ctx->rerun_onesweep = false;
-            ctx->next_srgb8_target = next_target;
-            if (rc != BGS_OK) return rc;
+            if ((rc = enqueue_frame(ctx, L, L.in)) != BGS_OK) return rc;
             continue;
         }
 
-        L.force_onesweep = false;
-        bool level_moved = false;
-        if (render && scan) {   // the completed frame's heavy-tile feedback (null after a frame that left none) is what the next dense frames read
-            L.heavy_done = L.pending_heavy_out;
-            L.heavy_done_grid = L.pending_tx | (L.pending_ty << 16);
-            // only now does the lane's next frame write the OTHER buffer: a re-run (above) wrote the one its failed
-            // attempt wrote, never the completed frame's list it was reading
-            if (L.pending_heavy_out) L.heavy_parity ^= 1u;
-            L.cost_done = L.pending_cost_out;
-            L.cost_done_kind = L.in_kind;
-            L.cost_done_grid = L.pending_tx | (L.pending_ty << 16);
-            // what the cost plane behind the lane's tile order said: the share of the frame's tile work that was in tiles which
-            // ended saturated (tile_order_kernel sums, this frame's clean-up block reports; x 0x7FFF)
-            if (L.pending_sat_kind && h.saturated_tiles_prev != 0xFFFFFFFFu) {
-                const auto kit = ctx->kinds.find(L.pending_sat_kind);
-                if (kit != ctx->kinds.end()) {
-                    const double share = (double)h.saturated_tiles_prev / (double)0x7FFF;
-                    if (share >= bgs_ctx::MIDROUND_ON) kit->second.midround = true;
-                    else if (share <= bgs_ctx::MIDROUND_OFF) kit->second.midround = false;
-                }
-            }
-            if (L.pending_cost_out) L.cost_parity ^= 1u;
+        if (p.render && p.scan) learn_feedback(ctx, L);
+        learn_draw_hint(ctx, h.draw_count);
+        learn_splitters(ctx, L);
+        const bool level_moved = p.render && p.scan && h.visible_count > 0 && learn_level(ctx, L, t);
+        // the kind is settled: a frame of it ran with everything it needed
+        if (p.render && p.scan && attempt == 0 && !level_moved && L.in.kind) {
+            if (ctx->kinds.size() >= (1u << 20)) ctx->kinds.clear();   // (12 MB of kinds: a host that hashes noise into its settings)
+            ctx->kinds[L.in.kind].sup_level = p.level;
         }
-        // (up at once; down only after 64 completed frames in a row at under a quarter of it: a context that
-        // cycles through cameras seeing different shares of the cloud keeps one hint — and one captured graph
-        // per lane)
-        if (!ctx->draw_hint_valid || h.draw_count > ctx->draw_hint) {
-            ctx->draw_hint = (uint32_t)std::min<uint64_t>((uint64_t)h.draw_count + h.draw_count / 8 + 1024, 0xFFFFFFFFull);
-            ctx->draw_hint_valid = true;
-            ctx->draw_shrink_votes = 0;
-        } else if ((uint64_t)h.draw_count * 4 < ctx->draw_hint) {
-            if (++ctx->draw_shrink_votes >= 64u) {
-                ctx->draw_hint = (uint32_t)std::min<uint64_t>((uint64_t)h.draw_count * 2 + 1024, 0xFFFFFFFFull);
-                ctx->draw_shrink_votes = 0;
-            }
-        } else {
-            ctx->draw_shrink_votes = 0;
-        }
-        if (places == 4 && h.draw_count >= BUCKET_COUNT) {
-            // the frame's sorted list is good: its quantile keys balance the buckets of the next frames.
-            // bucket() is only monotone for an ascending table, so that is checked, not assumed
-            if (splitters_ascending(h.splitters, BUCKET_COUNT * L.pending_split_sub - 1u) && L.in_cloud) {
-                int slot = find_splitter_slot(ctx, L.in_cloud, &L.in_view, &L.in_settings);
-                if (slot < 0) {  // a view not seen lately: take an empty slot, else the least recently used one
-                    slot = 0;
-                    for (int i = 0; i < bgs_ctx::SPLITTER_SLOTS; ++i) {
-                        if (!ctx->split_slots[i].epoch) { slot = i; break; }
-                        if (ctx->split_slots[i].last_used < ctx->split_slots[slot].last_used) slot = i;
-                    }
-                }
-                auto& sl = ctx->split_slots[slot];
-                std::memcpy(sl.table.key, h.splitters, (BUCKET_COUNT * L.pending_split_sub - 1u) * sizeof(uint32_t));   // what the clean-up wrote
-                sl.table.sub = L.pending_split_sub;   // (256 * sub - 1 quantile keys: what the frame's clean-up was asked for)
-                sl.cloud = L.in_cloud;
-                sl.n = n;
-                sl.sort_mode = L.in_settings.sort_mode;
-                std::memcpy(sl.transform, L.in_settings.transform, sizeof sl.transform);
-                view_pose(&L.in_view, sl.pos, sl.fwd);
-                std::memcpy(sl.clip_from_view, L.in_view.clip_from_view, sizeof sl.clip_from_view);
-                sl.viewport_wh[0] = L.in_view.viewport[2];
-                sl.viewport_wh[1] = L.in_view.viewport[3];
-                // the median key is ~bits(dist^2) of the median drawable splat (keys are 0xFFFFFFFF - bits)
-                const uint32_t mid_bits = 0xFFFFFFFFu - h.splitters[BUCKET_COUNT * L.pending_split_sub / 2 - 1];
-                float d2;
-                std::memcpy(&d2, &mid_bits, 4);
-                sl.reach = (d2 > 0.0f && d2 < 3.0e38f) ? std::sqrt(d2) : 1.0f;
-                sl.epoch = ++ctx->split_epoch;
-                sl.last_used = ctx->seq;
-            }
-        }
+
         // after a render only the drawable prefix of the list is materialised (the culled tail stays
         // in its side buffer); bgs_sort appends it so that callers get the reference's full list
-        L.last_sorted_n = render ? h.draw_count : n;
-        if (!render && h.draw_count < n) {
+        L.last_sorted_n = p.render ? h.draw_count : p.n;
+        if (!p.render && h.draw_count < p.n) {
             // bgs_sort contract: one contiguous list, culled entries last (ascending index)
             HIP_TRY(ctx, hipMemcpyAsync(const_cast<uint2*>(L.last_sorted) + h.draw_count, L.culled,
-                                        (size_t)(n - h.draw_count) * sizeof(uint2), hipMemcpyDeviceToDevice, st));
-            HIP_TRY(ctx, hipStreamSynchronize(st));
+                                        (size_t)(p.n - h.draw_count) * sizeof(uint2), hipMemcpyDeviceToDevice, L.stream));
+            HIP_TRY(ctx, hipStreamSynchronize(L.stream));
         }
-        if (render && scan && h.visible_count > 0) {
-            // list entries per visible splat: ~1.2 when splats are smaller than a supertile, 15-20 when they
-            // span many -> the supertile level of the next frames (next_supertile_level, frame_params.h; relative
-            // to the level THIS frame ran at, not to ctx->sup_level, which frames completed in the meantime may
-            // already have moved)
-            const uint32_t lv = L.pending_level;
-            double longer = 1.0;
-            uint32_t target = next_supertile_level((double)total / (double)h.visible_count, lv, L.pending_edges, &longer);
-            // a level whose edge equals a lower level's is that lower level (enqueue_frame canonicalises the same way):
-            // moving between them is not a change — no new capacity prediction, no vote reset, no level_changes
-            while (target > 1 && L.pending_edges[target - 1] == L.pending_edges[target]) --target;
-            if (L.in_kind != ctx->cur_kind) {
-                // a frame of ANOTHER kind than the one the context is on by now (kinds alternate while frames are in
-                // flight): its verdict belongs to its own kind, not to ctx->sup_level
-                const auto kit = ctx->kinds.find(L.in_kind);
-                if (kit != ctx->kinds.end()) kit->second.sup_level = target;
-                level_moved = target != lv;
-            } else {
-            if (target != lv && ctx->sup_level != target) {
-                // lists of another level: predicted from THIS frame's longest list (coarser supertiles hold
-                // longer lists: entries scale with the ratio, lists with the area), never from the old hint
-                const double predicted = (double)pending_longest * (target > lv ? longer : 1.0) * 1.25;
-                ctx->coarse_cap_hint = std::max<uint32_t>(pow2_ceil((uint64_t)std::min(predicted, 1.0e9)), 4096u);
-                ctx->list_shrink_votes = 0;
-            }
-            if (target != lv) { if (ctx->sup_level != target) ctx->level_changes += 1; ctx->sup_level = target; level_moved = true; }
-            // (a settled kind remembers its level for the next time the context comes back to it)
-            const auto kit = ctx->kinds.find(L.in_kind);
-            if (kit != ctx->kinds.end()) kit->second.sup_level = target;
-            }
-        }
-
-        // the kind is settled: a frame of it ran with everything it needed
-        if (render && scan && attempt == 0 && !level_moved && L.in_kind) {
-            if (ctx->kinds.size() >= (1u << 20)) ctx->kinds.clear();   // (12 MB of kinds: a host that hashes noise into its settings)
-            ctx->kinds[L.in_kind].sup_level = L.pending_level;
-        }
-
-        bgs_stats& stt = L.result;
-        std::memset(&stt, 0, sizeof stt);
-        stt.regrow_count = ctx->regrow_count;
-        stt.splat_count = n;
-        stt.visible_count = render ? h.visible_count : h.draw_count;
-        stt.draw_count = h.draw_count;
-        stt.sort_path = L.pending_bucket ? 1u : 0u;
-        stt.list_capacity = (render && scan) ? L.pending_coarse_cap : 0u;
-        stt.instance_count = render ? total : 0;
-        stt.instance_capacity = L.inst_cap;
-        stt.list_entries_allocated = (render && scan) ? (uint64_t)L.coarse_entries : 0;
-        stt.strip_tiles = (render && scan) ? h.strip_tiles : 0u;
-        stt.tile_saturation = (render && scan && L.pending_sat_kind && h.saturated_tiles_prev != 0xFFFFFFFFu)
-                                  ? (0x10000u | (h.saturated_tiles_prev & 0x7FFFu) | (L.pending_midround ? 0x80000000u : 0u)) : 0u;
-        stt.tiles_x = render ? L.pending_tx : 0;
-        stt.tiles_y = render ? L.pending_ty : 0;
-        stt.depth_passes = places;
-        stt.tile_passes = (render && !scan) ? 2 : 0;
-        stt.binning_mode = scan ? BINNING_SCAN : BINNING_SORT;
-        {
-            // SURVEY 8(d) algorithmic bytes. SURVEY's bytes_sort is N*16 + N*8 + k*N*16; the partition
-            // in keygen means only the D drawable pairs go through the k passes, so that is counted
-            // (the bucket sort moves each drawable pair twice: scatter + gather, sorted write: k = 1.5).
-            const uint64_t N = n, k = places, D = h.draw_count;
-            // (keygen reads N positions and writes the D drawable pairs; the N - D culled pairs only in frames that
-            // have a reader for them)
-            uint64_t bytes = N * 16 + D * 8 + (L.pending_culled_written ? (N - D) * 8 : 0) + (L.pending_bucket ? D * 24 : k * D * 16);
-            if (render) {
-                const uint64_t B = L.pending_cloud_format == CLOUD_F16 ? 128 : 240, R = rec_bytes, V = h.visible_count, I = total;
-                const uint64_t P = (uint64_t)L.pending_w * L.pending_h;
-                if (scan)  // coarse entries (rank + tile rect, 8 B): written once, read by the tiles of their supertile
-                    bytes += V * (B - 16) + V * R + V * 8 + V * 8 + I * 8 + I * 8 + P * 16;   // (+ the 4-byte tile rect per rank, written by project_kernel and read by bin_kernel)
-                else
-                    bytes += V * (B - 16) + V * R + I * 8 + 2 * I * 16 + I * (4 + R) + P * 16;
-            }
-            stt.algorithmic_bytes = bytes;
-        }
-        L.has_result = true;
-        L.result_kind = (uint8_t)(!render ? 1 : (scan ? 2 : 3));
+        fill_stats(ctx, L, t);
     }
     return BGS_OK;
 }
@@ -741,69 +756,206 @@ int collect_stats(bgs_ctx* ctx) {
     return BGS_OK;
 }
 
-// Enqueue one frame on lane L. Returns without waiting; the caller decides when to finish the lane.
-int enqueue_frame(bgs_ctx* ctx, Lane& L, const bgs_cloud* cloud, const bgs_view* view, const bgs_settings* s,
-                  bool render, bool allow_graph) {
-    FrameParams fp{};
-    fill_frame_params(cloud->ptrs.n, view, s, fp);
-    fp.debug = ctx->debug_flags;
-    fp.srgb8_target = render ? (uint64_t)(uintptr_t)ctx->next_srgb8_target : 0;
-    const uint32_t n = fp.n;
-    const uint32_t places = depth_places(s);
-    const bool surfel = render && fp.gaussian_mode == 0u && fp.aabb != 0u;
-    const size_t rec_bytes = surfel ? sizeof(RecordSurfel) : sizeof(Record);
-
-    int rc;
-    if ((rc = lane_create(ctx, L)) != BGS_OK) return rc;
-    if ((rc = ensure_entries(ctx, L, n)) != BGS_OK) return rc;
-    const bool scan = ctx->binning == BINNING_SCAN;
-    // what finish_lane re-runs the frame with (view / settings may already live in the lane: a re-run)
-    L.in_cloud = cloud;
-    if (view != &L.in_view) L.in_view = *view;
-    if (s != &L.in_settings) L.in_settings = *s;
-    L.in_srgb8_target = render ? ctx->next_srgb8_target : nullptr;
-    L.in_allow_graph = allow_graph;
-    L.in_output_srgb8 = ctx->output_srgb8;
-    L.in_output_rgba16f = ctx->output_rgba16f;
-    L.in_packed_only = ctx->packed_only;
-    L.in_debug_flags = ctx->debug_flags;
+// Every choice of one frame, from its inputs and the context's learnt state. Allocates nothing and changes no state.
+FramePlan plan_frame(const bgs_ctx& ctx, const Lane& L, const FrameInputs& in) {
+    FramePlan p;
+    const uint32_t flags = in.debug_flags;
+    const bgs_settings* s = &in.settings;
+    FrameParams& fp = p.fp;
+    fill_frame_params(in.cloud->ptrs.n, &in.view, s, fp);
+    fp.debug = flags;
+    fp.srgb8_target = (uint64_t)(uintptr_t)in.srgb8_target;
+    const uint32_t n = p.n = fp.n;
+    p.places = depth_places(s);
+    p.render = in.render;
+    p.scan = ctx.binning == BINNING_SCAN;
+    p.surfel = in.render && fp.gaussian_mode == 0u && fp.aabb != 0u;
+    p.rec_bytes = p.surfel ? sizeof(RecordSurfel) : sizeof(Record);
+    p.cloud_format = in.cloud->ptrs.format;
+    // The culled tail (index order, 8 B per culled splat: 7 of the 24 MB keygen moves on the headline frame) has two
+    // readers: bgs_sort's full list and RasterizeMode::Depth (sorted[N-1] of the full list, gaussian.wgsl:331-340).
+    // Every other rendered frame skips the writes; bgs_sorted_entries_device_ptr after a render has always meant the
+    // drawable prefix only.
+    p.culled_tail = !in.render || s->rasterize_mode == BGS_RASTERIZE_DEPTH;
 
     // Depth-sort path. The bucket sort needs 32-bit keys (shorter keys are mostly ties, which it ranks
     // quadratically), a draw count that fits its geometry (a bucket holds <= BUCKET_CAP pairs) and the key
     // range of a recent frame; it is checked on the device and the frame re-run with the digit passes when
     // it does not work out (then bucket_block keeps the following frames on the passes for a while).
-    // Debug flags: 0x80000 never, 0x200000 also with a guessed range (no completed frame yet).
-    const bool guess = (ctx->debug_flags & 0x200000u) != 0u;
-    const int split_slot = (places == 4 && n > 0) ? find_splitter_slot(ctx, cloud, view, s) : -1;
+    const bool hint = ctx.draw_hint_valid;
+    const int slot = (p.places == 4 && n > 0) ? find_splitter_slot(&ctx, in.cloud, &in.view, s) : -1;
     // Geometry: NARROW buckets (BUCKET_CAP pairs, 256-thread workgroups) while 256 * BUCKET_SUB_KERNARG of them at BUCKET_TARGET
     // pairs hold the list (1.57 M pairs: every frame of the headline's kind), WIDE ones (BUCKET_CAP_WIDE, 1024 threads, 128 KB
     // of LDS) past that: a 5 M-pair list is 768 wide buckets instead of 2816 narrow ones, which keygen's scatter reached with
-    // 1.5 pairs per (tile, bucket). Debug flag 0x100: narrow whatever the length (round 5's geometry, A/B), 0x800: wide
-    // whatever the length (tests).
+    // 1.5 pairs per (tile, bucket).
     const uint32_t narrow_max = BUCKET_COUNT * BUCKET_SUB_KERNARG * BUCKET_TARGET;
-    const bool wide_out = ((ctx->draw_hint_valid && ctx->draw_hint > narrow_max && !(ctx->debug_flags & 0x100u)) || (ctx->debug_flags & 0x800u));
-    const uint32_t cap_out = wide_out ? BUCKET_CAP_WIDE : BUCKET_CAP, target_out = wide_out ? BUCKET_TARGET_WIDE : BUCKET_TARGET;
-    bool bucket = places == 4 && n > 0 && !(ctx->debug_flags & 0x80000u) && ctx->bucket_block == 0 && !ctx->rerun_onesweep &&
-                  ((split_slot >= 0 && ctx->draw_hint_valid) || guess) &&
-                  (!ctx->draw_hint_valid || ctx->draw_hint <= BUCKET_MAX * (cap_out / 4u) * 3u);
-    if (ctx->bucket_block > 0 && places == 4) ctx->bucket_block -= 1;
+    p.wide = (hint && ctx.draw_hint > narrow_max && !(flags & BGS_DEBUG_BUCKETS_NARROW)) || (flags & BGS_DEBUG_BUCKETS_WIDE);
+    const uint32_t cap_out = p.wide ? BUCKET_CAP_WIDE : BUCKET_CAP, target_out = p.wide ? BUCKET_TARGET_WIDE : BUCKET_TARGET;
+    p.bucket = p.places == 4 && n > 0 && !(flags & BGS_DEBUG_NO_BUCKET_SORT) && ctx.bucket_block == 0 && !in.force_passes &&
+               ((slot >= 0 && hint) || (flags & BGS_DEBUG_GUESSED_SPLITTERS)) &&
+               (!hint || ctx.draw_hint <= BUCKET_MAX * (cap_out / 4u) * 3u);
     // Buckets: 256 * sub, as many as keep a bucket near its target (narrow: sub = 1 up to 524 k drawable pairs — the
-    // headline's 120 k —, 2 at 1 M, 3 at 1.5 M; wide: 1 up to 2.1 M, 3 at 5 M, 16 up to 50 M; debug flag 0x200: at least 3
-    // whatever the length, 0x400: at least 5 — the device-table path — to exercise the finer tables on small lists). A frame
-    // sorts with the table its slot HOLDS (table.sub), in the geometry the hint asks for: a table that is too coarse for
-    // the list in that geometry is not used, and every completed frame leaves a table of the sub the current hint asks for
-    // (split_sub_out).
-    uint32_t split_sub_out = 1u;
-    if (ctx->draw_hint_valid)
-        split_sub_out = std::min<uint32_t>(std::max<uint32_t>((ctx->draw_hint + BUCKET_COUNT * target_out - 1u) / (BUCKET_COUNT * target_out), 1u), BUCKET_SUB_MAX);
-    if (ctx->debug_flags & 0x200u) split_sub_out = std::max<uint32_t>(split_sub_out, BUCKET_SUB_KERNARG);
-    if (ctx->debug_flags & 0x400u) split_sub_out = std::max<uint32_t>(split_sub_out, 5u);
-    uint32_t bucket_sub = 1u;
-    if (bucket && split_slot >= 0) {
-        bucket_sub = std::min<uint32_t>(std::max<uint32_t>(ctx->split_slots[split_slot].table.sub, 1u), BUCKET_SUB_MAX);
-        if (ctx->draw_hint_valid && ctx->draw_hint > BUCKET_COUNT * bucket_sub * (cap_out / 4u) * 3u) bucket = false;   // too coarse a table
+    // headline's 120 k —, 2 at 1 M, 3 at 1.5 M; wide: 1 up to 2.1 M, 3 at 5 M, 16 up to 50 M). A frame sorts with the table
+    // its slot HOLDS (table.sub), in the geometry the hint asks for: a table that is too coarse for the list in that
+    // geometry is not used, and every completed frame leaves a table of the sub the current hint asks for (split_sub_out).
+    if (hint)
+        p.split_sub_out = std::min<uint32_t>(std::max<uint32_t>((ctx.draw_hint + BUCKET_COUNT * target_out - 1u) / (BUCKET_COUNT * target_out), 1u), BUCKET_SUB_MAX);
+    if (flags & BGS_DEBUG_SPLIT_SUB_3) p.split_sub_out = std::max<uint32_t>(p.split_sub_out, BUCKET_SUB_KERNARG);
+    if (flags & BGS_DEBUG_SPLIT_SUB_5) p.split_sub_out = std::max<uint32_t>(p.split_sub_out, 5u);
+    if (p.bucket && slot >= 0) {
+        p.bucket_sub = std::min<uint32_t>(std::max<uint32_t>(ctx.split_slots[slot].table.sub, 1u), BUCKET_SUB_MAX);
+        if (hint && ctx.draw_hint > BUCKET_COUNT * p.bucket_sub * (cap_out / 4u) * 3u) p.bucket = false;   // too coarse a table
     }
-    if (bucket && bucket_sub > BUCKET_SUB_KERNARG && !L.d_split_keys) {   // the lane's device table + its pinned staging
+    if (p.bucket && slot >= 0) { p.split_slot = slot; p.split_epoch = ctx.split_slots[slot].epoch; }
+    fp.sort_path = p.bucket ? 1u : 0u;
+
+    // Supertile edge (in tiles): four levels (supertile_edges, frame_params.h). Every tile scans its supertile's whole
+    // list, so small splats want short lists (level 0: scene-like frame 91.7 -> 87.9 us against level 1); a splat that
+    // spans many supertiles costs one list entry, one append and a share of the ballots in each, while a tile that
+    // saturates after ~60 hits does not mind scanning three times as many candidates (dense frame, 6 lanes on 3 streams:
+    // 13.3 k frames/s at level 1, 14.6 k at level 2, 15.3 k at level 3). Images do not depend on the level; it follows
+    // the entries-per-visible-splat ratio of the completed frames (finish_lane) unless a debug flag forces one.
+    supertile_edges((uint32_t)fp.tiles_x, (uint32_t)fp.tiles_y, p.edges);
+    uint32_t level = ctx.sup_level;
+    if (flags & BGS_DEBUG_LEVEL_0) level = 0;
+    else if (flags & BGS_DEBUG_LEVEL_1) level = 1;
+    else if (flags & BGS_DEBUG_LEVEL_2) level = 2;
+    else if (flags & BGS_DEBUG_LEVEL_3) level = 3;
+    p.level = canonical_supertile_level(level, p.edges);
+    // tile / edge by reciprocal multiply is exact for edges <= 32 (supertile_div)
+    p.sup_edge = supertile_bins_fit((uint32_t)fp.tiles_x, (uint32_t)fp.tiles_y, p.edges[p.level]) ? p.edges[p.level] : p.edges[1];
+    p.num_st = (((uint32_t)fp.tiles_x + p.sup_edge - 1) / p.sup_edge) * (((uint32_t)fp.tiles_y + p.sup_edge - 1) / p.sup_edge);
+
+    // Grids: only the D drawable entries are sorted, and D is known on the device only; launching a block per N/tile
+    // would start ~6x more blocks than tiles, each queueing for a ticket just to leave. Project grid: one block per 256
+    // ranks of the D drawable entries when that fits the chip (two 170-190-VGPR blocks are resident per CU; the kernel
+    // strides over the rest); bin grid: one block per 1024 ranks (every block then takes exactly one ticket).
+    p.large = n > (4u << 20);
+    p.wide_bin = ctx.depth == 1;
+    p.sort_blocks = ctx.num_cus * 4;
+    p.bin_blocks = ctx.num_cus * 3;
+    p.binning_blocks = ctx.num_cus * 4;
+    if (hint && !(flags & BGS_DEBUG_NO_DRAW_HINT)) {
+        const uint64_t want = (uint64_t)ctx.draw_hint / sort_tile_size(p.large) + 8;
+        p.sort_blocks = (int)std::min<uint64_t>((uint64_t)p.sort_blocks, std::max<uint64_t>(want, 32));
+        p.bin_blocks = (int)std::min<uint64_t>((uint64_t)p.bin_blocks, std::max<uint64_t>((uint64_t)ctx.draw_hint / 256 + 8, 32));
+        p.binning_blocks = (int)std::min<uint64_t>((uint64_t)p.binning_blocks, std::max<uint64_t>((uint64_t)ctx.draw_hint / 1024 + 4, 16));
+    }
+    p.want_srgb8 = in.render && (in.output_srgb8 || in.output_rgba16f || in.srgb8_target);
+    p.out_format = !p.want_srgb8 ? 0u : ((in.output_rgba16f ? OUT_RGBA16F : OUT_SRGB8) |
+                                         ((in.packed_only && p.scan) ? OUT_SKIP_F32 : 0u));
+
+    // Rasteriser (raster_instantiation, frame_params.h): the mid-round exit for dense frames (supertile level >= 2), and
+    // for frames of a kind whose saturating tiles hold a good share of the work (KindState::midround, from the cost planes)
+    // when several frames are in flight: the trained-like 1 M frame 5.75 -> 6.31 k frames/s with 8 lanes, but ALONE on the
+    // chip its launch ends with its longest lists' serial chains, which do not saturate and only pay the checks (231 -> 272 us)
+    p.raster_cleans = in.render && p.scan && fp.tiles_x > 0 && fp.tiles_y > 0 && !(flags & BGS_DEBUG_NO_RASTER_CLEANUP);
+    bool kind_midround = false;
+    if (ctx.depth > 1) { const auto kit = ctx.kinds.find(in.kind); if (kit != ctx.kinds.end()) kind_midround = kit->second.midround; }
+    p.raster = raster_instantiation(fp, p.level, kind_midround, ctx.depth, flags);
+    p.ntiles = (uint32_t)(fp.tiles_x * fp.tiles_y);
+    // the feedback buffers alternate with every completed frame: not under frame graphs
+    const bool feedback = p.raster_cleans && !(in.allow_graph && ctx.use_graphs) && p.ntiles <= 65535u;
+    // Dense frames (the mid-round exit at supertile level >= 2) leave, and use, the heavy-tile feedback (kernels.h
+    // HeavyFeedback) — when ONE frame is in flight (pipeline depth 1): the strip workgroups cut the launch's tail (dense
+    // 1 M frame: raster 49.4 -> 45.3 us, the heaviest tiles' serial chains split four ways), but with several frames in
+    // flight that tail is filled by the other lanes' kernels anyway and the extra workgroups and the flag load only cost
+    // (20.6 -> 20.0 k frames/s with 8 lanes; profiles/r3_notes.md). Not with the tile trace.
+    p.heavy = feedback && p.raster.mode == 1 && p.level >= 2u && !ctx.tile_trace &&
+              (ctx.depth == 1 || (flags & BGS_DEBUG_STRIPS_ANY_DEPTH)) && !(flags & BGS_DEBUG_NO_STRIPS);
+    // Tile costs (kernels.h TileCost): every BINNING_SCAN frame leaves them, and a frame with more tile waves than the
+    // chip holds at once draws its raster workgroups in the order made of a completed frame's costs; the tile trace shows
+    // it. Unlike the heavy-tile strips it pays with frames in flight too, if little (+0.6 % dense, +0.9 % surfel
+    // frames/s; alone on the chip 6-21 % of the rasteriser's time).
+    p.cost = feedback && (ctx.depth == 1 || !(flags & BGS_DEBUG_NO_TILE_COST_PIPELINED)) && !(flags & BGS_DEBUG_NO_TILE_COST);
+    if (p.cost && p.ntiles > (uint32_t)(ctx.num_cus * 4 * raster_scan_waves_per_simd(fp))) {
+        // L.order holds a permutation of this grid's workgroups from the moment it was first made for the grid
+        // (order_grid); it is made again from the newest completed costs every TILE_ORDER_REFRESH-th frame. (ensure_cost
+        // keeps the lane's buffers, and what they hold, unless the grid outgrew them.)
+        const uint32_t grid = (uint32_t)fp.tiles_x | ((uint32_t)fp.tiles_y << 16);
+        const bool kept = L.cost[0] && p.ntiles <= L.cost_tiles;
+        const bool have_costs = kept && L.cost_done && L.cost_done != L.cost[L.cost_parity] && L.cost_done_grid == grid;
+        const bool have_order = kept && L.order_grid == grid;
+        p.refresh = have_costs && (!have_order || L.order_age + 1u >= TILE_ORDER_REFRESH || (flags & BGS_DEBUG_ORDER_EVERY_FRAME));
+        p.ordered = p.refresh || have_order;
+    }
+    // (a frame that makes the order makes its saturation counts anew, ahead of its own kernels)
+    p.sat_kind = !p.ordered ? 0 : (p.refresh ? L.cost_done_kind : L.order_kind);
+    // ---- opt-in (bgs_set_graphs): a steady-state BINNING_SCAN frame as a hipGraph, captured once per
+    // (lane, Control parity), then replayed with ONE node update — keygen's arguments carry the new
+    // FrameParams, every other kernel reads them from the copy keygen leaves in device memory.
+    // Measured: 7 launches cost 19 us of host time (30 us with stage events), a replay 10 us; on the
+    // GPU a replayed frame is ~5 % SLOWER than the same launches issued directly (178 vs 171 us per
+    // frame back to back on one stream), so it is for hosts that cannot spare the CPU time.
+    p.graph_ok = in.allow_graph && ctx.use_graphs && p.raster_cleans && p.bucket_sub <= BUCKET_SUB_KERNARG &&
+                 !(flags & BGS_DEBUG_NO_GRAPHS) && !ctx.tile_trace;
+    return p;
+}
+
+// What the launches of a captured frame depend on besides FrameParams: the plan's choices and the buffers they were
+// bound to. Nothing that changes from frame to frame (the splitter slot, its epoch: keygen's node update carries them).
+GraphKey graph_key(const FramePlan& p, const FrameInputs& in, const Lane& L, const KeygenLaunch& kg, uint32_t coarse_cap) {
+    GraphKey key;
+    std::memset(&key, 0, sizeof key);
+    const FrameParams& fp = p.fp;
+    const void* planes[6] = {in.cloud->ptrs.position_visibility, in.cloud->ptrs.packed, nullptr, nullptr, nullptr, nullptr};
+    std::memcpy(key.cloud, planes, sizeof planes);
+    const void* bufs[11] = {L.entries[0], L.entries[1], L.culled, L.records, L.coarse, L.fb, L.fb8, L.scratch, L.d_fp,
+                            L.h_ctl_dev, L.bucket_slots};   // (L.rects lives and dies with L.entries)
+    std::memcpy(key.bufs, bufs, sizeof bufs);
+    key.n = p.n; key.format = p.cloud_format; key.places = p.places; key.sort_mode = in.settings.sort_mode;
+    key.gaussian_mode = fp.gaussian_mode; key.aabb = fp.aabb;
+    key.any_mode = (fp.rasterize_mode != RASTERIZE_COLOR || fp.draw_mode != 0u) ? 1u : 0u;
+    key.srgb8 = p.out_format;
+    key.debug_flags = in.debug_flags;
+    key.width = fp.width; key.height = fp.height;
+    key.sort_blocks = p.bucket ? 0 : p.sort_blocks;  // the bucket sort's grid is fixed
+    key.bin_blocks = p.bin_blocks * 4096 + p.binning_blocks;   // (the bin kernel's shape follows the pipeline depth, as keygen's does: key.keygen_threads)
+    key.keygen_blocks = (int32_t)kg.blocks; key.keygen_func = kg.func; key.keygen_threads = kg.threads;
+    key.wide_bin = p.wide_bin ? 1u : 0u;
+    const RasterInst& r = p.raster;
+    key.raster_variant = r.samples | (r.depth ? 0x100u : 0u) | (r.overlay ? 0x200u : 0u) | (r.mode == 1 ? 0x400u : r.mode == 2 ? 0x800u : 0u);
+    key.split_sub = p.split_sub_out;   // (round 5's advisor: a replay across a 524 k-pair step of the hint left a table of the captured sub under the new sub's label)
+    key.sup_edge = p.sup_edge;
+    key.scratch_bytes = L.scratch_bytes; key.scratch_inst_cap = L.scratch_inst_cap; key.scratch_n = L.scratch_n;
+    key.coarse_cap = coarse_cap;
+    key.sort_path = p.bucket ? (p.bucket_sub | (p.wide ? 0x100u : 0u)) : 0u;   // (the bucket sort's grid and instantiation and keygen's dynamic LDS follow it)
+    return key;
+}
+
+// Replay the lane's graph of this key (keygen's node updated to this frame), or capture `issue` into a new one.
+template <class Issue>
+int launch_graph(bgs_ctx* ctx, Lane& L, const GraphKey& key, KeygenLaunch& kg, Issue&& issue) {
+    FrameGraph& G = L.graph[L.ctl_parity];
+    if (G.exec && std::memcmp(&G.key, &key, sizeof key) == 0) {
+        HIP_TRY(ctx, kg.update_node(G.exec, G.keygen_node));
+        ctx->graph_replays += 1;
+    } else {
+        graph_destroy(G);
+        HIP_TRY(ctx, hipStreamBeginCapture(L.stream, hipStreamCaptureModeThreadLocal));
+        const hipError_t ie = issue();
+        const hipError_t ce = hipStreamEndCapture(L.stream, &G.graph);
+        size_t roots = 1;
+        if (ie != hipSuccess || ce != hipSuccess || !G.graph ||
+            hipGraphInstantiate(&G.exec, G.graph, nullptr, nullptr, 0) != hipSuccess ||
+            hipGraphGetRootNodes(G.graph, &G.keygen_node, &roots) != hipSuccess || roots != 1) {
+            graph_destroy(G);
+            (void)hipGetLastError();
+            return fail(ctx, BGS_EHIP, "capturing the frame into a hipGraph failed");
+        }
+        G.key = key;
+        ctx->graph_captures += 1;
+    }
+    HIP_TRY(ctx, hipGraphLaunch(G.exec, L.stream));
+    return BGS_OK;
+}
+
+// The buffers a planned frame needs (allocated or grown); *coarse_cap: the entries per supertile list it gets.
+int ensure_frame_buffers(bgs_ctx* ctx, Lane& L, const FramePlan& p, const FrameInputs& in, uint32_t* coarse_cap) {
+    int rc;
+    if ((rc = lane_create(ctx, L)) != BGS_OK) return rc;
+    if ((rc = ensure_entries(ctx, L, p.n)) != BGS_OK) return rc;
+    if (p.bucket && p.bucket_sub > BUCKET_SUB_KERNARG && !L.d_split_keys) {   // the lane's device table + its pinned staging
         L.d_split_keys = dev_alloc<uint32_t>(BUCKET_MAX);
         void* hp = nullptr;
         if (!L.d_split_keys || hipHostMalloc(&hp, BUCKET_MAX * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) {
@@ -812,60 +964,38 @@ int enqueue_frame(bgs_ctx* ctx, Lane& L, const bgs_cloud* cloud, const bgs_view*
         }
         L.h_split_keys = (uint32_t*)hp;
     }
-    if (bucket) {
-        fp.sort_path = 1u;
-        if ((rc = ensure_bucket_slots(ctx, L, bucket_sub, wide_out)) != BGS_OK) return rc;
-        ctx->bucket_frames += 1;
-    } else if (places > 0) {
-        ctx->onesweep_frames += 1;
-    }
-    // Supertile edge (in tiles): four levels. Level 1 is the smallest power of two >= 8 that keeps the coarse
-    // bins <= 256 and <= 32 per axis (8 at 1080p: 135 bins); level 0 the smallest edge >= 3/4 of it that does
-    // (6 at 1080p: 240 bins); levels 2 and 3 are 2x and 4x level 1 (16 and 32 at 1080p: 40 and 12 bins).
-    // Every tile scans its supertile's whole list, so small splats want short lists (level 0: scene-like frame
-    // 91.7 -> 87.9 us against level 1); a splat that spans many supertiles costs one list entry, one append and
-    // a share of the ballots in each, while a tile that saturates after ~60 hits does not mind scanning three
-    // times as many candidates (dense frame, 6 lanes on 3 streams: 13.3 k frames/s at level 1, 14.6 k at level
-    // 2, 15.3 k at level 3). Images do not depend on the level; it follows the entries-per-visible-splat ratio
-    // of the completed frames (finish_lane). Debug flags force a level: 0x10000 -> 0, 0x8000 -> 1,
-    // 0x400000 -> 2, 0x800000 -> 3.
-    auto bins = [&](uint32_t e, uint32_t& bx, uint32_t& by) {
-        bx = ((uint32_t)fp.tiles_x + e - 1) / e;
-        by = ((uint32_t)fp.tiles_y + e - 1) / e;
-        return bx * by <= MAX_SUPERTILES && bx <= MAX_SUPERTILES_PER_AXIS && by <= MAX_SUPERTILES_PER_AXIS;
-    };
-    uint32_t edge_c = 8, cbx = 0, cby = 0, edge_f = 1, fbx = 0, fby = 0;
-    while (!bins(edge_c, cbx, cby)) edge_c *= 2;
-    // the fine edge stays within 3/4 of the coarse one (no flip-flop between the two rules)
-    edge_f = (3 * edge_c + 3) / 4;
-    while (!bins(edge_f, fbx, fby)) ++edge_f;
-    if (edge_f >= edge_c) { edge_f = edge_c; fbx = cbx; fby = cby; }
-    uint32_t level = ctx->sup_level;
-    if (ctx->debug_flags & 0x10000u) level = 0;
-    else if (ctx->debug_flags & 0x8000u) level = 1;
-    else if (ctx->debug_flags & 0x400000u) level = 2;
-    else if (ctx->debug_flags & 0x800000u) level = 3;
-    // levels whose edges coincide (edge_c >= 16, i.e. targets of ~2048 px and up: levels 2 and 3 both clamp to 32
-    // tiles) are ONE level: the frame runs, and is accounted, at the lowest level with that edge
-    auto level_edge = [&](uint32_t lv) { return lv == 0 ? edge_f : std::min<uint32_t>(edge_c << (lv - 1u), 32u); };
-    while (level > 1 && level_edge(level - 1u) == level_edge(level)) --level;
-    // tile / edge by reciprocal multiply is exact for edges <= 32 (supertile_div)
-    uint32_t sup_edge = level == 0 ? edge_f : std::min<uint32_t>(edge_c << (level - 1u), 32u), sup_bx = 0, sup_by = 0;
-    if (!bins(sup_edge, sup_bx, sup_by)) { sup_edge = edge_c; sup_bx = cbx; sup_by = cby; }
-    const uint32_t num_st = sup_bx * sup_by;
-    uint32_t coarse_cap = 1;  // entries per supertile list
-    if (render) {
-        if (scan) {
-            if ((rc = ensure_coarse(ctx, L, n, num_st, &coarse_cap)) != BGS_OK) return rc;
+    if (p.bucket && (rc = ensure_bucket_slots(ctx, L, p.bucket_sub, p.wide)) != BGS_OK) return rc;
+    if (p.render) {
+        if (p.scan) {
+            if ((rc = ensure_coarse(ctx, L, p.n, p.num_st, in.debug_flags, coarse_cap)) != BGS_OK) return rc;
             if ((rc = ensure_rects(ctx, L)) != BGS_OK) return rc;
         } else {
             if ((rc = ensure_instances(ctx, L, std::max<uint64_t>(L.inst_cap, MIN_INSTANCE_CAPACITY))) != BGS_OK) return rc;
         }
-        if ((rc = ensure_records(ctx, L, (size_t)n * rec_bytes)) != BGS_OK) return rc;
-        if ((rc = ensure_framebuffer(ctx, L, (uint32_t)fp.width, (uint32_t)fp.height, ctx->output_srgb8 || ctx->output_rgba16f)) != BGS_OK) return rc;
+        if ((rc = ensure_records(ctx, L, (size_t)p.n * p.rec_bytes)) != BGS_OK) return rc;
+        if ((rc = ensure_framebuffer(ctx, L, (uint32_t)p.fp.width, (uint32_t)p.fp.height, in.output_srgb8 || in.output_rgba16f)) != BGS_OK) return rc;
     }
-    if ((rc = ensure_scratch(ctx, L, n, L.inst_cap)) != BGS_OK) return rc;
+    if ((rc = ensure_scratch(ctx, L, p.n, L.inst_cap)) != BGS_OK) return rc;
+    if (p.heavy && (rc = ensure_heavy(ctx, L, p.ntiles)) != BGS_OK) return rc;
+    if (p.cost && (rc = ensure_cost(ctx, L, p.ntiles)) != BGS_OK) return rc;
+    return BGS_OK;
+}
 
+// Enqueue one frame on lane L: plan it, allocate, bind, commit its context changes, issue it, and keep its inputs and
+// plan in the lane. Returns without waiting; the caller decides when to finish the lane.
+int enqueue_frame(bgs_ctx* ctx, Lane& L, const FrameInputs& in) {
+    // ---- 1. the frame's choices
+    const FramePlan p = plan_frame(*ctx, L, in);
+    const FrameParams& fp = p.fp;
+    const uint32_t n = p.n, places = p.places, flags = in.debug_flags;
+    const bool render = p.render, scan = p.scan, bucket = p.bucket;
+
+    // ---- 2. buffers
+    uint32_t coarse_cap = 1;  // entries per supertile list
+    int rc = ensure_frame_buffers(ctx, L, p, in, &coarse_cap);
+    if (rc != BGS_OK) return rc;
+
+    // ---- 3. bindings
     hipStream_t st = L.stream;
     const bool need_memset = !L.scratch_clean;  // else the previous frame's rasteriser left it zeroed
     if (need_memset) L.ctl_parity = 0;
@@ -876,7 +1006,70 @@ int enqueue_frame(bgs_ctx* ctx, Lane& L, const bgs_cloud* cloud, const bgs_view*
     uint2* ranges = (uint2*)(L.scratch + L.off_ranges);
     uint32_t* bin_status = (uint32_t*)(L.scratch + L.off_bin_status);
     uint32_t* part_status = (uint32_t*)(L.scratch + L.off_part_status);
+    const size_t depth_tiles = ((size_t)L.scratch_n + sort_tile_size(false) - 1) / sort_tile_size(false) + 1;
+    const uint32_t grid = (uint32_t)fp.tiles_x | ((uint32_t)fp.tiles_y << 16);
+    uint8_t* const heavy_out = p.heavy ? L.heavy[L.heavy_parity] : nullptr;
+    const uint8_t* const heavy_in = (p.heavy && L.heavy_done && L.heavy_done != heavy_out && L.heavy_done_grid == grid) ? L.heavy_done : nullptr;
+    uint16_t* const cost_out = p.cost ? L.cost[L.cost_parity] : nullptr;
+    const uint16_t* const cost_in = p.refresh ? L.cost_done : nullptr;
+    uint16_t* const tile_order = p.ordered ? L.order : nullptr;
+    uint2* const draw_list = L.entries[places & 1u];  // the passes ping-pong from entries[0]
+    // SortMode::Rayon / Std sort ascending on the inverted key; the last step of either path un-inverts it
+    const uint32_t final_xor = (fp.sort_mode == BGS_SORT_RAYON || fp.sort_mode == BGS_SORT_STD) ? 0xFFFFFFFFu : 0u;
 
+    KeygenLaunch kg{};
+    kg.fp = fp;
+    kg.pos = in.cloud->ptrs.position_visibility;
+    kg.entries = L.entries[0];
+    kg.culled = p.culled_tail ? L.culled : nullptr;
+    kg.ctl = ctl;
+    kg.part_status = part_status;
+    kg.places = places;
+    kg.ticket_slot = 7;
+    kg.fp_out = L.d_fp;
+    kg.zero_word = reinterpret_cast<uint32_t*>(heavy_out);   // keygen, the frame's first kernel, zeroes the heavy-tile list's count
+    kg.bucket_slots = L.bucket_slots;
+    kg.bucket_status = depth_status;  // the depth passes' look-back words are free in a bucket-sort frame
+    if (bucket) {
+        if (p.split_slot >= 0) {
+            const SplitterKeys& tk = ctx->split_slots[p.split_slot].table;
+            const uint32_t nkeys = BUCKET_COUNT * p.bucket_sub - 1u;
+            if (p.bucket_sub <= BUCKET_SUB_KERNARG) std::memcpy(kg.split.key, tk.key, nkeys * sizeof(uint32_t));
+            else std::memcpy(L.h_split_keys, tk.key, nkeys * sizeof(uint32_t));   // (the lane's previous frame is complete: nobody reads the staging)
+            kg.split.device_keys = L.d_split_keys;
+        } else {  // BGS_DEBUG_GUESSED_SPLITTERS: equal steps over the 32-bit range (badly balanced)
+            for (uint32_t i = 0; i < BUCKET_COUNT; ++i) kg.split.key[i] = (i + 1u) << 24;
+        }
+        kg.split.sub = p.bucket_sub;
+        kg.split.wide = p.wide ? 1u : 0u;
+    }
+    kg.wide = p.wide_bin;
+    const bool have_keygen = kg.prepare(ctx->num_cus * 4);
+    FrameCleanup cl{};
+    if (p.raster_cleans) {
+        cl.part_status = part_status;
+        cl.depth_status = depth_status;
+        cl.bin_status = bin_status;
+        cl.other_ctl = (Control*)(L.scratch + (L.ctl_parity ? 0 : L.off_ctl1));
+        cl.host_ctl = L.h_ctl_dev;
+        cl.pass_stride = (uint32_t)(depth_tiles * RADIX_BASE);
+        cl.places = bucket ? 0u : places;
+        cl.depth_tile = sort_tile_size(p.large);
+        cl.sorted = draw_list;
+        cl.key_xor = final_xor;
+        cl.split_sub = p.split_sub_out;
+        if (tile_order) cl.order_stats = reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(tile_order) + tile_order_stats_offset(p.ntiles));
+    }
+
+    // ---- 4. the context's and the lane's state
+    if (ctx->bucket_block > 0 && places == 4) ctx->bucket_block -= 1;
+    if (bucket) ctx->bucket_frames += 1;
+    else if (places > 0) ctx->onesweep_frames += 1;
+    if (bucket && p.split_slot >= 0) ctx->split_slots[p.split_slot].last_used = ctx->seq + 1;
+    if (p.cost) ctx->cost_frames += 1;
+    if (p.ordered) ctx->ordered_frames += 1;
+    if (p.refresh) { ctx->order_refreshes += 1; L.order_kind = L.cost_done_kind; L.order_grid = grid; L.order_age = 0; }
+    else if (p.ordered) L.order_age += 1u;
     const bool timed_frame = (ctx->frame_counter++ % ctx->profiling_stride) == 0;
     const int prof = timed_frame ? ctx->profiling : 0;
     const int last_mark = render ? 6 : 2;
@@ -890,157 +1083,13 @@ int enqueue_frame(bgs_ctx* ctx, Lane& L, const bgs_cloud* cloud, const bgs_view*
         if (prof >= 2 || (prof == 1 && (i == 0 || i == last_mark))) (void)hipEventRecord(ev[i], st);
     };
 
-    // ---- what will be launched -------------------------------------------------------------------
-    KeygenLaunch kg{};
-    kg.fp = fp;
-    kg.pos = cloud->ptrs.position_visibility;
-    kg.entries = L.entries[0];
-    // The culled tail (index order, 8 B per culled splat: 7 of the 24 MB keygen moves on the headline frame) has two
-    // readers: bgs_sort's full list and RasterizeMode::Depth (sorted[N-1] of the full list, gaussian.wgsl:331-340).
-    // Every other rendered frame skips the writes; bgs_sorted_entries_device_ptr after a render has always meant the
-    // drawable prefix only.
-    kg.culled = (render && s->rasterize_mode != BGS_RASTERIZE_DEPTH) ? nullptr : L.culled;
-    kg.ctl = ctl;
-    kg.part_status = part_status;
-    kg.places = places;
-    kg.ticket_slot = 7;
-    kg.fp_out = L.d_fp;
-    kg.zero_word = nullptr;   // set below, once the frame's heavy-tile feedback buffer is known
-    kg.bucket_slots = L.bucket_slots;
-    kg.bucket_status = depth_status;  // the depth passes' look-back words are free in a bucket-sort frame
-    L.pending_split_slot = -1;
-    L.pending_split_epoch = 0;
-    L.pending_split_sub = split_sub_out;
-    if (bucket) {
-        if (split_slot >= 0) {
-            const SplitterKeys& tk = ctx->split_slots[split_slot].table;
-            const uint32_t nkeys = BUCKET_COUNT * bucket_sub - 1u;
-            if (bucket_sub <= BUCKET_SUB_KERNARG) std::memcpy(kg.split.key, tk.key, nkeys * sizeof(uint32_t));
-            else std::memcpy(L.h_split_keys, tk.key, nkeys * sizeof(uint32_t));   // (the lane's previous frame is complete: nobody reads the staging)
-            kg.split.device_keys = L.d_split_keys;
-            ctx->split_slots[split_slot].last_used = ctx->seq + 1;
-            L.pending_split_slot = split_slot;
-            L.pending_split_epoch = ctx->split_slots[split_slot].epoch;
-        } else {  // debug flag 0x200000: a guessed table (equal steps over the 32-bit range: badly balanced)
-            for (uint32_t i = 0; i < BUCKET_COUNT; ++i) kg.split.key[i] = (i + 1u) << 24;
-        }
-        kg.split.sub = bucket_sub;
-        kg.split.wide = wide_out ? 1u : 0u;
-    }
-    kg.wide = ctx->depth == 1;
-    const bool have_keygen = kg.prepare(ctx->num_cus * 4);
-    const bool large = n > (4u << 20);
-    const size_t depth_tiles = ((size_t)L.scratch_n + sort_tile_size(false) - 1) / sort_tile_size(false) + 1;
-    const bool hinted = ctx->draw_hint_valid && !(ctx->debug_flags & 0x2000u);
-    int sort_blocks = ctx->num_cus * 4;
-    if (hinted) {
-        // only the D drawable entries are sorted, and D is known on the device only; launching a block
-        // per N/tile would start ~6x more blocks than tiles, each queueing for a ticket just to leave
-        const uint64_t want = (uint64_t)ctx->draw_hint / sort_tile_size(large) + 8;
-        sort_blocks = (int)std::min<uint64_t>((uint64_t)sort_blocks, std::max<uint64_t>(want, 32));
-    }
-    // project grid: one block per 256 ranks of the D drawable entries when that fits the chip (two 170-190-VGPR blocks
-    // are resident per CU; the kernel strides over the rest); bin grid: one block per 1024 ranks (every block then
-    // takes exactly one ticket)
-    int bin_blocks = ctx->num_cus * 3, binning_blocks = ctx->num_cus * 4;
-    if (hinted) {
-        bin_blocks = (int)std::min<uint64_t>((uint64_t)bin_blocks, std::max<uint64_t>((uint64_t)ctx->draw_hint / 256 + 8, 32));
-        binning_blocks = (int)std::min<uint64_t>((uint64_t)binning_blocks, std::max<uint64_t>((uint64_t)ctx->draw_hint / 1024 + 4, 16));
-    }
-    const bool want_srgb8 = render && (ctx->output_srgb8 || ctx->output_rgba16f || ctx->next_srgb8_target);
-    const uint32_t out_format = !want_srgb8 ? 0u : ((ctx->output_rgba16f ? OUT_RGBA16F : OUT_SRGB8) |
-                                                    ((ctx->packed_only && scan) ? OUT_SKIP_F32 : 0u));
-    uint2* const draw_list = L.entries[places & 1u];  // the passes ping-pong from entries[0]
-    // SortMode::Rayon / Std sort ascending on the inverted key; the last step of either path un-inverts it
-    const uint32_t final_xor = (s->sort_mode == BGS_SORT_RAYON || s->sort_mode == BGS_SORT_STD) ? 0xFFFFFFFFu : 0u;
-    FrameCleanup cl{};
-    if (render && scan) {
-        cl.part_status = part_status;
-        cl.depth_status = depth_status;
-        cl.bin_status = bin_status;
-        cl.other_ctl = (Control*)(L.scratch + (L.ctl_parity ? 0 : L.off_ctl1));
-        cl.host_ctl = L.h_ctl_dev;
-        cl.pass_stride = (uint32_t)(depth_tiles * RADIX_BASE);
-        cl.places = bucket ? 0u : places;
-        cl.depth_tile = sort_tile_size(large);
-        cl.sorted = draw_list;
-        cl.key_xor = final_xor;
-        cl.split_sub = split_sub_out;
-        if (ctx->debug_flags & 0x1000u) cl = FrameCleanup{};  // experiment: classic memset + copy path
-    }
-    const bool raster_cleans = render && scan && fp.tiles_x > 0 && fp.tiles_y > 0 && cl.other_ctl != nullptr;
-    // Dense frames (supertile level >= 2: the rasteriser's mid-round-exit instantiation) leave, and use, the heavy-tile
-    // feedback (kernels.h HeavyFeedback) — when ONE frame is in flight (pipeline depth 1): the strip workgroups cut the
-    // launch's tail (dense 1 M frame: raster 49.4 -> 45.3 us, the heaviest tiles' serial chains split four ways), but
-    // with several frames in flight that tail is filled by the other lanes' kernels anyway and the extra workgroups
-    // and the flag load only cost (20.6 -> 20.0 k frames/s with 8 lanes; profiles/r3_notes.md). Not under frame graphs
-    // (the consumed buffer changes with every completed frame), not with the tile trace, not for the surfel variant.
-    // Debug flag 0x2000000 switches it off, 0x4000000 forces it on at any depth (A/B).
-    // (Sample2 / Sample8 and the bounding-box overlay have no mid-round-exit instantiation: launch_raster_scan)
-    // ... and frames of a kind whose saturating tiles hold a good share of the work (KindState::midround, from the cost planes)
-    // when several frames are in flight: the trained-like 1 M frame 5.75 -> 6.31 k frames/s with 8 lanes, but ALONE on the chip
-    // its launch ends with its longest lists' serial chains, which do not saturate and only pay the checks (231 -> 272 us)
-    bool kind_midround = false;
-    if (ctx->depth > 1) { const auto kit = ctx->kinds.find(L.in_kind); if (kit != ctx->kinds.end()) kind_midround = kit->second.midround; }
-    const bool midround_exit = (level >= 2u || kind_midround || (ctx->debug_flags & 0x20000u)) && !(ctx->debug_flags & 0x1000000u) && (fp.sample_count == 1u || fp.sample_count == 4u) &&   // (0x20000: at any level, A/B)
-                               fp.visualize_bbox == 0u;
-    const uint32_t ntiles_frame = (uint32_t)(fp.tiles_x * fp.tiles_y);
-    const bool heavy_ok = render && scan && raster_cleans && midround_exit && level >= 2u && !surfel && !ctx->tile_trace &&
-                          (ctx->depth == 1 || (ctx->debug_flags & 0x4000000u)) &&
-                          !(ctx->debug_flags & 0x2000000u) && !(allow_graph && ctx->use_graphs) && ntiles_frame <= 65535u;
-    uint8_t* heavy_out = nullptr;
-    const uint8_t* heavy_in = nullptr;
-    if (heavy_ok) {
-        if ((rc = ensure_heavy(ctx, L, ntiles_frame)) != BGS_OK) return rc;
-        heavy_out = L.heavy[L.heavy_parity];
-        if (L.heavy_done && L.heavy_done != heavy_out && L.heavy_done_grid == ((uint32_t)fp.tiles_x | ((uint32_t)fp.tiles_y << 16))) heavy_in = L.heavy_done;
-        kg.zero_word = reinterpret_cast<uint32_t*>(heavy_out);   // keygen, the frame's first kernel, zeroes the list's count
-    }
-
-    // Tile costs (kernels.h TileCost): every BINNING_SCAN frame leaves them, and a frame with more tile waves than the
-    // chip holds at once draws its raster workgroups in the order made of a completed frame's costs. Not under frame
-    // graphs (the buffers alternate with every completed frame); the tile trace shows it. Unlike the heavy-tile strips it
-    // pays with frames in flight too, if little (+0.6 % dense, +0.9 % surfel frames/s; alone on the chip 6-21 % of the
-    // rasteriser's time). Debug flag 0x10000000 switches it off, 0x20000000 off for pipeline depths > 1, 0x40000000
-    // makes the order anew with every frame.
-    const bool cost_ok = render && scan && raster_cleans &&
-                         (ctx->depth == 1 || !(ctx->debug_flags & 0x20000000u)) && !(ctx->debug_flags & 0x10000000u) &&
-                         !(allow_graph && ctx->use_graphs) && ntiles_frame <= 65535u;
-    uint16_t* cost_out = nullptr;
-    const uint16_t* cost_in = nullptr;
-    uint16_t* tile_order = nullptr;
-    if (cost_ok) {
-        if ((rc = ensure_cost(ctx, L, ntiles_frame)) != BGS_OK) return rc;
-        cost_out = L.cost[L.cost_parity];
-        const uint32_t grid_now = (uint32_t)fp.tiles_x | ((uint32_t)fp.tiles_y << 16);
-        if (ntiles_frame > (uint32_t)(ctx->num_cus * 4 * raster_scan_waves_per_simd(fp))) {
-            // L.order holds a permutation of this grid's workgroups from the moment it was first made for the grid
-            // (order_grid); it is made again from the newest completed costs every TILE_ORDER_REFRESH-th frame
-            const bool have_costs = L.cost_done && L.cost_done != cost_out && L.cost_done_grid == grid_now;
-            const bool have_order = L.order_grid == grid_now;
-            if (have_costs && (!have_order || L.order_age + 1u >= TILE_ORDER_REFRESH || (ctx->debug_flags & 0x40000000u)))
-                cost_in = L.cost_done;
-            if (cost_in || have_order) tile_order = L.order;
-        }
-    }
-    if (cost_out) ctx->cost_frames += 1;
-    if (tile_order) ctx->ordered_frames += 1;
-    if (cost_in) ctx->order_refreshes += 1;
-    if (cost_in) L.order_kind = L.cost_done_kind;   // (this frame makes the order — and its saturation counts — anew, ahead of its own kernels)
-    L.pending_sat_kind = 0;
-    L.pending_midround = midround_exit;
-    if (tile_order && cl.other_ctl) {
-        cl.order_stats = reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(tile_order) + tile_order_stats_offset(ntiles_frame));
-        L.pending_sat_kind = L.order_kind;
-    }
-
-    // the launches of one frame, in stream order (issued directly, or once into a stream capture)
+    // ---- 5. the launches of one frame, in stream order (issued directly, or once into a stream capture)
     auto issue = [&]() -> hipError_t {
         mark(0);
-        if (cost_in) launch_tile_order(st, cost_in, tile_order, ntiles_frame, fp, midround_exit);   // (counted with the frame's first stage)
+        if (cost_in) launch_tile_order(st, cost_in, tile_order, p.ntiles, fp, p.raster.mode != 0);   // (counted with the frame's first stage)
         if (have_keygen) {
-            if (bucket && bucket_sub > BUCKET_SUB_KERNARG) {
-                const hipError_t ce = hipMemcpyAsync(L.d_split_keys, L.h_split_keys, (BUCKET_COUNT * bucket_sub - 1u) * sizeof(uint32_t),
+            if (bucket && p.bucket_sub > BUCKET_SUB_KERNARG) {
+                const hipError_t ce = hipMemcpyAsync(L.d_split_keys, L.h_split_keys, (BUCKET_COUNT * p.bucket_sub - 1u) * sizeof(uint32_t),
                                                      hipMemcpyHostToDevice, st);
                 if (ce != hipSuccess) return ce;
             }
@@ -1050,161 +1099,78 @@ int enqueue_frame(bgs_ctx* ctx, Lane& L, const bgs_cloud* cloud, const bgs_view*
         mark(1);
         int cur = 0;
         if (bucket) {
-            const hipError_t e = launch_bucket_sort(st, L.bucket_slots, draw_list, ctl, final_xor, BUCKET_COUNT * bucket_sub, wide_out);
+            const hipError_t e = launch_bucket_sort(st, L.bucket_slots, draw_list, ctl, final_xor, BUCKET_COUNT * p.bucket_sub, p.wide);
             if (e != hipSuccess) return e;
         }
-        for (uint32_t p = 0; p < (bucket ? 0u : places); ++p) {
-            const uint32_t key_xor =
-                (p + 1 == places && (s->sort_mode == BGS_SORT_RAYON || s->sort_mode == BGS_SORT_STD)) ? 0xFFFFFFFFu : 0u;
+        for (uint32_t q = 0; q < (bucket ? 0u : places); ++q) {
             // only the V' drawable entries are sorted; the culled tail is already in its final order
-            launch_onesweep_pass(st, L.entries[cur], L.entries[cur ^ 1], &ctl->draw_count, n, ctl->hist_depth[p],
-                                 depth_status + (size_t)p * depth_tiles * RADIX_BASE, &ctl->ticket[p][0], &ctl->error,
-                                 p * RADIX_BITS, key_xor, large, sort_blocks);
+            launch_onesweep_pass(st, L.entries[cur], L.entries[cur ^ 1], &ctl->draw_count, n, ctl->hist_depth[q],
+                                 depth_status + (size_t)q * depth_tiles * RADIX_BASE, &ctl->ticket[q][0], &ctl->error,
+                                 q * RADIX_BITS, q + 1 == places ? final_xor : 0u, p.large, p.sort_blocks);
             cur ^= 1;
         }
         mark(2);
         if (render && scan) {
-            launch_project_bin(st, fp, L.d_fp, cloud->ptrs, draw_list, L.culled, ctl, bin_status, L.records, L.rects, L.coarse,
-                               coarse_cap, sup_edge, /*ticket_slot=*/4, bin_blocks, binning_blocks, /*wide_bin=*/ctx->depth == 1);
+            launch_project_bin(st, fp, L.d_fp, in.cloud->ptrs, draw_list, L.culled, ctl, bin_status, L.records, L.rects, L.coarse,
+                               coarse_cap, p.sup_edge, /*ticket_slot=*/4, p.bin_blocks, p.binning_blocks, p.wide_bin);
             mark(3);
-            launch_raster_scan(st, fp, L.d_fp, L.records, L.coarse, coarse_cap, sup_edge, ctl, L.fb, L.fb8,
-                               (ctx->debug_flags & 0x40000u) ? 0u : out_format, cl, ctx->tile_trace,
-                               midround_exit ? (level >= 2u ? 1 : 2) : 0, heavy_in, heavy_out, tile_order, cost_out);
+            launch_raster_scan(st, fp, L.d_fp, L.records, L.coarse, coarse_cap, p.sup_edge, ctl, L.fb, L.fb8,
+                               (flags & BGS_DEBUG_SEPARATE_ENCODE) ? 0u : p.out_format, cl, ctx->tile_trace,
+                               p.raster.mode, heavy_in, heavy_out, tile_order, cost_out);
             mark(6);
         } else if (render) {
             const uint32_t capacity = (uint32_t)std::min<uint64_t>(L.inst_cap, MAX_INSTANCE_CAPACITY);
-            launch_project_emit(st, fp, cloud->ptrs, draw_list, L.culled, ctl, scan_status, L.records, L.inst[0], capacity,
+            launch_project_emit(st, fp, in.cloud->ptrs, draw_list, L.culled, ctl, scan_status, L.records, L.inst[0], capacity,
                                 /*ticket_slot=*/4, ctx->num_cus * 3);
             mark(3);
             const size_t inst_tiles = (L.scratch_inst_cap + sort_tile_size(true) - 1) / sort_tile_size(true) + 1;
-            for (uint32_t p = 0; p < 2; ++p)
-                launch_onesweep_pass(st, L.inst[p], L.inst[p ^ 1], &ctl->instance_count, capacity, ctl->hist_tile[p],
-                                     tile_status + (size_t)p * inst_tiles * RADIX_BASE, &ctl->ticket[5 + p][0],
-                                     &ctl->error, p * RADIX_BITS, 0u, true, ctx->num_cus * 4);
+            for (uint32_t q = 0; q < 2; ++q)
+                launch_onesweep_pass(st, L.inst[q], L.inst[q ^ 1], &ctl->instance_count, capacity, ctl->hist_tile[q],
+                                     tile_status + (size_t)q * inst_tiles * RADIX_BASE, &ctl->ticket[5 + q][0],
+                                     &ctl->error, q * RADIX_BITS, 0u, true, ctx->num_cus * 4);
             mark(4);
             launch_tile_ranges(st, L.inst[0], ctl, ranges);
             mark(5);
-            launch_raster(st, fp, L.records, L.inst[0], ranges, L.fb, view->clear_color, ctl);
+            launch_raster(st, fp, L.records, L.inst[0], ranges, L.fb, in.view.clear_color, ctl);
             mark(6);
         }
-        // BINNING_SCAN frames get their sRGB8 image from the rasteriser itself (debug flag 0x40000: from the
+        // BINNING_SCAN frames get their sRGB8 image from the rasteriser itself (BGS_DEBUG_SEPARATE_ENCODE: from the
         // separate encode pass, for A/B runs)
-        if (want_srgb8 && !(render && scan && !(ctx->debug_flags & 0x40000u)))
-            launch_encode_srgb8(st, L.fb, L.fb8, (uint32_t)fp.width * (uint32_t)fp.height, L.d_fp, out_format);
+        if (p.want_srgb8 && !(render && scan && !(flags & BGS_DEBUG_SEPARATE_ENCODE)))
+            launch_encode_srgb8(st, L.fb, L.fb8, (uint32_t)fp.width * (uint32_t)fp.height, L.d_fp, p.out_format);
         return hipGetLastError();
     };
-
-    // ---- opt-in (bgs_set_graphs): a steady-state BINNING_SCAN frame as a hipGraph, captured once per
-    // (lane, Control parity), then replayed with ONE node update — keygen's arguments carry the new
-    // FrameParams, every other kernel reads them from the copy keygen leaves in device memory.
-    // Measured: 7 launches cost 19 us of host time (30 us with stage events), a replay 10 us; on the
-    // GPU a replayed frame is ~5 % SLOWER than the same launches issued directly (178 vs 171 us per
-    // frame back to back on one stream), so it is for hosts that cannot spare the CPU time.
-    const bool use_graph = allow_graph && ctx->use_graphs && render && scan && raster_cleans && !need_memset && bucket_sub <= BUCKET_SUB_KERNARG &&
-                           prof == 0 && have_keygen && !(ctx->debug_flags & 0x4000u) && !ctx->tile_trace;
-    if (use_graph) {
-        GraphKey key;
-        std::memset(&key, 0, sizeof key);
-        const void* planes[6] = {cloud->ptrs.position_visibility, cloud->ptrs.packed, nullptr, nullptr, nullptr, nullptr};
-        std::memcpy(key.cloud, planes, sizeof planes);
-        const void* bufs[11] = {L.entries[0], L.entries[1], L.culled, L.records, L.coarse, L.fb, L.fb8, L.scratch, L.d_fp,
-                                L.h_ctl_dev, L.bucket_slots};   // (L.rects lives and dies with L.entries)
-        std::memcpy(key.bufs, bufs, sizeof bufs);
-        key.n = n;
-        key.format = cloud->ptrs.format;
-        key.places = places;
-        key.sort_mode = s->sort_mode;
-        key.gaussian_mode = fp.gaussian_mode;
-        key.aabb = fp.aabb;
-        key.any_mode = (fp.rasterize_mode != RASTERIZE_COLOR || fp.draw_mode != 0u) ? 1u : 0u;
-        key.srgb8 = out_format;
-        key.debug_flags = ctx->debug_flags;
-        key.width = fp.width;
-        key.height = fp.height;
-        key.sort_blocks = bucket ? 0 : sort_blocks;  // the bucket sort's grid is fixed
-        key.bin_blocks = bin_blocks * 4096 + binning_blocks;   // (the bin kernel's shape follows ctx->depth, as keygen's does: key.keygen_threads)
-        key.keygen_blocks = (int32_t)kg.blocks;
-        key.keygen_func = kg.func;
-        key.keygen_threads = kg.threads;
-        key.wide_bin = ctx->depth == 1 ? 1u : 0u;
-        key.raster_variant = fp.sample_count | (fp.depth_ptr ? 0x100u : 0u) | (fp.visualize_bbox ? 0x200u : 0u) | (midround_exit ? (level >= 2u ? 0x400u : 0x800u) : 0u);
-        key.split_sub = split_sub_out;   // (round 5's advisor: a replay across a 524 k-pair step of the hint left a table of the captured sub under the new sub's label)
-        key.sup_edge = sup_edge;
-        key.scratch_bytes = L.scratch_bytes;
-        key.scratch_inst_cap = L.scratch_inst_cap;
-        key.scratch_n = L.scratch_n;
-        key.coarse_cap = coarse_cap;
-        key.sort_path = bucket ? (bucket_sub | (wide_out ? 0x100u : 0u)) : 0u;   // (the bucket sort's grid and instantiation and keygen's dynamic LDS follow it)
-        FrameGraph& G = L.graph[L.ctl_parity];
-        if (G.exec && std::memcmp(&G.key, &key, sizeof key) == 0) {
-            HIP_TRY(ctx, kg.update_node(G.exec, G.keygen_node));
-            ctx->graph_replays += 1;
-        } else {
-            graph_destroy(G);
-            HIP_TRY(ctx, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-            const hipError_t ie = issue();
-            const hipError_t ce = hipStreamEndCapture(st, &G.graph);
-            size_t roots = 1;
-            if (ie != hipSuccess || ce != hipSuccess || !G.graph ||
-                hipGraphInstantiate(&G.exec, G.graph, nullptr, nullptr, 0) != hipSuccess ||
-                hipGraphGetRootNodes(G.graph, &G.keygen_node, &roots) != hipSuccess || roots != 1) {
-                graph_destroy(G);
-                (void)hipGetLastError();
-                return fail(ctx, BGS_EHIP, "capturing the frame into a hipGraph failed");
-            }
-            G.key = key;
-            ctx->graph_captures += 1;
-        }
-        HIP_TRY(ctx, hipGraphLaunch(G.exec, st));
+    if (p.graph_ok && !need_memset && prof == 0 && have_keygen) {
+        if ((rc = launch_graph(ctx, L, graph_key(p, in, L, kg, coarse_cap), kg, issue)) != BGS_OK) return rc;
     } else {
         if (need_memset) HIP_TRY(ctx, hipMemsetAsync(L.scratch, 0, L.scratch_bytes, st));
         // no keygen (empty cloud): the kernels behind it still read the frame's parameters
         if (!have_keygen) HIP_TRY(ctx, hipMemcpyAsync(L.d_fp, &fp, sizeof fp, hipMemcpyHostToDevice, st));
         HIP_TRY(ctx, issue());
     }
-    L.scratch_clean = false;
-    L.last_sorted = draw_list;
-    L.last_sorted_n = n;
-    L.fb8_valid = false;
-    L.fb_valid = !(out_format & OUT_SKIP_F32) || (ctx->debug_flags & 0x40000u);
-    L.fb8_is_f16 = (out_format & OUT_RGBA16F) != 0u;
-    if (want_srgb8) {
-        L.fb8_out = ctx->next_srgb8_target ? ctx->next_srgb8_target : L.fb8;
-        L.fb8_valid = true;
-    }
-    ctx->next_srgb8_target = nullptr;
     // the Control block travels back with the frame; it is looked at when the lane is completed.
     // A BINNING_SCAN frame's rasteriser has already written the counters to L.h_ctl and left the
     // scratch region zeroed for the next frame.
-    if (raster_cleans) { L.scratch_clean = true; L.ctl_parity ^= 1u; }
-    else {
-        if (places == 4 && n > 0) launch_splitters(st, draw_list, ctl, final_xor, split_sub_out);
+    L.scratch_clean = p.raster_cleans;
+    if (p.raster_cleans) {
+        L.ctl_parity ^= 1u;
+    } else {
+        if (places == 4 && n > 0) launch_splitters(st, draw_list, ctl, final_xor, p.split_sub_out);
         HIP_TRY(ctx, hipMemcpyAsync(L.h_ctl, ctl, sizeof(Control), hipMemcpyDeviceToHost, st));
     }
-
     HIP_TRY(ctx, hipEventRecord(L.done, st));
+
+    // ---- 6. the lane keeps the frame's inputs and plan
+    L.last_sorted = draw_list;
+    L.last_sorted_n = n;
+    L.fb_valid = !(p.out_format & OUT_SKIP_F32) || (flags & BGS_DEBUG_SEPARATE_ENCODE);
+    L.fb8_is_f16 = (p.out_format & OUT_RGBA16F) != 0u;
+    L.fb8_valid = p.want_srgb8;
+    if (p.want_srgb8) L.fb8_out = in.srgb8_target ? in.srgb8_target : L.fb8;
     L.pending = true;
-    L.pending_render = render;
-    L.pending_scan = scan;
-    L.pending_bucket = bucket;
-    L.pending_culled_written = kg.culled != nullptr;
-    L.pending_heavy_out = heavy_out;
-    L.pending_cost_out = cost_out;
-    if (cost_in) { L.order_grid = (uint32_t)fp.tiles_x | ((uint32_t)fp.tiles_y << 16); L.order_age = 0; }
-    else if (tile_order) L.order_age += 1u;
     L.pending_coarse_cap = coarse_cap;
-    L.pending_level = level;
-    L.pending_edges[0] = edge_f;
-    for (uint32_t k = 1; k < 4; ++k) L.pending_edges[k] = std::min<uint32_t>(edge_c << (k - 1u), 32u);
-    L.pending_n = n;
-    L.pending_places = places;
-    L.pending_num_st = num_st;
-    L.pending_rec_bytes = (uint32_t)rec_bytes;
-    L.pending_cloud_format = cloud->ptrs.format;
-    L.pending_w = (uint32_t)fp.width;
-    L.pending_h = (uint32_t)fp.height;
-    L.pending_tx = (uint32_t)fp.tiles_x;
-    L.pending_ty = (uint32_t)fp.tiles_y;
+    L.in = in;
+    L.plan = p;
     L.seq = ++ctx->seq;
     return BGS_OK;
 }
@@ -1213,27 +1179,28 @@ int run(bgs_ctx* ctx, const bgs_cloud* cloud, const bgs_view* view, const bgs_se
     int rc = validate(ctx, cloud, view, s, render);
     if (rc != BGS_OK) return rc;
     if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, BGS_EHIP, "hipSetDevice failed");
-    const bool will_be_async = ctx->async_frames && render && ctx->binning == BINNING_SCAN;
-    if (!will_be_async) {
-        // a blocking call: complete whatever is queued first (surfaces its watchdog state), use lane 0
-        if ((rc = finish_all(ctx)) != BGS_OK) return rc;
-        Lane& L = ctx->lanes[0];
+    const bool async = ctx->async_frames && render && ctx->binning == BINNING_SCAN;
+    // a blocking call: complete whatever is queued first (surfaces its watchdog state), use lane 0;
+    // an async frame: the next lane of the ring, completing its previous occupant first
+    Lane& L = ctx->lanes[async ? ctx->next : 0];
+    if (!async && (rc = finish_all(ctx)) != BGS_OK) return rc;
+    if (async && L.pending && (rc = finish_lane(ctx, L)) != BGS_OK) return rc;
+    const FrameInputs in{cloud, *view, *s, render, /*allow_graph=*/async, render ? ctx->next_srgb8_target : nullptr,
+                         ctx->output_srgb8, ctx->output_rgba16f, ctx->packed_only, ctx->debug_flags,
+                         render ? frame_kind(cloud, view, s) : 0ull, /*force_passes=*/false};
+    if (!async) {
         ctx->recent = 0;
         ctx->regrow_count = 0;
-        L.in_kind = render ? frame_kind(cloud, view, s) : 0ull;
-        if (render) switch_kind(ctx, L.in_kind);
-        if ((rc = enqueue_frame(ctx, L, cloud, view, s, render, false)) != BGS_OK) return rc;
+        if (render) switch_kind(ctx, in.kind);
+        if ((rc = enqueue_frame(ctx, L, in)) != BGS_OK) return rc;
+        ctx->next_srgb8_target = nullptr;   // (one-shot: it belonged to this frame)
         return finish_lane(ctx, L);  // re-runs the frame itself if a capacity was too small
     }
-    // async frame: next lane of the ring; completing its previous occupant first
-    Lane& L = ctx->lanes[ctx->next];
-    if (L.pending && (rc = finish_lane(ctx, L)) != BGS_OK) return rc;
     L.ready = false;
-    const uint64_t kind = frame_kind(cloud, view, s);
-    const bool learn = ctx->kinds.find(kind) == ctx->kinds.end();
-    L.in_kind = kind;
-    switch_kind(ctx, kind);
-    if ((rc = enqueue_frame(ctx, L, cloud, view, s, render, /*allow_graph=*/true)) != BGS_OK) return rc;
+    const bool learn = ctx->kinds.find(in.kind) == ctx->kinds.end();
+    switch_kind(ctx, in.kind);
+    if ((rc = enqueue_frame(ctx, L, in)) != BGS_OK) return rc;
+    ctx->next_srgb8_target = nullptr;
     ctx->recent = ctx->next;
     ctx->next = (ctx->next + 1) % ctx->depth;
     if (learn) {
@@ -1243,11 +1210,11 @@ int run(bgs_ctx* ctx, const bgs_cloud* cloud, const bgs_view* view, const bgs_se
         L.ready = true;
         ctx->early_frames += 1;
         // bounded: a kind whose frames never run clean (every frame re-run, a level that oscillates) is settled on anyway
-        if (ctx->kinds.find(kind) != ctx->kinds.end()) {
-            ctx->learning.erase(kind);   // (it ran clean: finish_lane settled it)
-        } else if (++ctx->learning[kind] >= bgs_ctx::LEARN_MAX) {
-            ctx->kinds[kind].sup_level = ctx->sup_level;
-            ctx->learning.erase(kind);
+        if (ctx->kinds.find(in.kind) != ctx->kinds.end()) {
+            ctx->learning.erase(in.kind);   // (it ran clean: finish_lane settled it)
+        } else if (++ctx->learning[in.kind] >= bgs_ctx::LEARN_MAX) {
+            ctx->kinds[in.kind].sup_level = ctx->sup_level;
+            ctx->learning.erase(in.kind);
         }
         if (ctx->learning.size() >= (1u << 16)) ctx->learning.clear();   // (a host that hashes noise into its settings)
     }

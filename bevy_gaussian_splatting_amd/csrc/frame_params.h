@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include "../../include/bgs.h"
+#include "../../include/bgs_diag.h"
 #include "bgs_device.h"
 
 namespace bgs {
@@ -102,6 +103,57 @@ inline uint32_t next_supertile_level(double ratio, uint32_t lv, const uint32_t e
         *longer_out = longer > 1.0 ? longer : 1.0;
     }
     return target;
+}
+
+// Supertile edges (in tiles) of levels 0..3 for a grid of tiles. Level 1 is the smallest power of two >= 8 that keeps the
+// coarse bins <= 256 and <= 32 per axis (8 at 1080p: 135 bins); level 0 the smallest edge >= 3/4 of it that does (6 at
+// 1080p: 240 bins; within 3/4 of level 1, so that the two rules cannot flip-flop); levels 2 and 3 are 2x and 4x level 1,
+// at most 32 (16 and 32 at 1080p: 40 and 12 bins).
+inline bool supertile_bins_fit(uint32_t tiles_x, uint32_t tiles_y, uint32_t edge) {
+    const uint32_t bx = (tiles_x + edge - 1) / edge, by = (tiles_y + edge - 1) / edge;
+    return bx * by <= MAX_SUPERTILES && bx <= MAX_SUPERTILES_PER_AXIS && by <= MAX_SUPERTILES_PER_AXIS;
+}
+inline void supertile_edges(uint32_t tiles_x, uint32_t tiles_y, uint32_t edges[4]) {
+    uint32_t edge_c = 8;
+    while (!supertile_bins_fit(tiles_x, tiles_y, edge_c)) edge_c *= 2;
+    uint32_t edge_f = (3 * edge_c + 3) / 4;
+    while (!supertile_bins_fit(tiles_x, tiles_y, edge_f)) ++edge_f;
+    edges[0] = edge_f < edge_c ? edge_f : edge_c;
+    for (uint32_t k = 1; k < 4; ++k) edges[k] = (edge_c << (k - 1u)) < 32u ? (edge_c << (k - 1u)) : 32u;
+}
+// Levels whose edges coincide (level 1 of 16 tiles and up, i.e. targets of ~2048 px: levels 2 and 3 both clamp to 32) are
+// ONE level: a frame runs, and is accounted, at the lowest level with that edge.
+inline uint32_t canonical_supertile_level(uint32_t level, const uint32_t edges[4]) {
+    while (level > 1 && edges[level - 1] == edges[level]) --level;
+    return level;
+}
+
+// The instantiation of raster_scan_kernel (render_kernels.hip) a BINNING_SCAN frame launches. mode: 0 the plain one;
+// 1 mid-round exit for DENSE frames (supertile level >= 2); 2 mid-round exit with the sparse frames' machinery, for frames
+// of a kind whose saturating tiles hold a good share of the work (KindState::midround) when several frames are in flight.
+// Only the OBB and AABB3D variants at 1 or 4 samples without the bounding-box overlay have the exit, and AABB3D has one
+// exit instantiation (1). Debug flags: BGS_DEBUG_NO_MIDROUND never, BGS_DEBUG_MIDROUND_ALWAYS at any level.
+struct RasterInst {
+    int variant = RV_OBB;
+    uint32_t samples = 4;
+    bool depth = false, overlay = false;
+    int mode = 0;
+};
+inline int raster_scan_mode(int variant, uint32_t samples, bool overlay, uint32_t level, bool kind_midround, int pipeline_depth,
+                            uint32_t debug_flags) {
+    if (variant == RV_SURFEL || (samples != 1u && samples != 4u) || overlay || (debug_flags & BGS_DEBUG_NO_MIDROUND)) return 0;
+    if (level < 2u && !(kind_midround && pipeline_depth > 1) && !(debug_flags & BGS_DEBUG_MIDROUND_ALWAYS)) return 0;
+    return (level >= 2u || variant == RV_AABB3D) ? 1 : 2;
+}
+inline RasterInst raster_instantiation(const FrameParams& fp, uint32_t level, bool kind_midround, int pipeline_depth,
+                                       uint32_t debug_flags) {
+    RasterInst r;
+    r.variant = fp.aabb == 0u ? RV_OBB : (fp.gaussian_mode != 0u ? RV_AABB3D : RV_SURFEL);
+    r.samples = fp.sample_count;
+    r.depth = fp.depth_ptr != 0ull;
+    r.overlay = fp.visualize_bbox != 0u;
+    r.mode = raster_scan_mode(r.variant, r.samples, r.overlay, level, kind_midround, pipeline_depth, debug_flags);
+    return r;
 }
 
 // A splitter table is usable only if it is ascending: bucket(key) = number of splitters <= key is monotone in

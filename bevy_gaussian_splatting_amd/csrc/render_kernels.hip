@@ -622,7 +622,6 @@ void launch_tile_ranges(hipStream_t stream, const uint2* instances, const Contro
 // ---------------------------------------------------------------------------------------
 // tile rasteriser
 // ---------------------------------------------------------------------------------------
-constexpr int RV_OBB = 0, RV_AABB3D = 1, RV_SURFEL = 2;
 // A pixel stops compositing once its transmittance is below the frame's cut-off
 //     t_eps = min(T_EPS, T_BUDGET / cmax),   cmax = the largest colour magnitude among the frame's records
 // (project kernels, Control::color_max_bits). What the splats behind could still add is at most t_eps * cmax
@@ -2239,13 +2238,12 @@ void launch_raster_scan(hipStream_t stream, const FrameParams& fp, const FramePa
     const uint32_t sup_x = ((uint32_t)fp.tiles_x + sup - 1u) / sup;
     // instantiations: variant x mid-round exit x samples per pixel; the per-tile trace exists for the variants without a
     // depth buffer, the depth test for the untraced ones. Sample2 / Sample8 and the bounding-box overlay (debug features:
-    // nothing in the reference selects them by default) come untraced and without the mid-round exit only — the caller
-    // (enqueue_frame) never asks those frames for either.
+    // nothing in the reference selects them by default) come untraced and without the mid-round exit only, surfels without
+    // the exit, AABB3D with one exit instantiation (mode 1): the caller (raster_instantiation, frame_params.h) asks for
+    // nothing else, and passes heavy-tile buffers with mode 1 only.
     const bool depth = fp.depth_ptr != 0ull, bbox = fp.visualize_bbox != 0u;
     const uint32_t ms = fp.sample_count;
     const bool plain = (ms == 1u || ms == 4u) && !bbox;
-    if (!plain) mode = 0;
-    if (mode != 1) { heavy_in = nullptr; heavy_out = nullptr; }   // (the strips are the dense frames')
 #define BGS_LAUNCH_RS4(V, X, TR, MS, DP, BB)                                                      \
     hipLaunchKernelGGL((raster_scan_kernel<V, TR, X, MS, DP, BB>), dim3(grid), dim3(256), 0, stream, d_fp, rec, coarse,      \
                        coarse_cap, sup_mul, sup_x, ctl, framebuffer, srgb8_default, out_format, cleanup, (TR) ? tile_trace : (uint4*)nullptr, heavy_in, heavy_out, order, cost_out)
@@ -2277,7 +2275,7 @@ void launch_raster_scan(hipStream_t stream, const FrameParams& fp, const FramePa
         else BGS_LAUNCH_RSX(RV_SURFEL);
     }
     else if (fp.aabb == 0u) { if (mode == 1) BGS_LAUNCH_RS(RV_OBB, 1); else if (mode == 2) BGS_LAUNCH_RS(RV_OBB, 2); else BGS_LAUNCH_RS(RV_OBB, 0); }
-    else if (fp.gaussian_mode != 0u) { if (mode != 0) BGS_LAUNCH_RS(RV_AABB3D, 1); else BGS_LAUNCH_RS(RV_AABB3D, 0); }   // (no interior path: one exit instantiation)
+    else if (fp.gaussian_mode != 0u) { if (mode == 1) BGS_LAUNCH_RS(RV_AABB3D, 1); else BGS_LAUNCH_RS(RV_AABB3D, 0); }   // (no interior path: one exit instantiation)
     else BGS_LAUNCH_RS(RV_SURFEL, 0);
 #undef BGS_LAUNCH_RSX
 #undef BGS_LAUNCH_RS

@@ -15,26 +15,45 @@
 extern "C" {
 #endif
 
-/* Kernel-ablation switches for performance experiments (scripts/ablate.py). Bits 1..64 switch parts
- * of kernels off and produce WRONG images; 0x1000 (per-frame memset + Control copy instead of the
- * rasteriser's in-kernel clean-up), 0x2000 (no draw-count hint for the sort grids), 0x4000 (no
- * hipGraph replay even when bgs_set_graphs is on), 0x10000 / 0x8000 / 0x400000 / 0x800000 (force supertile
- * level 0 / 1 / 2 / 3 instead of choosing by the completed frames' list statistics), 0x40000 (sRGB8 image from the
- * separate encode pass instead of the rasteriser's fused output), 0x80000 (depth sort always by the
- * onesweep digit passes, never the bucket sort), 0x200000 (bucket sort even before a completed frame has
- * told the key range: full 32-bit range guessed), 0x100000 (supertile lists start at 64 entries, to
- * exercise the overflow -> re-run path), 0x200 / 0x400 (the bucket sort with at least 768 / 1280 buckets whatever the list's
- * length: the finer splitter tables, in keygen's arguments / in the lane's device table) keep images correct and exist for
- * A/B timing and tests.
- * 0x8000000: every BINNING_SCAN frame is run twice, as if a data-dependent capacity had been too small (exercises the
- * re-run path). 0x10000000: no tile-cost feedback / cost-ordered raster workgroups; 0x20000000: none at pipeline
- * depths > 1; 0x40000000: the order is made anew with every frame (default: every 8th).
- * 0x100 / 0x800: the bucket sort with narrow (4096-pair) / wide (16 384-pair) buckets whatever the list's length (default: wide
- * past 1.57 M drawable pairs). 0x1000000: never the rasteriser's mid-round-exit instantiations; 0x20000: always one of them,
- * whatever the supertile level and the kind's saturation share (the dense frames' at level >= 2, the sparse frames' below);
- * 0x2000000 / 0x4000000: the heavy-tile strip workgroups never / at any pipeline depth (default: depth 1 only).
- * Bits 1..64 exist only in libraries built with -DBGS_ABLATION=1 (scripts/build_variant.sh); the production library
- * ignores them. Production code leaves this at 0. */
+/* Debug flags (bgs_set_debug_flags): test hooks and experiment switches. Production code leaves them at 0.
+ * Bits 1..64 are kernel-ablation switches for performance experiments (scripts/ablate.py): they switch parts of kernels
+ * off and produce WRONG images, and exist only in libraries built with -DBGS_ABLATION=1 (scripts/build_variant.sh); the
+ * production library ignores them. Every flag below keeps images correct and exists for A/B timing and tests. */
+enum bgs_debug_flag {
+    BGS_DEBUG_BUCKETS_NARROW = 0x100,           /* bucket sort with narrow (4096-pair) buckets whatever the list's length
+                                                   (default: wide past 1.57 M drawable pairs) */
+    BGS_DEBUG_SPLIT_SUB_3 = 0x200,              /* bucket sort with at least 768 buckets whatever the list's length: the finer
+                                                   splitter tables, in keygen's arguments */
+    BGS_DEBUG_SPLIT_SUB_5 = 0x400,              /* ... at least 1280 buckets: the tables in the lane's device table */
+    BGS_DEBUG_BUCKETS_WIDE = 0x800,             /* bucket sort with wide (16 384-pair) buckets whatever the list's length */
+    BGS_DEBUG_NO_RASTER_CLEANUP = 0x1000,       /* per-frame memset + Control copy instead of the rasteriser's in-kernel
+                                                   clean-up */
+    BGS_DEBUG_NO_DRAW_HINT = 0x2000,            /* no draw-count hint for the sort, project and bin grids */
+    BGS_DEBUG_NO_GRAPHS = 0x4000,               /* no hipGraph replay even when bgs_set_graphs is on */
+    BGS_DEBUG_LEVEL_1 = 0x8000,                 /* force supertile level 1 instead of choosing by the completed frames' list
+                                                   statistics */
+    BGS_DEBUG_LEVEL_0 = 0x10000,                /* ... level 0 */
+    BGS_DEBUG_MIDROUND_ALWAYS = 0x20000,        /* always a mid-round-exit rasteriser, whatever the supertile level and the
+                                                   kind's saturation share (the dense frames' at level >= 2, the sparse
+                                                   frames' below) */
+    BGS_DEBUG_SEPARATE_ENCODE = 0x40000,        /* sRGB8 image from the separate encode pass instead of the rasteriser's
+                                                   fused output */
+    BGS_DEBUG_NO_BUCKET_SORT = 0x80000,         /* depth sort always by the onesweep digit passes */
+    BGS_DEBUG_SMALL_LISTS = 0x100000,           /* supertile lists start at 64 entries (exercises the overflow -> re-run
+                                                   path) */
+    BGS_DEBUG_GUESSED_SPLITTERS = 0x200000,     /* bucket sort even before a completed frame has told the key range: the
+                                                   full 32-bit range guessed */
+    BGS_DEBUG_LEVEL_2 = 0x400000,               /* force supertile level 2 */
+    BGS_DEBUG_LEVEL_3 = 0x800000,               /* force supertile level 3 */
+    BGS_DEBUG_NO_MIDROUND = 0x1000000,          /* never a mid-round-exit rasteriser */
+    BGS_DEBUG_NO_STRIPS = 0x2000000,            /* never the heavy-tile strip workgroups (default: pipeline depth 1 only) */
+    BGS_DEBUG_STRIPS_ANY_DEPTH = 0x4000000,     /* the heavy-tile strip workgroups at any pipeline depth */
+    BGS_DEBUG_RERUN_EVERY_FRAME = 0x8000000,    /* every BINNING_SCAN frame is run twice, as if a data-dependent capacity
+                                                   had been too small (exercises the re-run path) */
+    BGS_DEBUG_NO_TILE_COST = 0x10000000,        /* no tile-cost feedback / cost-ordered raster workgroups */
+    BGS_DEBUG_NO_TILE_COST_PIPELINED = 0x20000000,  /* ... none at pipeline depths > 1 */
+    BGS_DEBUG_ORDER_EVERY_FRAME = 0x40000000    /* the cost order is made anew with every frame (default: every 8th) */
+};
 int bgs_set_debug_flags(bgs_ctx* ctx, uint32_t flags);
 
 /* What the adaptive machinery has done since bgs_create: out[0] frames enqueued on the bucket sort path,

@@ -76,7 +76,7 @@ def shim() -> ctypes.CDLL:
     global _shim
     if _shim is not None:
         return _shim
-    deps = [SHIM_SRC] + [os.path.join(CSRC, f) for f in ("splat_math.h", "exact_log.h", "bgs_device.h", "frame_params.h")]
+    deps = [SHIM_SRC, os.path.join(CSRC, "..", "..", "include", "bgs_diag.h")] + [os.path.join(CSRC, f) for f in ("splat_math.h", "exact_log.h", "bgs_device.h", "frame_params.h")]
     if not os.path.exists(SHIM_LIB) or any(os.path.getmtime(d) > os.path.getmtime(SHIM_LIB) for d in deps):
         subprocess.run(
             ["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fopenmp", "-shared", "-fPIC",

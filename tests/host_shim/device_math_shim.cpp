@@ -66,6 +66,12 @@ uint32_t shim_next_supertile_level(double ratio, uint32_t lv, const uint32_t* ed
 }
 uint32_t shim_pow2_ceil(uint64_t v) { return pow2_ceil_u32(v); }
 int shim_splitters_ascending(const uint32_t* key, uint32_t count) { return splitters_ascending(key, count) ? 1 : 0; }
+void shim_supertile_edges(uint32_t tiles_x, uint32_t tiles_y, uint32_t* edges) { supertile_edges(tiles_x, tiles_y, edges); }
+uint32_t shim_canonical_supertile_level(uint32_t level, const uint32_t* edges) { return canonical_supertile_level(level, edges); }
+int shim_raster_scan_mode(int variant, uint32_t samples, int overlay, uint32_t level, int kind_midround, int pipeline_depth,
+                          uint32_t debug_flags) {
+    return raster_scan_mode(variant, samples, overlay != 0, level, kind_midround != 0, pipeline_depth, debug_flags);
+}
 
 // keys exactly as keygen_kernel stores them (before any final-pass un-inversion)
 void shim_sort_keys(const FrameParams* fp, const float* pos_vis, uint32_t n, uint32_t* keys_out) {

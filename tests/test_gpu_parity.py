@@ -1958,18 +1958,21 @@ def test_a_kind_whose_saturating_tiles_hold_the_work_runs_the_midround_exit_rast
     to the host, and kinds at >= 30 % (trained-like 1 M: 36 %) run the rasteriser instantiation that looks for saturation
     inside a staging round — with frames in flight only (alone on the chip the launch ends with its longest lists, which do
     not saturate). Leaving early changes no bit: the frame equals the one with that instantiation switched off (debug flag
-    0x1000000). The scene-like frame (no tile saturates) stays on the plain instantiation."""
+    0x1000000). The scene-like frame (no tile saturates) stays on the plain instantiation. Dense surfel frames, pipelined at
+    supertile level 2 (debug flag 0x400000), have no mid-round-exit instantiation and report none, nor strip tiles."""
     from bevy_gaussian_splatting_amd import trained_like_gaussians_3d_seeded
     v = View.headless(1920, 1080)
-    for what in ("trained", "scene"):
+    for what in ("trained", "scene", "surfel"):
         c = trained_like_gaussians_3d_seeded(1_000_000, 7) if what == "trained" else random_gaussians_3d_seeded(1_000_000, 2)
-        s = CloudSettings() if what == "trained" else CloudSettings(global_scale=0.05)
+        s = {"trained": CloudSettings(), "scene": CloudSettings(global_scale=0.05),
+             "surfel": CloudSettings(gaussian_mode=GaussianMode.Gaussian2d, aabb=True)}[what]
+        flags = 0x400000 if what == "surfel" else 0
         h = plugin.upload(c)
         try:
             plugin.reset_adaptive_state()
-            plugin.set_debug_flags(0x1000000)
+            plugin.set_debug_flags(0x1000000 | flags)
             want = plugin.render(h, v, s)
-            plugin.set_debug_flags(0)
+            plugin.set_debug_flags(flags)
             plugin.reset_adaptive_state()
             plugin.set_async(True)
             plugin.set_pipeline_depth(4)
@@ -1982,14 +1985,17 @@ def test_a_kind_whose_saturating_tiles_hold_the_work_runs_the_midround_exit_rast
             assert ts["known"], what
             if what == "trained":
                 assert ts["work_share"] >= 0.30 and ts["midround_exit"], ts
-            else:
+            elif what == "scene":
                 assert ts["work_share"] <= 0.15 and not ts["midround_exit"], ts
+            else:
+                assert not ts["midround_exit"] and plugin.stats()["strip_tiles"] == 0, ts
             assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), what
             plugin.synchronize()
             plugin.set_pipeline_depth(1)           # one frame at a time: the plain instantiation, whatever the share
             for i in range(3):
                 got = plugin.render(h, v, s)
             assert not plugin.stats()["tile_saturation"]["midround_exit"], what
+            assert what != "surfel" or plugin.stats()["strip_tiles"] == 0
             assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), what
         finally:
             plugin.set_debug_flags(0)

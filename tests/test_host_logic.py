@@ -161,6 +161,69 @@ def test_supertile_level_rule_is_stable_and_direct():
     assert sh.shim_pow2_ceil(1 << 20) == 1 << 20 and sh.shim_pow2_ceil((1 << 40) + 1) == 1 << 31
 
 
+def test_supertile_edges_and_canonical_levels():
+    """frame_params.h supertile_edges / canonical_supertile_level (what plan_frame runs a frame at and finish_lane moves
+    between): at 1920x1080 (120 x 68 tiles) the four levels' edges are 6, 8, 16, 32; levels whose edges coincide are one
+    level, the lowest; every edge keeps the coarse bins within 256 and 32 per axis."""
+    import ctypes
+    import helpers as H
+    sh = H.shim()
+
+    def edges(tx, ty):
+        e = (ctypes.c_uint32 * 4)()
+        sh.shim_supertile_edges(tx, ty, e)
+        return list(e)
+
+    def canon(lv, e):
+        return sh.shim_canonical_supertile_level(lv, (ctypes.c_uint32 * 4)(*e))
+
+    assert edges(120, 68) == [6, 8, 16, 32]
+    assert [canon(lv, [6, 8, 16, 32]) for lv in range(4)] == [0, 1, 2, 3]
+    big = edges(256, 256)   # 4096 x 4096: level 1 is 16 tiles, levels 2 and 3 both clamp to 32
+    assert big[1] == 16 and big[2] == big[3] == 32
+    assert [canon(lv, big) for lv in range(4)] == [0, 1, 2, 2]
+    assert canon(3, [8, 8, 32, 32]) == 2 and canon(1, [8, 8, 16, 32]) == 1   # level 1 never collapses to level 0
+    for tx, ty in ((1, 1), (20, 12), (120, 68), (160, 90), (240, 135), (256, 256), (256, 1), (1, 256)):
+        e = edges(tx, ty)
+        assert e[0] <= e[1] <= e[2] <= e[3] <= 32
+        for edge in e:
+            bx, by = -(-tx // edge), -(-ty // edge)
+            assert bx * by <= 256 and bx <= 32 and by <= 32, (tx, ty, e)
+
+
+def test_rasteriser_instantiation_choice():
+    """frame_params.h raster_scan_mode: the rasteriser instantiation a frame launches, which is also what it reports
+    (bgs_stats.tile_saturation bit 31) and what a captured graph is keyed by. Surfels, Sample2 / Sample8 and the
+    bounding-box overlay never get a mid-round-exit mode; AABB3D has one exit mode."""
+    import helpers as H
+    sh = H.shim()
+    OBB, AABB3D, SURFEL = 0, 1, 2
+    NO_MIDROUND, MIDROUND_ALWAYS = 0x1000000, 0x20000
+
+    def mode(variant, samples=4, overlay=0, level=1, kind=0, depth=1, flags=0):
+        return sh.shim_raster_scan_mode(variant, samples, overlay, level, kind, depth, flags)
+
+    for level in range(4):
+        for kind in (0, 1):
+            for depth in (1, 4):
+                for flags in (0, MIDROUND_ALWAYS):
+                    for samples in (1, 2, 4, 8):
+                        assert mode(SURFEL, samples, 0, level, kind, depth, flags) == 0
+                        assert mode(OBB, samples, 1, level, kind, depth, flags) == 0
+                        assert mode(AABB3D, samples, 1, level, kind, depth, flags) == 0
+                    for samples in (2, 8):
+                        assert mode(OBB, samples, 0, level, kind, depth, flags) == 0
+                    for v in (OBB, AABB3D):
+                        assert mode(v, 4, 0, level, kind, depth, flags | NO_MIDROUND) == 0
+                        assert mode(AABB3D, 4, 0, level, kind, depth, flags) in (0, 1)
+    assert mode(OBB, level=2) == 1 and mode(OBB, 1, level=3) == 1 and mode(AABB3D, level=2) == 1
+    assert mode(OBB, level=1) == 0 and mode(OBB, level=0) == 0
+    # a kind whose saturating tiles hold the work: the sparse frames' exit, with frames in flight only
+    assert mode(OBB, level=1, kind=1, depth=4) == 2 and mode(OBB, level=1, kind=1, depth=1) == 0
+    assert mode(AABB3D, level=1, kind=1, depth=4) == 1
+    assert mode(OBB, level=0, flags=MIDROUND_ALWAYS) == 2 and mode(OBB, level=2, flags=MIDROUND_ALWAYS) == 1
+
+
 def test_splitter_tables_are_only_accepted_when_ascending():
     """bucket(key) = number of splitters <= key orders the buckets only for an ascending table."""
     import ctypes
