@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = (
     "bgs_set_queue_holders",
     "bgs_set_tile_trace",
     "bgs_selftest_ln_f32",
+    "bgs_selftest_pack",
     "bgs_settings_default",
     "bgs_view_perspective",
     "bgs_cloud_upload_f32",
@@ -221,6 +222,8 @@ def load() -> ctypes.CDLL:
     lib.bgs_set_queue_holders.restype = ctypes.c_int
     lib.bgs_selftest_ln_f32.argtypes = [vp, u32, u32, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint64)]
     lib.bgs_selftest_ln_f32.restype = ctypes.c_int
+    lib.bgs_selftest_pack.argtypes = [vp, u32, vp, u32, vp]
+    lib.bgs_selftest_pack.restype = ctypes.c_int
     lib.bgs_settings_default.argtypes = [ctypes.POINTER(BgsSettings)]
     lib.bgs_settings_default.restype = None
     lib.bgs_view_perspective.argtypes = [

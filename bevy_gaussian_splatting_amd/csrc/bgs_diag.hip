@@ -116,6 +116,34 @@ int bgs_selftest_ln_f32(bgs_ctx* ctx, uint32_t first_bits, uint32_t count, float
     return BGS_OK;
 }
 
+int bgs_selftest_pack(bgs_ctx* ctx, uint32_t format, const void* device_in_rgba_f32, uint32_t pixels, void* device_out) {
+    if (!ctx) return fail(nullptr, BGS_EINVAL, "ctx is NULL");
+    if (format != BGS_PACK_SRGB8 && format != BGS_PACK_RGBA16F)
+        return fail(ctx, BGS_EINVAL, "pack self-test: format must be BGS_PACK_SRGB8 or BGS_PACK_RGBA16F");
+    if (pixels == 0 || !device_in_rgba_f32 || !device_out)
+        return fail(ctx, BGS_EINVAL, "pack self-test: pixels >= 1 and both device buffers");
+    const size_t out_align = format == BGS_PACK_RGBA16F ? 8u : 4u;
+    if ((reinterpret_cast<uintptr_t>(device_in_rgba_f32) & 15u) || (reinterpret_cast<uintptr_t>(device_out) & (out_align - 1u)))
+        return fail(ctx, BGS_EINVAL, "pack self-test: the input must be 16-byte aligned, the output 4- (sRGB8) or 8-byte "
+                                     "(Rgba16Float) aligned");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, BGS_EHIP, "hipSetDevice failed");
+    int rc = finish_all(ctx);
+    if (rc != BGS_OK) return rc;
+    // encode_srgb8_kernel takes its destination from FrameParams::srgb8_target: a zeroed one sends it to device_out
+    FrameParams* d_fp = dev_alloc<FrameParams>(1);
+    if (!d_fp) return fail(ctx, BGS_ENOMEM, "hipMalloc(pack self-test) failed");
+    hipStream_t st = ctx->lanes[0].stream;
+    bool ok = hipMemsetAsync(d_fp, 0, sizeof(FrameParams), st) == hipSuccess;
+    if (ok) {
+        launch_encode_srgb8(st, static_cast<const float4*>(device_in_rgba_f32), static_cast<uint32_t*>(device_out), pixels,
+                            d_fp, format == BGS_PACK_RGBA16F ? OUT_RGBA16F : OUT_SRGB8);
+        ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
+    }
+    (void)hipFree(d_fp);
+    if (!ok) { (void)hipGetLastError(); return fail(ctx, BGS_EHIP, "pack self-test failed on the device"); }
+    return BGS_OK;
+}
+
 int bgs_selftest_tile_order(bgs_ctx* ctx, const uint16_t* host_cost, uint32_t ntiles, uint32_t runs, uint16_t* host_order, uint32_t* host_sums) {
     if (!ctx) return fail(nullptr, BGS_EINVAL, "ctx is NULL");
     if (!host_cost || !host_order || ntiles == 0 || ntiles > 65535u || (runs != 1u && runs != 2u && runs != 4u))

@@ -29,6 +29,7 @@
 
 #include "kernels.h"
 #include "lookback.h"
+#include "pack_tables.h"
 #include "splat_math.h"
 
 // Kernel-ablation bits (fp.debug & 1 .. 64: parts of kernels switched off, WRONG images; scripts/ablate.py) exist only in
@@ -1115,14 +1116,27 @@ __device__ __forceinline__ float trans_mean(const PxMs& T) { return T.S * T.rb; 
 template <int NS> __device__ __forceinline__ float trans_mean(const PxMsN<NS>& T) { return T.S * T.rb; }
 
 // Rgba8UnormSrgb packing of one premultiplied linear pixel (shared by the rasteriser's fused output and
-// encode_srgb8_kernel, so both give the same bytes)
-__device__ __forceinline__ uint32_t unorm8(float x) {
-    x = fminf(fmaxf(x, 0.0f), 1.0f);  // NaN -> 0
-    return (uint32_t)(x * 255.0f + 0.5f);
+// encode_srgb8_kernel, so both give the same bytes). Exact for every binary32 input (include/bgs.h "packed outputs"):
+// NaN, -0 and everything <= 0 -> 0, everything >= 1 (+inf included) -> 255, in between round to nearest of the exact
+// OETF (colour) or of 255 x (alpha). The clamp is done on the bit pattern, so it does not depend on the mode bits.
+__device__ __forceinline__ int32_t clamp01_bits(float x) {
+    const int32_t b = __float_as_int(x);
+    return b > 0x7F800000 ? 0 : min(max(b, 0), 0x3F800000);   // (a pattern with the sign bit set is negative as int32)
 }
-__device__ __forceinline__ float srgb_oetf(float x) {
-    x = fminf(fmaxf(x, 0.0f), 1.0f);
-    return x <= 0.0031308f ? 12.92f * x : fmaf(1.055f, __builtin_amdgcn_exp2f(__builtin_amdgcn_logf(x) * (1.0f / 2.4f)), -0.055f);
+// alpha: 255 x + 1/2 is exact in binary64 (a 24-bit significand times 255), so the truncation is round to nearest
+__device__ __forceinline__ uint32_t unorm8(float x) {
+    return (uint32_t)fma((double)__int_as_float(clamp01_bits(x)), 255.0, 0.5);
+}
+// colour: the hardware OETF (v_log_f32 / v_exp_f32, about 1 ulp) gives a code within one of the exact one (every
+// binary32 input checked on the device, tests/test_packed_exact.py); one step against the least inputs of that code
+// and the next (pack_tables.h, compared as integers) makes it exact
+__device__ __forceinline__ uint32_t srgb8(float x) {
+    const int32_t b = clamp01_bits(x);
+    const float c = __int_as_float(b);
+    const float o = c <= 0.0031308f ? 12.92f * c : fmaf(1.055f, __builtin_amdgcn_exp2f(__builtin_amdgcn_logf(c) * (1.0f / 2.4f)), -0.055f);
+    const uint32_t e = min((uint32_t)(o * 255.0f + 0.5f), 255u);
+    const int2 t = *reinterpret_cast<const int2*>(kSrgb8CodeBounds[e]);
+    return e + (uint32_t)(b >= t.y) - (uint32_t)(b < t.x);
 }
 // ---------------------------------------------------------------------------------------
 // INTERIOR records (round 6). What the record loop of a tile wave costs is its instruction COUNT, scalar ones included:
@@ -1311,7 +1325,7 @@ __device__ __forceinline__ uint2 pack_rgba16f(const float4 c) {
     return out;
 }
 __device__ __forceinline__ uint32_t pack_srgb8(const float4 c) {
-    return unorm8(srgb_oetf(c.x)) | (unorm8(srgb_oetf(c.y)) << 8) | (unorm8(srgb_oetf(c.z)) << 16) | (unorm8(c.w) << 24);
+    return srgb8(c.x) | (srgb8(c.y) << 8) | (srgb8(c.z) << 16) | (unorm8(c.w) << 24);
 }
 
 // XCD-aware work order: workgroup b runs on XCD b % 8 (observed dispatch, a speed assumption
@@ -2315,7 +2329,7 @@ void launch_raster(hipStream_t stream, const FrameParams& fp, const void* record
 // ---------------------------------------------------------------------------------------
 // Rgba8UnormSrgb encode of the f32 target: what the reference's colour attachment stores
 // (TextureFormat::Rgba8UnormSrgb, src/render/mod.rs:917-921, examples/headless.rs:120-123).
-// Linear RGB -> sRGB OETF -> unorm8 (round to nearest); alpha is linear. 33 MB read, 8 MB write.
+// Linear RGB -> sRGB OETF -> unorm8 (round to nearest, pack_srgb8); alpha is linear. 33 MB read, 8 MB write.
 // Used for the multi-GPU framebuffer gather (8.3 MB per 1080p frame instead of 33 MB).
 // ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void encode_srgb8_kernel(const float4* __restrict__ fb,

@@ -266,6 +266,14 @@ class GaussianSplattingPlugin:
             out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if download else None, ctypes.byref(chk)))
         return out, int(chk.value)
 
+    def selftest_pack(self, fmt: str, device_in: int, pixels: int, device_out: int) -> None:
+        """`bgs_selftest_pack`: the packed outputs' conversion (encode_srgb8_kernel) of `pixels` RGBA f32 pixels at the
+        device address `device_in` into `device_out` (4 bytes per pixel for fmt "srgb8", 8 for "rgba16f"; an int is
+        passed as the bgs_pack_format as it is). The caller's writes to the input must be complete (e.g.
+        torch.cuda.synchronize()); returns once the output is written."""
+        code = fmt if isinstance(fmt, int) else {"srgb8": 1, "rgba16f": 2}[fmt]   # BGS_PACK_SRGB8 / BGS_PACK_RGBA16F
+        self._check(self._lib.bgs_selftest_pack(self._ctx, code, device_in or None, int(pixels), device_out or None))
+
     def set_pipeline_streams(self, streams: int) -> None:
         """HIP streams the lanes are multiplexed onto (0 = one per lane); see bgs_set_pipeline_streams."""
         self._check(self._lib.bgs_set_pipeline_streams(self._ctx, int(streams)))

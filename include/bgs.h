@@ -266,12 +266,15 @@ int bgs_render(bgs_ctx* ctx, const bgs_cloud* cloud, const bgs_view* view,
 int bgs_framebuffer_device_ptr(bgs_ctx* ctx, void** dptr, uint64_t* bytes);
 /* Also produce, with every bgs_render, the frame in the reference's colour-attachment format
  * TextureFormat::Rgba8UnormSrgb (src/render/mod.rs:917-921, examples/headless.rs:120-123): linear
- * RGB -> sRGB transfer -> unorm8, alpha linear, 4 bytes per pixel R,G,B,A. Default off. */
+ * RGB -> sRGB transfer -> unorm8, alpha linear, 4 bytes per pixel R,G,B,A. Default off.
+ * Exact for every f32 value: colour = round to nearest of the exact sRGB OETF (255 oetf(x)), alpha = round to
+ * nearest of 255 x; NaN and values <= 0 (-0 included) -> 0, values >= 1 (+inf included) -> 255. */
 int bgs_set_output_srgb8(bgs_ctx* ctx, int enabled);
 int bgs_framebuffer_srgb8_device_ptr(bgs_ctx* ctx, void** dptr, uint64_t* bytes);
 /* The same for an hdr camera: the reference's colour attachment is then TextureFormat::Rgba16Float
  * (src/render/mod.rs:917-921). Every bgs_render also produces the frame as IEEE binary16 RGBA (8 bytes per
- * pixel, round to nearest even, overflow to inf), linear and unclamped. Exclusive with the sRGB8 output
+ * pixel, round to nearest even, subnormals kept, overflow to inf, NaN -> NaN), linear and unclamped. Exclusive with
+ * the sRGB8 output
  * (enabling one disables the other); bgs_set_srgb8_target / bgs_pipeline_pop's second pointer then carry
  * this image. Like the 8-bit image it is ONE conversion of the f32 result, not a per-blend quantisation. */
 int bgs_set_output_rgba16f(bgs_ctx* ctx, int enabled);

@@ -121,6 +121,14 @@ int bgs_tile_order_counters(bgs_ctx* ctx, uint64_t* cost_frames, uint64_t* order
 int bgs_selftest_tile_order(bgs_ctx* ctx, const uint16_t* host_cost, uint32_t ntiles, uint32_t runs, uint16_t* host_order,
                             uint32_t* host_sums);
 
+/* The packed outputs' conversion (the one the rasteriser's fused output and the separate encode pass share) on
+ * caller-supplied pixels: encode_srgb8_kernel, launched as a frame launches it, reads `pixels` RGBA f32 pixels from
+ * device_in_rgba_f32 (16-byte aligned) and writes `pixels` packed texels to device_out: 4 bytes each (BGS_PACK_SRGB8,
+ * 4-byte aligned) or 8 (BGS_PACK_RGBA16F, 8-byte aligned). Both buffers are DEVICE memory and stay the caller's, whose
+ * writes to the input must be complete; the call returns once the output is written. Test hook. */
+enum bgs_pack_format { BGS_PACK_SRGB8 = 1, BGS_PACK_RGBA16F = 2 };
+int bgs_selftest_pack(bgs_ctx* ctx, uint32_t format, const void* device_in_rgba_f32, uint32_t pixels, void* device_out);
+
 #ifdef __cplusplus
 }
 #endif
