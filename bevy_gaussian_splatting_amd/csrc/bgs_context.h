@@ -21,14 +21,42 @@
 #include "../../include/bgs.h"
 #include "../../include/bgs_diag.h"
 #include "bgs_device.h"
+#include "device_buffer.h"
 #include "frame_params.h"
 #include "kernels.h"
 
 using namespace bgs;
 
+namespace bgs_host {
+
+// The two memory policies of Buffer (device_buffer.h). A failed allocation leaves HIP's sticky error set, and the next
+// hipGetLastError() — the one a frame's launches end in — would report it as that frame's: it is cleared here, always.
+struct DeviceMem {
+    static void* alloc(size_t bytes) {
+        void* p = nullptr;
+        if (hipMalloc(&p, bytes) == hipSuccess) return p;
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    static void free(void* p) { (void)hipFree(p); }
+};
+struct PinnedMem {
+    static void* alloc(size_t bytes) {
+        void* p = nullptr;
+        if (hipHostMalloc(&p, bytes, hipHostMallocDefault) == hipSuccess) return p;
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    static void free(void* p) { (void)hipHostFree(p); }
+};
+template <class T> using DeviceBuffer = Buffer<T, DeviceMem>;
+template <class T> using PinnedBuffer = Buffer<T, PinnedMem>;
+
+}  // namespace bgs_host
+
 struct bgs_cloud {
     CloudPtrs ptrs{};
-    void* allocs[4] = {nullptr, nullptr, nullptr, nullptr};
+    bgs_host::DeviceBuffer<uint8_t> positions, packed;   // what ptrs.position_visibility and ptrs.packed point at
     uint64_t bytes = 0;
 };
 
@@ -43,13 +71,6 @@ constexpr int EV_COUNT = BGS_STAGE_COUNT + 1;
 constexpr int EV_RING = 64;   // per-stage timings are averaged over up to this many frames per lane
 constexpr int MAX_LANES = 8;
 
-template <class T>
-T* dev_alloc(size_t count) {
-    void* p = nullptr;
-    if (hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) return nullptr;
-    return (T*)p;
-}
-
 // What the launches of a captured frame depend on besides FrameParams (which one node carries, see
 // KeygenLaunch): compared bytewise, any difference rebuilds the graph.
 struct GraphKey {
@@ -61,8 +82,8 @@ struct GraphKey {
     uint32_t sup_edge;
     // the offsets baked into the nodes depend on the scratch layout and the list capacity, not only on
     // the base pointers (a re-allocation may return the same address)
-    uint64_t scratch_bytes, scratch_inst_cap;
-    uint32_t scratch_n, coarse_cap, sort_path;
+    ScratchLayout scratch;
+    uint32_t coarse_cap, sort_path;
     // keygen has several instantiations per size (with / without chains, 256- or 1024-thread tiles: KeygenLaunch): a
     // captured node is only ever UPDATED to the kernel and block size it was captured with
     const void* keygen_func;
@@ -118,44 +139,41 @@ struct FramePlan {
     uint64_t sat_kind = 0;
 };
 
-// Everything one in-flight frame owns.
+// Everything one in-flight frame owns. The buffers free themselves (lane_destroy: L = Lane()); a buffer's capacity is in
+// elements of its type.
 struct Lane {
     hipStream_t stream = nullptr;  // owned by the context; lanes may share one (bgs_set_pipeline_streams)
     hipEvent_t done = nullptr;     // recorded behind the lane's frame: what completing the lane waits for
-    FrameParams* d_fp = nullptr;  // the frame's FrameParams as the kernels behind keygen read them
+    DeviceBuffer<FrameParams> d_fp;  // the frame's FrameParams as the kernels behind keygen read them
     FrameGraph graph[2];          // the captured BINNING_SCAN frame, one per Control parity
 
-    // zeroed-every-frame scratch: [Control | depth status | scan status | tile status | ranges |
-    //                              bin status | partition status]
-    uint8_t* scratch = nullptr;
-    size_t scratch_bytes = 0;
-    size_t off_depth_status = 0, off_scan_status = 0, off_tile_status = 0, off_ranges = 0, off_bin_status = 0,
-           off_part_status = 0, off_ctl1 = 0;
+    // zeroed-every-frame scratch and where its parts lie (scratch_layout, frame_params.h; grown monotonically in the
+    // splat and the instance capacity it is laid out for)
+    DeviceBuffer<uint8_t> scratch;
+    ScratchLayout layout;
     uint32_t ctl_parity = 0;  // which of the lane's two Control blocks the next frame uses
     // true while the scratch region is known to be all zero without a memset: the rasteriser of a
     // BINNING_SCAN frame zeroes what the frame used (FrameCleanup, kernels.h)
     bool scratch_clean = false;
-    uint32_t scratch_n = 0;         // splat capacity the scratch was laid out for
-    uint64_t scratch_inst_cap = 0;  // instance capacity the scratch was laid out for
 
-    uint2* entries[2] = {nullptr, nullptr};
-    uint2* culled = nullptr;  // entries with the culled sentinel key, in index order
-    uint32_t entries_cap = 0;
-    void* records = nullptr;
-    size_t records_bytes = 0;
-    uint32_t* rects = nullptr;   // BINNING_SCAN: packed tile rectangle per rank (project_kernel -> bin_kernel), entries_cap words
-    uint2* inst[2] = {nullptr, nullptr};  // BINNING_SORT only
-    uint64_t inst_cap = 0;
-    uint32_t* coarse = nullptr;  // BINNING_SCAN: [num_supertiles][coarse_cap] ordered (rank, tile rect) lists
-    size_t coarse_entries = 0;   // 8-byte entries allocated (all lists together)
-    uint2* bucket_slots = nullptr;  // bucket sort: [256 * bucket_sub_cap][BUCKET_CAP] pairs (8 MB per narrow sub, 32 MB per wide one), allocated on first use, grown with sub
-    uint32_t bucket_sub_cap = 0;
-    uint32_t* d_split_keys = nullptr;   // a long splitter table (sub > BUCKET_SUB_KERNARG) as keygen reads it: BUCKET_MAX words
-    uint32_t* h_split_keys = nullptr;   // ... and the pinned staging it is copied from, ahead of keygen, on the frame's stream
+    // the sort's ping-pong lists and the entries with the culled sentinel key (index order): one group, all of one
+    // capacity or all empty (ensure_entries)
+    DeviceBuffer<uint2> entries[2], culled;
+    DeviceBuffer<uint8_t> records;
+    DeviceBuffer<uint32_t> rects;   // BINNING_SCAN: packed tile rectangle per rank (project_kernel -> bin_kernel), as many words as entries; released with them
+    DeviceBuffer<uint2> inst[2];    // BINNING_SORT only (one group)
+    DeviceBuffer<uint32_t> coarse;  // BINNING_SCAN: [num_supertiles][coarse_cap] ordered (rank, tile rect) lists: two words per entry
+    // bucket sort: BUCKET_COUNT * BUCKET_CAP pairs (8 MB) per narrow sub, four times that per wide one; allocated on first
+    // use, grown with sub
+    DeviceBuffer<uint2> bucket_slots;
+    // a long splitter table (sub > BUCKET_SUB_KERNARG) as keygen reads it, BUCKET_MAX words, and the pinned staging it is
+    // copied from, ahead of keygen, on the frame's stream (one group)
+    DeviceBuffer<uint32_t> d_split_keys;
+    PinnedBuffer<uint32_t> h_split_keys;
     // heavy-tile feedback of the rasteriser (kernels.h HeavyFeedback): two buffers per lane, written alternately, so that
     // frames of other lanes can still be reading the one this lane's previous frame completed
-    uint8_t* heavy[2] = {nullptr, nullptr};
-    uint32_t heavy_tiles = 0, heavy_parity = 0;  // heavy[heavy_parity] is what the lane's NEXT frame writes; flipped when a frame COMPLETES
+    DeviceBuffer<uint8_t> heavy[2];
+    uint32_t heavy_parity = 0;  // heavy[heavy_parity] is what the lane's NEXT frame writes; flipped when a frame COMPLETES
     // The feedback the lane's next dense frame consumes: the buffer its most recently COMPLETED dense frame wrote (any
     // view: a stale list costs balance, never pixels — every tile is drawn exactly once, by its regular wave or by a
     // strip workgroup, whichever the list it reads says). Per LANE: a lane's frames run one after the other, so the
@@ -167,22 +185,19 @@ struct Lane {
     // the lane's next frame writes, cost_done what its most recently completed frame wrote; `order` is made of
     // cost_done at the start of a frame and read by that frame's rasteriser only
     bool ready = false;   // the lane's frame is complete but nobody has taken it yet (bgs_pipeline_pop): a frame finished early, see bgs_ctx::kinds
-    uint16_t* cost[2] = {nullptr, nullptr};
-    uint16_t* order = nullptr;
-    uint32_t cost_tiles = 0, cost_parity = 0;
+    DeviceBuffer<uint16_t> cost[2], order;   // (cost planes: tile_cost_bytes / 2 elements)
+    uint32_t cost_parity = 0;
     const uint16_t* cost_done = nullptr;
     uint32_t cost_done_grid = 0;
     uint32_t order_grid = 0xFFFFFFFFu, order_age = 0;   // the grid `order` is a permutation for; frames drawn with it since it was made
-    float4* fb = nullptr;
-    size_t fb_pixels = 0;
-    uint32_t* fb8 = nullptr;     // Rgba8UnormSrgb image (optional)
-    uint32_t* fb8_out = nullptr; // where the last frame's sRGB8 image went (fb8 or a caller's target)
-    size_t fb8_pixels = 0;
+    DeviceBuffer<float4> fb;
+    DeviceBuffer<uint32_t> fb8;  // the packed image (optional): two words per pixel, room for either format (4 or 8 bytes)
+    uint32_t* fb8_out = nullptr; // where the last frame's packed image went (fb8 or a caller's target)
     uint32_t fb_w = 0, fb_h = 0;
     bool fb8_valid = false, fb8_is_f16 = false;
     bool fb_valid = true;  // false after a packed-only frame (the f32 target was not written)
 
-    Control* h_ctl = nullptr;  // pinned; filled by a copy enqueued with the frame, or by the rasteriser
+    PinnedBuffer<Control> h_ctl;  // filled by a copy enqueued with the frame, or by the rasteriser
     Control* h_ctl_dev = nullptr;  // the same memory as the device sees it
     hipEvent_t ev_ring[EV_RING][EV_COUNT] = {};
     uint8_t ev_kind[EV_RING] = {};  // 0 unused, 1 sort-only frame, 2 render/scan, 3 render/sort-binning

@@ -195,6 +195,14 @@ inline uint32_t supertile_div(uint32_t tile, uint32_t mul) { return (tile * mul)
 constexpr uint32_t BINNING_SCAN = 0;  // ordered coarse lists + lazy per-tile scan (default)
 constexpr uint32_t BINNING_SORT = 1;  // (tile, rank) instances + stable radix sort on the tile id
 
+// Onesweep geometry: 256 threads x KPT keys per tile.
+constexpr int SORT_THREADS = 256;
+constexpr int SORT_KPT_SMALL = 8;   // 2048-pair tiles: more tiles for <= ~4M keys
+constexpr int SORT_KPT_LARGE = 16;  // 4096-pair tiles
+inline uint32_t sort_tile_size(bool large) { return SORT_THREADS * (large ? SORT_KPT_LARGE : SORT_KPT_SMALL); }
+
+constexpr uint32_t KEYGEN_TILE = 2048;  // keygen's smallest tile: what the chain words are allocated and zeroed for
+
 // look-back status word: flag in the top 2 bits, 30-bit value
 constexpr uint32_t STATUS_FLAG_SHIFT = 30;
 constexpr uint32_t STATUS_VALUE_MASK = (1u << STATUS_FLAG_SHIFT) - 1u;

@@ -16,29 +16,28 @@ int bgs_radix_sort_pairs(bgs_ctx* ctx, bgs_sort_entry* entries, uint32_t n, uint
     if (!entries) return fail(ctx, BGS_EINVAL, "entries is NULL");
     Lane& L = ctx->lanes[0];
     if ((rc = ensure_entries(ctx, L, n)) != BGS_OK) return rc;
-    if ((rc = ensure_scratch(ctx, L, n, L.inst_cap)) != BGS_OK) return rc;
+    if ((rc = ensure_scratch(ctx, L, n, L.inst[0].capacity)) != BGS_OK) return rc;
     hipStream_t st = L.stream;
-    Control* ctl = (Control*)L.scratch;
-    uint32_t* depth_status = (uint32_t*)(L.scratch + L.off_depth_status);
-    HIP_TRY(ctx, hipMemsetAsync(L.scratch, 0, L.scratch_bytes, st));
+    Control* ctl = (Control*)L.scratch.ptr;
+    uint32_t* depth_status = (uint32_t*)(L.scratch.ptr + L.layout.off_depth_status);
+    HIP_TRY(ctx, hipMemsetAsync(L.scratch.ptr, 0, L.layout.bytes, st));
     L.scratch_clean = false;
-    HIP_TRY(ctx, hipMemcpyAsync(L.entries[0], entries, (size_t)n * sizeof(uint2), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(L.entries[0].ptr, entries, (size_t)n * sizeof(uint2), hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)&ctl->splat_count, (int)n, 1, st));
-    launch_histogram(st, L.entries[0], n, &ctl->hist_depth[0][0], passes);
+    launch_histogram(st, L.entries[0].ptr, n, &ctl->hist_depth[0][0], passes);
     const bool large = n > (4u << 20);
-    const size_t depth_tiles = ((size_t)L.scratch_n + sort_tile_size(false) - 1) / sort_tile_size(false) + 1;
     int cur = 0;
     for (uint32_t p = 0; p < passes; ++p) {
-        launch_onesweep_pass(st, L.entries[cur], L.entries[cur ^ 1], &ctl->splat_count, n, ctl->hist_depth[p],
-                             depth_status + (size_t)p * depth_tiles * RADIX_BASE, &ctl->ticket[p][0], &ctl->error,
+        launch_onesweep_pass(st, L.entries[cur].ptr, L.entries[cur ^ 1].ptr, &ctl->splat_count, n, ctl->hist_depth[p],
+                             depth_status + (size_t)p * L.layout.pass_stride, &ctl->ticket[p][0], &ctl->error,
                              p * RADIX_BITS, 0u, large, ctx->num_cus * 4);
         cur ^= 1;
     }
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(entries, L.entries[cur], (size_t)n * sizeof(uint2), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(L.h_ctl, ctl, sizeof(Control), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(entries, L.entries[cur].ptr, (size_t)n * sizeof(uint2), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(L.h_ctl.ptr, ctl, sizeof(Control), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (L.h_ctl->error) return fail(ctx, BGS_EINTERNAL, "device watchdog tripped in radix sort");
+    if (L.h_ctl.ptr->error) return fail(ctx, BGS_EINTERNAL, "device watchdog tripped in radix sort");
     return BGS_OK;
 }
 
@@ -49,11 +48,9 @@ int bgs_hbm_probe(bgs_ctx* ctx, uint64_t bytes, uint32_t iters, float* copy_gbs,
     if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, BGS_EHIP, "hipSetDevice failed");
     int rc = finish_all(ctx);
     if (rc != BGS_OK) return rc;
-    char* buf = nullptr;
-    if (hipMalloc((void**)&buf, (size_t)bytes * 3) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(ctx, BGS_ENOMEM, "hipMalloc(probe buffers) failed");
-    }
+    DeviceBuffer<char> probe;
+    if (!probe.reserve((size_t)bytes * 3)) return fail(ctx, BGS_ENOMEM, "hipMalloc(probe buffers) failed");
+    char* const buf = probe.ptr;
     hipStream_t st = ctx->lanes[0].stream;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     float ms_copy = 0.0f, ms_triad = 0.0f;
@@ -79,7 +76,6 @@ int bgs_hbm_probe(bgs_ctx* ctx, uint64_t bytes, uint32_t iters, float* copy_gbs,
     }
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
-    (void)hipFree(buf);
     if (!ok) { (void)hipGetLastError(); return fail(ctx, BGS_EHIP, "HBM probe failed"); }
     if (copy_gbs) *copy_gbs = ms_copy > 0.0f ? (float)(2.0 * (double)bytes * iters / (ms_copy * 1e6)) : 0.0f;
     if (triad_gbs) *triad_gbs = ms_triad > 0.0f ? (float)(3.0 * (double)bytes * iters / (ms_triad * 1e6)) : 0.0f;
@@ -92,13 +88,12 @@ int bgs_selftest_ln_f32(bgs_ctx* ctx, uint32_t first_bits, uint32_t count, float
     if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, BGS_EHIP, "hipSetDevice failed");
     int rc = finish_all(ctx);
     if (rc != BGS_OK) return rc;
-    float* d_out = nullptr;
-    unsigned long long* d_sum = dev_alloc<unsigned long long>(1);
-    if (!d_sum) return fail(ctx, BGS_ENOMEM, "hipMalloc(selftest) failed");
-    if (host_out && !(d_out = dev_alloc<float>(count))) {
-        (void)hipFree(d_sum);
-        return fail(ctx, BGS_ENOMEM, "hipMalloc(selftest output) failed");
-    }
+    DeviceBuffer<unsigned long long> sum_buf;
+    DeviceBuffer<float> out_buf;
+    if (!sum_buf.reserve(1)) return fail(ctx, BGS_ENOMEM, "hipMalloc(selftest) failed");
+    if (host_out && !out_buf.reserve(count)) return fail(ctx, BGS_ENOMEM, "hipMalloc(selftest output) failed");
+    unsigned long long* const d_sum = sum_buf.ptr;
+    float* const d_out = out_buf.ptr;   // (null without host_out)
     hipStream_t st = ctx->lanes[0].stream;
     unsigned long long sum = 0;
     bool ok = hipMemsetAsync(d_sum, 0, sizeof sum, st) == hipSuccess;
@@ -109,8 +104,6 @@ int bgs_selftest_ln_f32(bgs_ctx* ctx, uint32_t first_bits, uint32_t count, float
     }
     if (ok && host_out) ok = hipMemcpyAsync(host_out, d_out, (size_t)count * sizeof(float), hipMemcpyDeviceToHost, st) == hipSuccess;
     ok = ok && hipStreamSynchronize(st) == hipSuccess;
-    (void)hipFree(d_sum);
-    if (d_out) (void)hipFree(d_out);
     if (!ok) { (void)hipGetLastError(); return fail(ctx, BGS_EHIP, "ln self-test failed on the device"); }
     if (checksum_out) *checksum_out = (uint64_t)sum;
     return BGS_OK;
@@ -130,8 +123,9 @@ int bgs_selftest_pack(bgs_ctx* ctx, uint32_t format, const void* device_in_rgba_
     int rc = finish_all(ctx);
     if (rc != BGS_OK) return rc;
     // encode_srgb8_kernel takes its destination from FrameParams::srgb8_target: a zeroed one sends it to device_out
-    FrameParams* d_fp = dev_alloc<FrameParams>(1);
-    if (!d_fp) return fail(ctx, BGS_ENOMEM, "hipMalloc(pack self-test) failed");
+    DeviceBuffer<FrameParams> fp_buf;
+    if (!fp_buf.reserve(1)) return fail(ctx, BGS_ENOMEM, "hipMalloc(pack self-test) failed");
+    FrameParams* const d_fp = fp_buf.ptr;
     hipStream_t st = ctx->lanes[0].stream;
     bool ok = hipMemsetAsync(d_fp, 0, sizeof(FrameParams), st) == hipSuccess;
     if (ok) {
@@ -139,7 +133,6 @@ int bgs_selftest_pack(bgs_ctx* ctx, uint32_t format, const void* device_in_rgba_
                             d_fp, format == BGS_PACK_RGBA16F ? OUT_RGBA16F : OUT_SRGB8);
         ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
     }
-    (void)hipFree(d_fp);
     if (!ok) { (void)hipGetLastError(); return fail(ctx, BGS_EHIP, "pack self-test failed on the device"); }
     return BGS_OK;
 }
@@ -152,8 +145,11 @@ int bgs_selftest_tile_order(bgs_ctx* ctx, const uint16_t* host_cost, uint32_t nt
     int rc = finish_all(ctx);
     if (rc != BGS_OK) return rc;
     const uint32_t nblocks = (ntiles + 3u) / 4u;
-    uint16_t* d_cost = dev_alloc<uint16_t>(tile_cost_bytes(ntiles) / 2u);
-    uint16_t* d_order = dev_alloc<uint16_t>(tile_order_bytes(ntiles) / 2u);
+    DeviceBuffer<uint16_t> cost_buf, order_buf;
+    cost_buf.reserve(tile_cost_bytes(ntiles) / 2u);
+    order_buf.reserve(tile_order_bytes(ntiles) / 2u);
+    uint16_t* const d_cost = cost_buf.ptr;
+    uint16_t* const d_order = order_buf.ptr;
     hipStream_t st = ctx->lanes[0].stream;
     uint32_t pairs[16];
     bool ok = d_cost && d_order &&
@@ -171,8 +167,6 @@ int bgs_selftest_tile_order(bgs_ctx* ctx, const uint16_t* host_cost, uint32_t nt
         host_sums[0] = host_sums[1] = 0u;
         for (uint32_t x = 0; x < 8u; ++x) { host_sums[0] += pairs[2u * x]; host_sums[1] += pairs[2u * x + 1u]; }
     }
-    if (d_cost) (void)hipFree(d_cost);
-    if (d_order) (void)hipFree(d_order);
     if (!ok) { (void)hipGetLastError(); return fail(ctx, BGS_EHIP, "tile-order self-test failed on the device"); }
     return BGS_OK;
 }

@@ -24,8 +24,6 @@ int fail(bgs_ctx* ctx, int status, const std::string& msg) {
 }
 
 
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 // Lane i runs on stream i % S (S = bgs_set_pipeline_streams, default: the pipeline depth, i.e. a
 // stream per lane). With S < depth a stream holds the NEXT frame of a sibling lane while one executes,
 // so the stream never waits for the host between frames.
@@ -70,15 +68,13 @@ int lane_create(bgs_ctx* ctx, Lane& L) {
     HIP_TRY(ctx, hipEventCreateWithFlags(&L.done, hipEventDisableTiming));
     for (auto& slot : L.ev_ring)
         for (auto& ev : slot) HIP_TRY(ctx, hipEventCreate(&ev));
-    void* h = nullptr;
-    HIP_TRY(ctx, hipHostMalloc(&h, sizeof(Control), hipHostMallocDefault));
-    L.h_ctl = (Control*)h;
-    std::memset(L.h_ctl, 0, sizeof(Control));
+    if (!L.h_ctl.reserve(1))
+        return fail(ctx, BGS_EHIP, std::string("hipHostMalloc(&h, sizeof(Control), hipHostMallocDefault): ") + hipGetErrorString(hipErrorOutOfMemory));
+    std::memset(L.h_ctl.ptr, 0, sizeof(Control));
     void* hd = nullptr;
-    HIP_TRY(ctx, hipHostGetDevicePointer(&hd, h, 0));
+    HIP_TRY(ctx, hipHostGetDevicePointer(&hd, L.h_ctl.ptr, 0));
     L.h_ctl_dev = (Control*)hd;
-    L.d_fp = dev_alloc<FrameParams>(1);
-    if (!L.d_fp) return fail(ctx, BGS_ENOMEM, "hipMalloc(frame params) failed");
+    if (!L.d_fp.reserve(1)) return fail(ctx, BGS_ENOMEM, "hipMalloc(frame params) failed");
     return assign_streams(ctx);
 }
 
@@ -91,120 +87,46 @@ void graph_destroy(FrameGraph& g) {
 void lane_destroy(Lane& L) {
     if (L.stream) (void)hipStreamSynchronize(L.stream);
     for (auto& g : L.graph) graph_destroy(g);
-    if (L.d_fp) (void)hipFree(L.d_fp);
-    if (L.scratch) (void)hipFree(L.scratch);
-    for (auto e : L.entries) if (e) (void)hipFree(e);
-    if (L.culled) (void)hipFree(L.culled);
-    for (auto e : L.inst) if (e) (void)hipFree(e);
-    if (L.records) (void)hipFree(L.records);
-    if (L.rects) (void)hipFree(L.rects);
-    if (L.coarse) (void)hipFree(L.coarse);
-    if (L.bucket_slots) (void)hipFree(L.bucket_slots);
-    if (L.d_split_keys) (void)hipFree(L.d_split_keys);
-    if (L.h_split_keys) (void)hipHostFree(L.h_split_keys);
-    for (auto h : L.heavy) if (h) (void)hipFree(h);
-    for (auto c : L.cost) if (c) (void)hipFree(c);
-    if (L.order) (void)hipFree(L.order);
-    if (L.fb) (void)hipFree(L.fb);
-    if (L.fb8) (void)hipFree(L.fb8);
-    if (L.h_ctl) (void)hipHostFree(L.h_ctl);
     for (auto& slot : L.ev_ring)
         for (auto ev : slot) if (ev) (void)hipEventDestroy(ev);
     if (L.done) (void)hipEventDestroy(L.done);
-    L = Lane();
+    L = Lane();   // (every buffer frees itself)
 }
 
-// (Re)build the zeroed scratch region for n splats and inst_cap instances.
+// (Re)build the zeroed scratch region for n splats and inst_cap instances: both only ever grow.
 int ensure_scratch(bgs_ctx* ctx, Lane& L, uint32_t n, uint64_t inst_cap) {
-    if (L.scratch && n <= L.scratch_n && inst_cap <= L.scratch_inst_cap) return BGS_OK;
-    n = std::max(n, L.scratch_n);
-    inst_cap = std::max(inst_cap, L.scratch_inst_cap);
-    // depth sort may use either tile size; size for the smaller one
-    const size_t depth_tiles = ((size_t)n + sort_tile_size(false) - 1) / sort_tile_size(false) + 1;
-    const size_t scan_tiles = ((size_t)n + 255) / 256 + 1;
-    const size_t inst_tiles = (inst_cap + sort_tile_size(true) - 1) / sort_tile_size(true) + 1;
-    size_t off = align_up(sizeof(Control), 256);
-    const size_t off_depth = off;
-    off += align_up(4 * depth_tiles * RADIX_BASE * sizeof(uint32_t), 256);
-    const size_t off_scan = off;
-    off += align_up(scan_tiles * sizeof(unsigned long long), 256);
-    const size_t off_tile = off;
-    off += align_up(2 * inst_tiles * RADIX_BASE * sizeof(uint32_t), 256);
-    const size_t off_ranges = off;
-    off += align_up((size_t)RADIX_BASE * RADIX_BASE * sizeof(uint2), 256);
-    const size_t off_bin = off;
-    off += align_up(scan_tiles * MAX_SUPERTILES * sizeof(uint32_t), 256);
-    const size_t off_part = off;
-    off += align_up((((size_t)n + KEYGEN_TILE - 1) / KEYGEN_TILE + 1) * sizeof(uint32_t), 256);
-    const size_t off_ctl1 = off;  // the lane's second Control block (see FrameCleanup)
-    off += align_up(sizeof(Control), 256);
-    if (L.scratch) { (void)hipFree(L.scratch); L.scratch = nullptr; }
-    void* p = nullptr;
-    if (hipMalloc(&p, off) != hipSuccess) return fail(ctx, BGS_ENOMEM, "hipMalloc(scratch) failed");
-    L.scratch = (uint8_t*)p;
-    L.scratch_bytes = off;
-    L.off_depth_status = off_depth;
-    L.off_scan_status = off_scan;
-    L.off_tile_status = off_tile;
-    L.off_ranges = off_ranges;
-    L.off_bin_status = off_bin;
-    L.off_part_status = off_part;
-    L.off_ctl1 = off_ctl1;
+    if (L.scratch.ptr && n <= L.layout.n && inst_cap <= L.layout.inst_cap) return BGS_OK;
+    L.layout = scratch_layout(std::max(n, L.layout.n), std::max(inst_cap, L.layout.inst_cap));
     L.scratch_clean = false;
-    L.scratch_n = n;
-    L.scratch_inst_cap = inst_cap;
+    if (!L.scratch.reserve(L.layout.bytes)) return fail(ctx, BGS_ENOMEM, "hipMalloc(scratch) failed");
     return BGS_OK;
 }
 
+// The sort's lists and, with them, the tile rectangles (ensure_rects sizes those by the lists, and GraphKey::bufs does not
+// name them: they are released whenever the lists are reallocated).
 int ensure_entries(bgs_ctx* ctx, Lane& L, uint32_t n) {
-    if (n <= L.entries_cap && L.entries[0]) return BGS_OK;
-    for (auto& e : L.entries) { if (e) (void)hipFree(e); e = nullptr; }
-    if (L.culled) { (void)hipFree(L.culled); L.culled = nullptr; }
-    if (L.rects) { (void)hipFree(L.rects); L.rects = nullptr; }
-    for (auto& e : L.entries) {
-        e = dev_alloc<uint2>(n);
-        if (!e) return fail(ctx, BGS_ENOMEM, "hipMalloc(sort entries) failed");
-    }
-    L.culled = dev_alloc<uint2>(n);
-    if (!L.culled) return fail(ctx, BGS_ENOMEM, "hipMalloc(culled entries) failed");
-    L.entries_cap = n;
-    return BGS_OK;
+    if (L.entries[0].holds(n) && L.entries[1].holds(n) && L.culled.holds(n)) return BGS_OK;
+    L.rects.reset();
+    const int failed = reserve_group(n, L.entries[0], L.entries[1], L.culled);
+    if (failed < 0) return BGS_OK;
+    return fail(ctx, BGS_ENOMEM, failed < 2 ? "hipMalloc(sort entries) failed" : "hipMalloc(culled entries) failed");
 }
 
-// BINNING_SCAN renders only: the packed tile rectangle per rank (project_kernel -> bin_kernel); freed with the entries
+// BINNING_SCAN renders only: the packed tile rectangle per rank (project_kernel -> bin_kernel)
 int ensure_rects(bgs_ctx* ctx, Lane& L) {
-    if (L.rects) return BGS_OK;
-    L.rects = dev_alloc<uint32_t>(L.entries_cap);
-    if (!L.rects) return fail(ctx, BGS_ENOMEM, "hipMalloc(tile rectangles) failed");
+    if (!L.rects.reserve(L.entries[0].capacity)) return fail(ctx, BGS_ENOMEM, "hipMalloc(tile rectangles) failed");
     return BGS_OK;
 }
 
 int ensure_instances(bgs_ctx* ctx, Lane& L, uint64_t cap) {
-    if (cap <= L.inst_cap && L.inst[0]) return BGS_OK;
-    for (auto& e : L.inst) { if (e) (void)hipFree(e); e = nullptr; }
-    L.inst_cap = 0;
-    for (auto& e : L.inst) {
-        e = dev_alloc<uint2>(cap);
-        if (!e) return fail(ctx, BGS_ENOMEM, "hipMalloc(tile instances) failed");
-    }
-    L.inst_cap = cap;
+    if (reserve_group(cap, L.inst[0], L.inst[1]) >= 0) return fail(ctx, BGS_ENOMEM, "hipMalloc(tile instances) failed");
     return BGS_OK;
 }
 
 int ensure_records(bgs_ctx* ctx, Lane& L, size_t bytes) {
-    if (bytes <= L.records_bytes && L.records) return BGS_OK;
-    if (L.records) (void)hipFree(L.records);
-    L.records = nullptr;
-    L.records_bytes = 0;
-    void* p = nullptr;
-    if (hipMalloc(&p, std::max<size_t>(bytes, 256)) != hipSuccess)
-        return fail(ctx, BGS_ENOMEM, "hipMalloc(records) failed");
-    L.records = p;
-    L.records_bytes = bytes;
+    if (!L.records.reserve(bytes, 256)) return fail(ctx, BGS_ENOMEM, "hipMalloc(records) failed");
     return BGS_OK;
 }
-
-uint32_t pow2_ceil(uint64_t v) { return pow2_ceil_u32(v); }
 
 // Supertile lists: `num_st` lists of `cap` (rank, tile rect) entries each. `cap` follows the longest list
 // seen so far (ctx->coarse_cap_hint, never more than n: a list holds each rank at most once); a frame
@@ -212,92 +134,73 @@ uint32_t pow2_ceil(uint64_t v) { return pow2_ceil_u32(v); }
 int ensure_coarse(bgs_ctx* ctx, Lane& L, uint32_t n, uint32_t num_st, uint32_t debug_flags, uint32_t* cap_out) {
     const uint32_t n1 = std::max<uint32_t>(n, 1);
     if (ctx->coarse_cap_hint == 0)
-        ctx->coarse_cap_hint = (debug_flags & BGS_DEBUG_SMALL_LISTS) ? 64u : std::max<uint32_t>(pow2_ceil(n1 / 64u), 4096u);  // a first guess: a frame that outgrows it is re-run
+        ctx->coarse_cap_hint = (debug_flags & BGS_DEBUG_SMALL_LISTS) ? 64u : std::max<uint32_t>(pow2_ceil_u32(n1 / 64u), 4096u);  // a first guess: a frame that outgrows it is re-run
     const uint32_t want = std::min<uint32_t>(n1, ctx->coarse_cap_hint);
-    const size_t need = (size_t)num_st * want;
+    const size_t need = (size_t)num_st * want;   // 8-byte entries, all lists together
     // (grown when too small; a lane keeps what it has when the hint falls — a context that alternates between
     // views of different density would otherwise free and allocate every frame)
-    if (need > L.coarse_entries || !L.coarse) {
+    if (!L.coarse.holds(2 * need)) {
         if (need * 8u > (64ull << 30))
             return fail(ctx, BGS_ECAPACITY, "coarse bin lists would exceed 64 GiB; use bgs_set_binning(ctx, 1)");
-        if (L.coarse) (void)hipFree(L.coarse);
-        L.coarse = nullptr;
-        L.coarse_entries = 0;
-        L.coarse = dev_alloc<uint32_t>(2 * need);
-        if (!L.coarse)
+        if (!L.coarse.reserve(2 * need))
             return fail(ctx, BGS_ENOMEM, "hipMalloc(coarse lists) failed: " + std::to_string((need * 8u) >> 20) +
                                              " MiB per lane (8 B x supertiles x longest list); fewer lanes (bgs_set_pipeline_depth) need less");
-        L.coarse_entries = need;
     }
     // everything that is allocated is used (a lane that grew for an earlier frame keeps its longer lists;
     // not under BGS_DEBUG_SMALL_LISTS, which exists to exercise the overflow path)
-    *cap_out = (debug_flags & BGS_DEBUG_SMALL_LISTS) ? want : (uint32_t)std::min<size_t>(L.coarse_entries / num_st, n1);
+    *cap_out = (debug_flags & BGS_DEBUG_SMALL_LISTS) ? want : (uint32_t)std::min<size_t>(L.coarse.capacity / 2 / num_st, n1);
     return BGS_OK;
 }
 
 int ensure_bucket_slots(bgs_ctx* ctx, Lane& L, uint32_t sub, bool wide) {
     const uint32_t units = sub * (wide ? BUCKET_CAP_WIDE / BUCKET_CAP : 1u);   // (in narrow subs: 256 * BUCKET_CAP pairs = 8 MB each)
-    if (L.bucket_slots && units <= L.bucket_sub_cap) return BGS_OK;
-    if (L.bucket_slots) (void)hipFree(L.bucket_slots);   // (waits for the device: no frame in flight still uses them)
-    L.bucket_sub_cap = 0;
-    L.bucket_slots = dev_alloc<uint2>((size_t)BUCKET_COUNT * units * BUCKET_CAP);
-    if (!L.bucket_slots) return fail(ctx, BGS_ENOMEM, "hipMalloc(bucket sort slots) failed");
-    L.bucket_sub_cap = units;
+    // (growing frees first, which waits for the device: no frame in flight still uses the old slots)
+    if (!L.bucket_slots.reserve((size_t)BUCKET_COUNT * units * BUCKET_CAP)) return fail(ctx, BGS_ENOMEM, "hipMalloc(bucket sort slots) failed");
+    return BGS_OK;
+}
+
+// The lane's device splitter table and its pinned staging: one without the other is of no use
+int ensure_split_keys(bgs_ctx* ctx, Lane& L) {
+    if (reserve_group(BUCKET_MAX, L.d_split_keys, L.h_split_keys) >= 0)
+        return fail(ctx, BGS_ENOMEM, "hipMalloc / hipHostMalloc(splitter table) failed");
     return BGS_OK;
 }
 
 int ensure_heavy(bgs_ctx* ctx, Lane& L, uint32_t tiles) {
-    if (L.heavy[0] && tiles <= L.heavy_tiles) return BGS_OK;
-    // (hipFree waits for the device: no frame in flight still reads the old buffers)
+    const size_t bytes = heavy_feedback_bytes(tiles);
+    if (L.heavy[0].holds(bytes)) return BGS_OK;
+    // (freeing waits for the device: no frame in flight still reads the old buffers)
     L.heavy_done = nullptr;
-    for (auto& h : L.heavy) { if (h) (void)hipFree(h); h = nullptr; }
-    L.heavy_tiles = 0;
-    for (auto& h : L.heavy) {
-        void* p = nullptr;
-        if (hipMalloc(&p, heavy_feedback_bytes(tiles)) != hipSuccess) { (void)hipGetLastError(); return fail(ctx, BGS_ENOMEM, "hipMalloc(heavy-tile feedback) failed"); }
-        h = (uint8_t*)p;
-    }
-    L.heavy_tiles = tiles;
+    if (reserve_group(bytes, L.heavy[0], L.heavy[1]) >= 0) return fail(ctx, BGS_ENOMEM, "hipMalloc(heavy-tile feedback) failed");
     return BGS_OK;
 }
 
+// whether the lane's cost planes (and the order made of them) serve a grid of `tiles` as they are
+bool cost_holds(const Lane& L, uint32_t tiles) { return L.cost[0].holds(tile_cost_bytes(tiles) / 2u); }
+
 int ensure_cost(bgs_ctx* ctx, Lane& L, uint32_t tiles) {
-    if (L.cost[0] && tiles <= L.cost_tiles) return BGS_OK;
+    if (cost_holds(L, tiles)) return BGS_OK;
     L.cost_done = nullptr;
-    for (auto& c : L.cost) { if (c) (void)hipFree(c); c = nullptr; }
-    if (L.order) { (void)hipFree(L.order); L.order = nullptr; }
     L.order_grid = 0xFFFFFFFFu;
-    L.cost_tiles = 0;
-    for (auto& c : L.cost) {
-        void* p = nullptr;
-        if (hipMalloc(&p, tile_cost_bytes(tiles)) != hipSuccess || hipMemset(p, 0, tile_cost_bytes(tiles)) != hipSuccess) {
-            (void)hipGetLastError();
-            if (p) (void)hipFree(p);
-            return fail(ctx, BGS_ENOMEM, "hipMalloc(tile cost feedback) failed");
-        }
-        c = (uint16_t*)p;
+    L.order.reset();
+    bool ok = reserve_group(tile_cost_bytes(tiles) / 2u, L.cost[0], L.cost[1]) < 0;
+    for (auto& c : L.cost)   // new planes start zeroed
+        if (ok && hipMemset(c.ptr, 0, tile_cost_bytes(tiles)) != hipSuccess) { (void)hipGetLastError(); ok = false; }
+    if (!ok) {
+        for (auto& c : L.cost) c.reset();
+        return fail(ctx, BGS_ENOMEM, "hipMalloc(tile cost feedback) failed");
     }
-    void* p = nullptr;
-    if (hipMalloc(&p, tile_order_bytes(tiles)) != hipSuccess) { (void)hipGetLastError(); return fail(ctx, BGS_ENOMEM, "hipMalloc(tile order) failed"); }
-    L.order = (uint16_t*)p;
-    L.cost_tiles = tiles;
+    if (!L.order.reserve(tile_order_bytes(tiles) / 2u)) {
+        for (auto& c : L.cost) c.reset();
+        return fail(ctx, BGS_ENOMEM, "hipMalloc(tile order) failed");
+    }
     return BGS_OK;
 }
 
 int ensure_framebuffer(bgs_ctx* ctx, Lane& L, uint32_t w, uint32_t h, bool want8) {
     const size_t px = (size_t)w * h;
-    if (px > L.fb_pixels || !L.fb) {
-        if (L.fb) (void)hipFree(L.fb);
-        L.fb = dev_alloc<float4>(px);
-        if (!L.fb) return fail(ctx, BGS_ENOMEM, "hipMalloc(framebuffer) failed");
-        L.fb_pixels = px;
-    }
-    if (want8 && (px > L.fb8_pixels || !L.fb8)) {
-        if (L.fb8) (void)hipFree(L.fb8);
-        L.fb8 = dev_alloc<uint32_t>(2 * px);  // room for either packed format (4 or 8 bytes per pixel)
-        if (!L.fb8) return fail(ctx, BGS_ENOMEM, "hipMalloc(srgb8 framebuffer) failed");
-        L.fb8_pixels = px;
-    }
+    if (!L.fb.reserve(px)) return fail(ctx, BGS_ENOMEM, "hipMalloc(framebuffer) failed");
+    if (want8 && !L.fb8.reserve(2 * px)) return fail(ctx, BGS_ENOMEM, "hipMalloc(srgb8 framebuffer) failed");   // room for either packed format (4 or 8 bytes per pixel)
     L.fb_w = w;
     L.fb_h = h;
     return BGS_OK;
@@ -420,7 +323,7 @@ FrameTotals frame_totals(const FramePlan& p, const Control& h) {
 // finish_lane, step 1: nothing a frame that tripped the device watchdog left behind is trusted: not its counters, not
 // the scratch region
 int check_watchdog(bgs_ctx* ctx, Lane& L) {
-    const Control& h = *L.h_ctl;
+    const Control& h = *L.h_ctl.ptr;
     if (!h.error) return BGS_OK;
     L.scratch_clean = false;
     ctx->draw_hint_valid = false;
@@ -431,7 +334,7 @@ int check_watchdog(bgs_ctx* ctx, Lane& L) {
 // finish_lane, step 2: the capacities that depend on the data. *rerun: the frame must be run again.
 int check_capacities(bgs_ctx* ctx, Lane& L, const FrameTotals& t, int attempt, bool* rerun) {
     const FramePlan& p = L.plan;
-    const Control& h = *L.h_ctl;
+    const Control& h = *L.h_ctl.ptr;
     *rerun = false;
     if (p.bucket && h.sort_overflow) {
         // A bucket over capacity (1): the view changed faster than the splitters follow; the table is dropped
@@ -457,7 +360,7 @@ int check_capacities(bgs_ctx* ctx, Lane& L, const FrameTotals& t, int attempt, b
     if (p.render && p.scan) {
         // the capacity the next allocations aim at follows the longest list SEEN (25 % head-room, power of
         // two): up at once, down only after 64 completed frames in a row that would fit an eighth of it
-        const uint32_t want = std::max<uint32_t>(pow2_ceil((uint64_t)t.longest + t.longest / 4), 4096u);
+        const uint32_t want = std::max<uint32_t>(pow2_ceil_u32((uint64_t)t.longest + t.longest / 4), 4096u);
         if (p.level == ctx->sup_level) {
             if (want > ctx->coarse_cap_hint) {
                 ctx->coarse_cap_hint = want;
@@ -497,14 +400,14 @@ int check_capacities(bgs_ctx* ctx, Lane& L, const FrameTotals& t, int attempt, b
 // (null after a frame that left none); its saturation counts move its kind's mid-round-exit choice
 void learn_feedback(bgs_ctx* ctx, Lane& L) {
     const FramePlan& p = L.plan;
-    const Control& h = *L.h_ctl;
+    const Control& h = *L.h_ctl.ptr;
     const uint32_t grid = (uint32_t)p.fp.tiles_x | ((uint32_t)p.fp.tiles_y << 16);
     // only now does the lane's next frame write the OTHER buffer: a re-run wrote the one its failed attempt wrote,
     // never the completed frame's list it was reading
-    L.heavy_done = p.heavy ? L.heavy[L.heavy_parity] : nullptr;
+    L.heavy_done = p.heavy ? L.heavy[L.heavy_parity].ptr : nullptr;
     L.heavy_done_grid = grid;
     if (p.heavy) L.heavy_parity ^= 1u;
-    L.cost_done = p.cost ? L.cost[L.cost_parity] : nullptr;
+    L.cost_done = p.cost ? L.cost[L.cost_parity].ptr : nullptr;
     L.cost_done_kind = L.in.kind;
     L.cost_done_grid = grid;
     // what the cost plane behind the lane's tile order said: the share of the frame's tile work that was in tiles which
@@ -542,7 +445,7 @@ void learn_draw_hint(bgs_ctx* ctx, uint32_t draw_count) {
 // view. bucket() is only monotone for an ascending table, so that is checked, not assumed
 void learn_splitters(bgs_ctx* ctx, const Lane& L) {
     const FramePlan& p = L.plan;
-    const Control& h = *L.h_ctl;
+    const Control& h = *L.h_ctl.ptr;
     const uint32_t nkeys = BUCKET_COUNT * p.split_sub_out - 1u;
     if (p.places != 4 || h.draw_count < BUCKET_COUNT || !splitters_ascending(h.splitters, nkeys) || !L.in.cloud) return;
     int slot = find_splitter_slot(ctx, L.in.cloud, &L.in.view, &L.in.settings);
@@ -584,7 +487,7 @@ bool learn_level(bgs_ctx* ctx, const Lane& L, const FrameTotals& t) {
     // (a level whose edge equals a lower level's is that lower level: moving between them is not a change — no new
     // capacity prediction, no vote reset, no level_changes)
     const uint32_t target = canonical_supertile_level(
-        next_supertile_level((double)t.instances / (double)L.h_ctl->visible_count, lv, p.edges, &longer), p.edges);
+        next_supertile_level((double)t.instances / (double)L.h_ctl.ptr->visible_count, lv, p.edges, &longer), p.edges);
     const auto kit = ctx->kinds.find(L.in.kind);
     // (a settled kind remembers its level for the next time the context comes back to it)
     if (kit != ctx->kinds.end()) kit->second.sup_level = target;
@@ -595,7 +498,7 @@ bool learn_level(bgs_ctx* ctx, const Lane& L, const FrameTotals& t) {
         // lists of another level: predicted from THIS frame's longest list (coarser supertiles hold longer lists:
         // entries scale with the ratio, lists with the area), never from the old hint
         const double predicted = (double)t.longest * (target > lv ? longer : 1.0) * 1.25;
-        ctx->coarse_cap_hint = std::max<uint32_t>(pow2_ceil((uint64_t)std::min(predicted, 1.0e9)), 4096u);
+        ctx->coarse_cap_hint = std::max<uint32_t>(pow2_ceil_u32((uint64_t)std::min(predicted, 1.0e9)), 4096u);
         ctx->list_shrink_votes = 0;
         ctx->level_changes += 1;
         ctx->sup_level = target;
@@ -606,7 +509,7 @@ bool learn_level(bgs_ctx* ctx, const Lane& L, const FrameTotals& t) {
 // finish_lane, step 4: the lane's counters of the completed frame
 void fill_stats(const bgs_ctx* ctx, Lane& L, const FrameTotals& t) {
     const FramePlan& p = L.plan;
-    const Control& h = *L.h_ctl;
+    const Control& h = *L.h_ctl.ptr;
     const bool render = p.render, scan = p.scan;
     bgs_stats& stt = L.result;
     std::memset(&stt, 0, sizeof stt);
@@ -617,8 +520,8 @@ void fill_stats(const bgs_ctx* ctx, Lane& L, const FrameTotals& t) {
     stt.sort_path = p.bucket ? 1u : 0u;
     stt.list_capacity = (render && scan) ? L.pending_coarse_cap : 0u;
     stt.instance_count = render ? t.instances : 0;
-    stt.instance_capacity = L.inst_cap;
-    stt.list_entries_allocated = (render && scan) ? (uint64_t)L.coarse_entries : 0;
+    stt.instance_capacity = L.inst[0].capacity;
+    stt.list_entries_allocated = (render && scan) ? (uint64_t)(L.coarse.capacity / 2) : 0;
     stt.strip_tiles = (render && scan) ? h.strip_tiles : 0u;
     stt.tile_saturation = (render && scan && p.sat_kind && h.saturated_tiles_prev != 0xFFFFFFFFu)
                               ? (0x10000u | (h.saturated_tiles_prev & 0x7FFFu) | (p.raster.mode != 0 ? 0x80000000u : 0u)) : 0u;
@@ -659,7 +562,7 @@ int finish_lane(bgs_ctx* ctx, Lane& L) {
         int rc = check_watchdog(ctx, L);
         if (rc != BGS_OK) return rc;
         const FramePlan& p = L.plan;
-        const Control& h = *L.h_ctl;
+        const Control& h = *L.h_ctl.ptr;
         const FrameTotals t = frame_totals(p, h);
         bool rerun = false;
         if ((rc = check_capacities(ctx, L, t, attempt, &rerun)) != BGS_OK) return rc;
@@ -685,7 +588,7 @@ int finish_lane(bgs_ctx* ctx, Lane& L) {
         L.last_sorted_n = p.render ? h.draw_count : p.n;
         if (!p.render && h.draw_count < p.n) {
             // bgs_sort contract: one contiguous list, culled entries last (ascending index)
-            HIP_TRY(ctx, hipMemcpyAsync(const_cast<uint2*>(L.last_sorted) + h.draw_count, L.culled,
+            HIP_TRY(ctx, hipMemcpyAsync(const_cast<uint2*>(L.last_sorted) + h.draw_count, L.culled.ptr,
                                         (size_t)(p.n - h.draw_count) * sizeof(uint2), hipMemcpyDeviceToDevice, L.stream));
             HIP_TRY(ctx, hipStreamSynchronize(L.stream));
         }
@@ -873,8 +776,8 @@ FramePlan plan_frame(const bgs_ctx& ctx, const Lane& L, const FrameInputs& in) {
         // (order_grid); it is made again from the newest completed costs every TILE_ORDER_REFRESH-th frame. (ensure_cost
         // keeps the lane's buffers, and what they hold, unless the grid outgrew them.)
         const uint32_t grid = (uint32_t)fp.tiles_x | ((uint32_t)fp.tiles_y << 16);
-        const bool kept = L.cost[0] && p.ntiles <= L.cost_tiles;
-        const bool have_costs = kept && L.cost_done && L.cost_done != L.cost[L.cost_parity] && L.cost_done_grid == grid;
+        const bool kept = cost_holds(L, p.ntiles);
+        const bool have_costs = kept && L.cost_done && L.cost_done != L.cost[L.cost_parity].ptr && L.cost_done_grid == grid;
         const bool have_order = kept && L.order_grid == grid;
         p.refresh = have_costs && (!have_order || L.order_age + 1u >= TILE_ORDER_REFRESH || (flags & BGS_DEBUG_ORDER_EVERY_FRAME));
         p.ordered = p.refresh || have_order;
@@ -900,8 +803,8 @@ GraphKey graph_key(const FramePlan& p, const FrameInputs& in, const Lane& L, con
     const FrameParams& fp = p.fp;
     const void* planes[6] = {in.cloud->ptrs.position_visibility, in.cloud->ptrs.packed, nullptr, nullptr, nullptr, nullptr};
     std::memcpy(key.cloud, planes, sizeof planes);
-    const void* bufs[11] = {L.entries[0], L.entries[1], L.culled, L.records, L.coarse, L.fb, L.fb8, L.scratch, L.d_fp,
-                            L.h_ctl_dev, L.bucket_slots};   // (L.rects lives and dies with L.entries)
+    const void* bufs[11] = {L.entries[0].ptr, L.entries[1].ptr, L.culled.ptr, L.records.ptr, L.coarse.ptr, L.fb.ptr, L.fb8.ptr,
+                            L.scratch.ptr, L.d_fp.ptr, L.h_ctl_dev, L.bucket_slots.ptr};   // (L.rects lives and dies with L.entries: ensure_entries)
     std::memcpy(key.bufs, bufs, sizeof bufs);
     key.n = p.n; key.format = p.cloud_format; key.places = p.places; key.sort_mode = in.settings.sort_mode;
     key.gaussian_mode = fp.gaussian_mode; key.aabb = fp.aabb;
@@ -917,7 +820,7 @@ GraphKey graph_key(const FramePlan& p, const FrameInputs& in, const Lane& L, con
     key.raster_variant = r.samples | (r.depth ? 0x100u : 0u) | (r.overlay ? 0x200u : 0u) | (r.mode == 1 ? 0x400u : r.mode == 2 ? 0x800u : 0u);
     key.split_sub = p.split_sub_out;   // (round 5's advisor: a replay across a 524 k-pair step of the hint left a table of the captured sub under the new sub's label)
     key.sup_edge = p.sup_edge;
-    key.scratch_bytes = L.scratch_bytes; key.scratch_inst_cap = L.scratch_inst_cap; key.scratch_n = L.scratch_n;
+    key.scratch = L.layout;
     key.coarse_cap = coarse_cap;
     key.sort_path = p.bucket ? (p.bucket_sub | (p.wide ? 0x100u : 0u)) : 0u;   // (the bucket sort's grid and instantiation and keygen's dynamic LDS follow it)
     return key;
@@ -955,27 +858,19 @@ int ensure_frame_buffers(bgs_ctx* ctx, Lane& L, const FramePlan& p, const FrameI
     int rc;
     if ((rc = lane_create(ctx, L)) != BGS_OK) return rc;
     if ((rc = ensure_entries(ctx, L, p.n)) != BGS_OK) return rc;
-    if (p.bucket && p.bucket_sub > BUCKET_SUB_KERNARG && !L.d_split_keys) {   // the lane's device table + its pinned staging
-        L.d_split_keys = dev_alloc<uint32_t>(BUCKET_MAX);
-        void* hp = nullptr;
-        if (!L.d_split_keys || hipHostMalloc(&hp, BUCKET_MAX * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(ctx, BGS_ENOMEM, "hipMalloc / hipHostMalloc(splitter table) failed");
-        }
-        L.h_split_keys = (uint32_t*)hp;
-    }
+    if (p.bucket && p.bucket_sub > BUCKET_SUB_KERNARG && (rc = ensure_split_keys(ctx, L)) != BGS_OK) return rc;
     if (p.bucket && (rc = ensure_bucket_slots(ctx, L, p.bucket_sub, p.wide)) != BGS_OK) return rc;
     if (p.render) {
         if (p.scan) {
             if ((rc = ensure_coarse(ctx, L, p.n, p.num_st, in.debug_flags, coarse_cap)) != BGS_OK) return rc;
             if ((rc = ensure_rects(ctx, L)) != BGS_OK) return rc;
         } else {
-            if ((rc = ensure_instances(ctx, L, std::max<uint64_t>(L.inst_cap, MIN_INSTANCE_CAPACITY))) != BGS_OK) return rc;
+            if ((rc = ensure_instances(ctx, L, std::max<uint64_t>(L.inst[0].capacity, MIN_INSTANCE_CAPACITY))) != BGS_OK) return rc;
         }
         if ((rc = ensure_records(ctx, L, (size_t)p.n * p.rec_bytes)) != BGS_OK) return rc;
         if ((rc = ensure_framebuffer(ctx, L, (uint32_t)p.fp.width, (uint32_t)p.fp.height, in.output_srgb8 || in.output_rgba16f)) != BGS_OK) return rc;
     }
-    if ((rc = ensure_scratch(ctx, L, p.n, L.inst_cap)) != BGS_OK) return rc;
+    if ((rc = ensure_scratch(ctx, L, p.n, L.inst[0].capacity)) != BGS_OK) return rc;
     if (p.heavy && (rc = ensure_heavy(ctx, L, p.ntiles)) != BGS_OK) return rc;
     if (p.cost && (rc = ensure_cost(ctx, L, p.ntiles)) != BGS_OK) return rc;
     return BGS_OK;
@@ -999,44 +894,45 @@ int enqueue_frame(bgs_ctx* ctx, Lane& L, const FrameInputs& in) {
     hipStream_t st = L.stream;
     const bool need_memset = !L.scratch_clean;  // else the previous frame's rasteriser left it zeroed
     if (need_memset) L.ctl_parity = 0;
-    Control* ctl = (Control*)(L.scratch + (L.ctl_parity ? L.off_ctl1 : 0));
-    uint32_t* depth_status = (uint32_t*)(L.scratch + L.off_depth_status);
-    unsigned long long* scan_status = (unsigned long long*)(L.scratch + L.off_scan_status);
-    uint32_t* tile_status = (uint32_t*)(L.scratch + L.off_tile_status);
-    uint2* ranges = (uint2*)(L.scratch + L.off_ranges);
-    uint32_t* bin_status = (uint32_t*)(L.scratch + L.off_bin_status);
-    uint32_t* part_status = (uint32_t*)(L.scratch + L.off_part_status);
-    const size_t depth_tiles = ((size_t)L.scratch_n + sort_tile_size(false) - 1) / sort_tile_size(false) + 1;
+    const ScratchLayout& lay = L.layout;
+    uint8_t* const scratch = L.scratch.ptr;
+    Control* ctl = (Control*)(scratch + (L.ctl_parity ? lay.off_ctl1 : 0));
+    uint32_t* depth_status = (uint32_t*)(scratch + lay.off_depth_status);
+    unsigned long long* scan_status = (unsigned long long*)(scratch + lay.off_scan_status);
+    uint32_t* tile_status = (uint32_t*)(scratch + lay.off_tile_status);
+    uint2* ranges = (uint2*)(scratch + lay.off_ranges);
+    uint32_t* bin_status = (uint32_t*)(scratch + lay.off_bin_status);
+    uint32_t* part_status = (uint32_t*)(scratch + lay.off_part_status);
     const uint32_t grid = (uint32_t)fp.tiles_x | ((uint32_t)fp.tiles_y << 16);
-    uint8_t* const heavy_out = p.heavy ? L.heavy[L.heavy_parity] : nullptr;
+    uint8_t* const heavy_out = p.heavy ? L.heavy[L.heavy_parity].ptr : nullptr;
     const uint8_t* const heavy_in = (p.heavy && L.heavy_done && L.heavy_done != heavy_out && L.heavy_done_grid == grid) ? L.heavy_done : nullptr;
-    uint16_t* const cost_out = p.cost ? L.cost[L.cost_parity] : nullptr;
+    uint16_t* const cost_out = p.cost ? L.cost[L.cost_parity].ptr : nullptr;
     const uint16_t* const cost_in = p.refresh ? L.cost_done : nullptr;
-    uint16_t* const tile_order = p.ordered ? L.order : nullptr;
-    uint2* const draw_list = L.entries[places & 1u];  // the passes ping-pong from entries[0]
+    uint16_t* const tile_order = p.ordered ? L.order.ptr : nullptr;
+    uint2* const draw_list = L.entries[places & 1u].ptr;  // the passes ping-pong from entries[0]
     // SortMode::Rayon / Std sort ascending on the inverted key; the last step of either path un-inverts it
     const uint32_t final_xor = (fp.sort_mode == BGS_SORT_RAYON || fp.sort_mode == BGS_SORT_STD) ? 0xFFFFFFFFu : 0u;
 
     KeygenLaunch kg{};
     kg.fp = fp;
     kg.pos = in.cloud->ptrs.position_visibility;
-    kg.entries = L.entries[0];
-    kg.culled = p.culled_tail ? L.culled : nullptr;
+    kg.entries = L.entries[0].ptr;
+    kg.culled = p.culled_tail ? L.culled.ptr : nullptr;
     kg.ctl = ctl;
     kg.part_status = part_status;
     kg.places = places;
     kg.ticket_slot = 7;
-    kg.fp_out = L.d_fp;
+    kg.fp_out = L.d_fp.ptr;
     kg.zero_word = reinterpret_cast<uint32_t*>(heavy_out);   // keygen, the frame's first kernel, zeroes the heavy-tile list's count
-    kg.bucket_slots = L.bucket_slots;
+    kg.bucket_slots = L.bucket_slots.ptr;
     kg.bucket_status = depth_status;  // the depth passes' look-back words are free in a bucket-sort frame
     if (bucket) {
         if (p.split_slot >= 0) {
             const SplitterKeys& tk = ctx->split_slots[p.split_slot].table;
             const uint32_t nkeys = BUCKET_COUNT * p.bucket_sub - 1u;
             if (p.bucket_sub <= BUCKET_SUB_KERNARG) std::memcpy(kg.split.key, tk.key, nkeys * sizeof(uint32_t));
-            else std::memcpy(L.h_split_keys, tk.key, nkeys * sizeof(uint32_t));   // (the lane's previous frame is complete: nobody reads the staging)
-            kg.split.device_keys = L.d_split_keys;
+            else std::memcpy(L.h_split_keys.ptr, tk.key, nkeys * sizeof(uint32_t));   // (the lane's previous frame is complete: nobody reads the staging)
+            kg.split.device_keys = L.d_split_keys.ptr;
         } else {  // BGS_DEBUG_GUESSED_SPLITTERS: equal steps over the 32-bit range (badly balanced)
             for (uint32_t i = 0; i < BUCKET_COUNT; ++i) kg.split.key[i] = (i + 1u) << 24;
         }
@@ -1050,9 +946,9 @@ int enqueue_frame(bgs_ctx* ctx, Lane& L, const FrameInputs& in) {
         cl.part_status = part_status;
         cl.depth_status = depth_status;
         cl.bin_status = bin_status;
-        cl.other_ctl = (Control*)(L.scratch + (L.ctl_parity ? 0 : L.off_ctl1));
+        cl.other_ctl = (Control*)(scratch + (L.ctl_parity ? 0 : lay.off_ctl1));
         cl.host_ctl = L.h_ctl_dev;
-        cl.pass_stride = (uint32_t)(depth_tiles * RADIX_BASE);
+        cl.pass_stride = lay.pass_stride;
         cl.places = bucket ? 0u : places;
         cl.depth_tile = sort_tile_size(p.large);
         cl.sorted = draw_list;
@@ -1089,7 +985,7 @@ int enqueue_frame(bgs_ctx* ctx, Lane& L, const FrameInputs& in) {
         if (cost_in) launch_tile_order(st, cost_in, tile_order, p.ntiles, fp, p.raster.mode != 0);   // (counted with the frame's first stage)
         if (have_keygen) {
             if (bucket && p.bucket_sub > BUCKET_SUB_KERNARG) {
-                const hipError_t ce = hipMemcpyAsync(L.d_split_keys, L.h_split_keys, (BUCKET_COUNT * p.bucket_sub - 1u) * sizeof(uint32_t),
+                const hipError_t ce = hipMemcpyAsync(L.d_split_keys.ptr, L.h_split_keys.ptr, (BUCKET_COUNT * p.bucket_sub - 1u) * sizeof(uint32_t),
                                                      hipMemcpyHostToDevice, st);
                 if (ce != hipSuccess) return ce;
             }
@@ -1099,53 +995,52 @@ int enqueue_frame(bgs_ctx* ctx, Lane& L, const FrameInputs& in) {
         mark(1);
         int cur = 0;
         if (bucket) {
-            const hipError_t e = launch_bucket_sort(st, L.bucket_slots, draw_list, ctl, final_xor, BUCKET_COUNT * p.bucket_sub, p.wide);
+            const hipError_t e = launch_bucket_sort(st, L.bucket_slots.ptr, draw_list, ctl, final_xor, BUCKET_COUNT * p.bucket_sub, p.wide);
             if (e != hipSuccess) return e;
         }
         for (uint32_t q = 0; q < (bucket ? 0u : places); ++q) {
             // only the V' drawable entries are sorted; the culled tail is already in its final order
-            launch_onesweep_pass(st, L.entries[cur], L.entries[cur ^ 1], &ctl->draw_count, n, ctl->hist_depth[q],
-                                 depth_status + (size_t)q * depth_tiles * RADIX_BASE, &ctl->ticket[q][0], &ctl->error,
+            launch_onesweep_pass(st, L.entries[cur].ptr, L.entries[cur ^ 1].ptr, &ctl->draw_count, n, ctl->hist_depth[q],
+                                 depth_status + (size_t)q * lay.pass_stride, &ctl->ticket[q][0], &ctl->error,
                                  q * RADIX_BITS, q + 1 == places ? final_xor : 0u, p.large, p.sort_blocks);
             cur ^= 1;
         }
         mark(2);
         if (render && scan) {
-            launch_project_bin(st, fp, L.d_fp, in.cloud->ptrs, draw_list, L.culled, ctl, bin_status, L.records, L.rects, L.coarse,
+            launch_project_bin(st, fp, L.d_fp.ptr, in.cloud->ptrs, draw_list, L.culled.ptr, ctl, bin_status, L.records.ptr, L.rects.ptr, L.coarse.ptr,
                                coarse_cap, p.sup_edge, /*ticket_slot=*/4, p.bin_blocks, p.binning_blocks, p.wide_bin);
             mark(3);
-            launch_raster_scan(st, fp, L.d_fp, L.records, L.coarse, coarse_cap, p.sup_edge, ctl, L.fb, L.fb8,
+            launch_raster_scan(st, fp, L.d_fp.ptr, L.records.ptr, L.coarse.ptr, coarse_cap, p.sup_edge, ctl, L.fb.ptr, L.fb8.ptr,
                                (flags & BGS_DEBUG_SEPARATE_ENCODE) ? 0u : p.out_format, cl, ctx->tile_trace,
                                p.raster.mode, heavy_in, heavy_out, tile_order, cost_out);
             mark(6);
         } else if (render) {
-            const uint32_t capacity = (uint32_t)std::min<uint64_t>(L.inst_cap, MAX_INSTANCE_CAPACITY);
-            launch_project_emit(st, fp, in.cloud->ptrs, draw_list, L.culled, ctl, scan_status, L.records, L.inst[0], capacity,
+            const uint32_t capacity = (uint32_t)std::min<uint64_t>(L.inst[0].capacity, MAX_INSTANCE_CAPACITY);
+            launch_project_emit(st, fp, in.cloud->ptrs, draw_list, L.culled.ptr, ctl, scan_status, L.records.ptr, L.inst[0].ptr, capacity,
                                 /*ticket_slot=*/4, ctx->num_cus * 3);
             mark(3);
-            const size_t inst_tiles = (L.scratch_inst_cap + sort_tile_size(true) - 1) / sort_tile_size(true) + 1;
             for (uint32_t q = 0; q < 2; ++q)
-                launch_onesweep_pass(st, L.inst[q], L.inst[q ^ 1], &ctl->instance_count, capacity, ctl->hist_tile[q],
-                                     tile_status + (size_t)q * inst_tiles * RADIX_BASE, &ctl->ticket[5 + q][0],
+                launch_onesweep_pass(st, L.inst[q].ptr, L.inst[q ^ 1].ptr, &ctl->instance_count, capacity, ctl->hist_tile[q],
+                                     tile_status + (size_t)q * lay.inst_tiles * RADIX_BASE, &ctl->ticket[5 + q][0],
                                      &ctl->error, q * RADIX_BITS, 0u, true, ctx->num_cus * 4);
             mark(4);
-            launch_tile_ranges(st, L.inst[0], ctl, ranges);
+            launch_tile_ranges(st, L.inst[0].ptr, ctl, ranges);
             mark(5);
-            launch_raster(st, fp, L.records, L.inst[0], ranges, L.fb, in.view.clear_color, ctl);
+            launch_raster(st, fp, L.records.ptr, L.inst[0].ptr, ranges, L.fb.ptr, in.view.clear_color, ctl);
             mark(6);
         }
         // BINNING_SCAN frames get their sRGB8 image from the rasteriser itself (BGS_DEBUG_SEPARATE_ENCODE: from the
         // separate encode pass, for A/B runs)
         if (p.want_srgb8 && !(render && scan && !(flags & BGS_DEBUG_SEPARATE_ENCODE)))
-            launch_encode_srgb8(st, L.fb, L.fb8, (uint32_t)fp.width * (uint32_t)fp.height, L.d_fp, p.out_format);
+            launch_encode_srgb8(st, L.fb.ptr, L.fb8.ptr, (uint32_t)fp.width * (uint32_t)fp.height, L.d_fp.ptr, p.out_format);
         return hipGetLastError();
     };
     if (p.graph_ok && !need_memset && prof == 0 && have_keygen) {
         if ((rc = launch_graph(ctx, L, graph_key(p, in, L, kg, coarse_cap), kg, issue)) != BGS_OK) return rc;
     } else {
-        if (need_memset) HIP_TRY(ctx, hipMemsetAsync(L.scratch, 0, L.scratch_bytes, st));
+        if (need_memset) HIP_TRY(ctx, hipMemsetAsync(scratch, 0, lay.bytes, st));
         // no keygen (empty cloud): the kernels behind it still read the frame's parameters
-        if (!have_keygen) HIP_TRY(ctx, hipMemcpyAsync(L.d_fp, &fp, sizeof fp, hipMemcpyHostToDevice, st));
+        if (!have_keygen) HIP_TRY(ctx, hipMemcpyAsync(L.d_fp.ptr, &fp, sizeof fp, hipMemcpyHostToDevice, st));
         HIP_TRY(ctx, issue());
     }
     // the Control block travels back with the frame; it is looked at when the lane is completed.
@@ -1156,7 +1051,7 @@ int enqueue_frame(bgs_ctx* ctx, Lane& L, const FrameInputs& in) {
         L.ctl_parity ^= 1u;
     } else {
         if (places == 4 && n > 0) launch_splitters(st, draw_list, ctl, final_xor, p.split_sub_out);
-        HIP_TRY(ctx, hipMemcpyAsync(L.h_ctl, ctl, sizeof(Control), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipMemcpyAsync(L.h_ctl.ptr, ctl, sizeof(Control), hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(ctx, hipEventRecord(L.done, st));
 
@@ -1166,7 +1061,7 @@ int enqueue_frame(bgs_ctx* ctx, Lane& L, const FrameInputs& in) {
     L.fb_valid = !(p.out_format & OUT_SKIP_F32) || (flags & BGS_DEBUG_SEPARATE_ENCODE);
     L.fb8_is_f16 = (p.out_format & OUT_RGBA16F) != 0u;
     L.fb8_valid = p.want_srgb8;
-    if (p.want_srgb8) L.fb8_out = in.srgb8_target ? in.srgb8_target : L.fb8;
+    if (p.want_srgb8) L.fb8_out = in.srgb8_target ? in.srgb8_target : L.fb8.ptr;
     L.pending = true;
     L.pending_coarse_cap = coarse_cap;
     L.in = in;

@@ -156,6 +156,51 @@ inline RasterInst raster_instantiation(const FrameParams& fp, uint32_t level, bo
     return r;
 }
 
+// A lane's zeroed-every-frame scratch region for n splats and inst_cap tile instances, every part 256-byte aligned:
+//   [Control | depth status | scan status | tile status | ranges | bin status | partition status | Control 1]
+// (Control 1: the lane's second Control block, see FrameCleanup.) The look-back arrays have one spare tile each; the depth
+// passes may use either tile size, so theirs are sized for the smaller one. The depth passes' four arrays lie pass_stride
+// words apart, the tile passes' two inst_tiles * RADIX_BASE words. All fields are 8 bytes or pairs of 4: no padding, so
+// that a GraphKey can carry a layout and be compared bytewise.
+struct ScratchLayout {
+    uint64_t bytes = 0;   // of the whole region
+    uint64_t off_depth_status = 0, off_scan_status = 0, off_tile_status = 0, off_ranges = 0, off_bin_status = 0,
+             off_part_status = 0, off_ctl1 = 0;
+    uint64_t depth_tiles = 0, inst_tiles = 0;
+    uint64_t inst_cap = 0;   // what it was made for
+    uint32_t n = 0;
+    uint32_t pass_stride = 0;
+};
+static_assert(sizeof(ScratchLayout) == 11 * 8 + 2 * 4, "ScratchLayout has no padding (GraphKey)");
+
+inline ScratchLayout scratch_layout(uint32_t n, uint64_t inst_cap) {
+    const auto align256 = [](uint64_t v) { return (v + 255u) / 256u * 256u; };
+    ScratchLayout s;
+    s.n = n;
+    s.inst_cap = inst_cap;
+    s.depth_tiles = ((uint64_t)n + sort_tile_size(false) - 1) / sort_tile_size(false) + 1;
+    const uint64_t scan_tiles = ((uint64_t)n + 255) / 256 + 1;
+    s.inst_tiles = (inst_cap + sort_tile_size(true) - 1) / sort_tile_size(true) + 1;
+    s.pass_stride = (uint32_t)(s.depth_tiles * RADIX_BASE);
+    uint64_t off = align256(sizeof(Control));
+    s.off_depth_status = off;
+    off += align256(4 * s.depth_tiles * RADIX_BASE * sizeof(uint32_t));
+    s.off_scan_status = off;
+    off += align256(scan_tiles * sizeof(unsigned long long));
+    s.off_tile_status = off;
+    off += align256(2 * s.inst_tiles * RADIX_BASE * sizeof(uint32_t));
+    s.off_ranges = off;
+    off += align256((uint64_t)RADIX_BASE * RADIX_BASE * 2 * sizeof(uint32_t));   // (uint2 per tile)
+    s.off_bin_status = off;
+    off += align256(scan_tiles * MAX_SUPERTILES * sizeof(uint32_t));
+    s.off_part_status = off;
+    off += align256((((uint64_t)n + KEYGEN_TILE - 1) / KEYGEN_TILE + 1) * sizeof(uint32_t));
+    s.off_ctl1 = off;
+    off += align256(sizeof(Control));
+    s.bytes = off;
+    return s;
+}
+
 // A splitter table is usable only if it is ascending: bucket(key) = number of splitters <= key is monotone in
 // the key exactly then, and the bucket sort's ORDER (not just its balance) rests on that.
 inline bool splitters_ascending(const uint32_t* key, uint32_t count) {

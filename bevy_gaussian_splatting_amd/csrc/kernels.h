@@ -64,11 +64,7 @@ struct FrameCleanup {
     const uint32_t* order_stats;
 };
 
-// Onesweep geometry: 256 threads x KPT keys per tile.
-constexpr int SORT_THREADS = 256;
-constexpr int SORT_KPT_SMALL = 8;   // 2048-pair tiles: more tiles for <= ~4M keys
-constexpr int SORT_KPT_LARGE = 16;  // 4096-pair tiles
-inline uint32_t sort_tile_size(bool large) { return SORT_THREADS * (large ? SORT_KPT_LARGE : SORT_KPT_SMALL); }
+// (the onesweep tile geometry, SORT_THREADS .. sort_tile_size, and KEYGEN_TILE: bgs_device.h)
 
 // keygen + fused global digit histograms (radix_sort_a, src/sort/radix.wgsl:71-107) + stable
 // partition: drawable entries -> `entries` (index order), culled-sentinel entries -> `culled`
@@ -100,7 +96,6 @@ struct KeygenLaunch {
     hipError_t launch(hipStream_t stream);
     hipError_t update_node(hipGraphExec_t exec, hipGraphNode_t node);  // same launch, as a graph node update
 };
-constexpr uint32_t KEYGEN_TILE = 2048;  // the smallest tile: what the chain words are allocated and zeroed for
 // Splats per keygen tile (= per block and ticket) for a cloud of n splats. The chained scans behind a tile cost
 // per TILE, so tiles grow with the cloud: 2048 (256 threads x 8) for small clouds, 4096 (256 x 16) from 2^19 splats.
 // BGS_KEYGEN_WIDE_THREADS = 1024 builds the wide tiles as 1024 threads x 4 (and 8192-splat tiles, 1024 x 8, from

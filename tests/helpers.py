@@ -52,6 +52,22 @@ class FrameParamsC(ctypes.Structure):
     ]
 
 
+class ScratchLayoutC(ctypes.Structure):
+    """ctypes image of bgs::ScratchLayout (bevy_gaussian_splatting_amd/csrc/frame_params.h)."""
+
+    REGIONS = ("off_depth_status", "off_scan_status", "off_tile_status", "off_ranges", "off_bin_status", "off_part_status",
+               "off_ctl1")   # in address order, behind the first Control block at 0
+    _fields_ = ([("bytes", ctypes.c_uint64)] + [(r, ctypes.c_uint64) for r in REGIONS] +
+                [("depth_tiles", ctypes.c_uint64), ("inst_tiles", ctypes.c_uint64), ("inst_cap", ctypes.c_uint64),
+                 ("n", ctypes.c_uint32), ("pass_stride", ctypes.c_uint32)])
+
+
+def scratch_layout(n: int, inst_cap: int) -> ScratchLayoutC:
+    out = ScratchLayoutC()
+    shim().shim_scratch_layout(n, inst_cap, ctypes.byref(out))
+    return out
+
+
 class ShimOut(ctypes.Structure):
     _fields_ = [
         ("visible", ctypes.c_int32), ("draw", ctypes.c_int32),
@@ -76,7 +92,7 @@ def shim() -> ctypes.CDLL:
     global _shim
     if _shim is not None:
         return _shim
-    deps = [SHIM_SRC, os.path.join(CSRC, "..", "..", "include", "bgs_diag.h")] + [os.path.join(CSRC, f) for f in ("splat_math.h", "exact_log.h", "bgs_device.h", "frame_params.h")]
+    deps = [SHIM_SRC, os.path.join(CSRC, "..", "..", "include", "bgs_diag.h")] + [os.path.join(CSRC, f) for f in ("splat_math.h", "exact_log.h", "bgs_device.h", "frame_params.h", "device_buffer.h")]
     if not os.path.exists(SHIM_LIB) or any(os.path.getmtime(d) > os.path.getmtime(SHIM_LIB) for d in deps):
         subprocess.run(
             ["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fopenmp", "-shared", "-fPIC",
@@ -112,7 +128,21 @@ def shim() -> ctypes.CDLL:
     l.shim_project.restype = None
     l.shim_distance_to_camera.argtypes = [ctypes.POINTER(FrameParamsC), fp]
     l.shim_distance_to_camera.restype = ctypes.c_float
+    l.shim_scratch_layout.argtypes = [ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(ScratchLayoutC)]
+    l.shim_scratch_layout.restype = None
+    l.shim_scratch_layout_size.argtypes = []
+    l.shim_scratch_layout_size.restype = ctypes.c_uint32
+    i64p, u64p, vp = ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p
+    for name, args, res in (("shim_mem_reset", [ctypes.c_int64], None), ("shim_mem_counters", [i64p], None),
+                            ("shim_buf_new", [], vp), ("shim_buf_delete", [vp], None),
+                            ("shim_buf_reserve", [vp, ctypes.c_uint64, ctypes.c_int64], ctypes.c_int),
+                            ("shim_buf_reset", [vp], None), ("shim_buf_state", [vp, u64p], None),
+                            ("shim_buf_move_assign", [vp, vp], None), ("shim_buf_move_new", [vp], vp),
+                            ("shim_buf_release_and_free", [vp], None),
+                            ("shim_buf_reserve_group", [vp, vp, vp, ctypes.c_uint64], ctypes.c_int)):
+        getattr(l, name).argtypes, getattr(l, name).restype = args, res
     assert l.shim_frame_params_size() == ctypes.sizeof(FrameParamsC)
+    assert l.shim_scratch_layout_size() == ctypes.sizeof(ScratchLayoutC)
     _shim = l
     return l
 

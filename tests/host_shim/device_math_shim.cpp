@@ -4,6 +4,9 @@
 // so tests/test_device_math_host.py can check the per-splat arithmetic the HIP kernels run
 // against the oracle WITHOUT a GPU. This is a pre-flight check, not a product path: libbgs
 // never runs these functions on the host and has no CPU fallback.
+#include <stdlib.h>
+
+#include "../../bevy_gaussian_splatting_amd/csrc/device_buffer.h"
 #include "../../bevy_gaussian_splatting_amd/csrc/frame_params.h"
 #include "../../bevy_gaussian_splatting_amd/csrc/splat_math.h"
 
@@ -71,6 +74,52 @@ uint32_t shim_canonical_supertile_level(uint32_t level, const uint32_t* edges) {
 int shim_raster_scan_mode(int variant, uint32_t samples, int overlay, uint32_t level, int kind_midround, int pipeline_depth,
                           uint32_t debug_flags) {
     return raster_scan_mode(variant, samples, overlay != 0, level, kind_midround != 0, pipeline_depth, debug_flags);
+}
+
+// the scratch layout of a lane (frame_params.h), as 11 x u64 + 2 x u32
+void shim_scratch_layout(uint32_t n, uint64_t inst_cap, ScratchLayout* out) { *out = scratch_layout(n, inst_cap); }
+uint32_t shim_scratch_layout_size(void) { return (uint32_t)sizeof(ScratchLayout); }
+
+// ---- Buffer (device_buffer.h) over a memory policy that counts: live allocations and their peak, calls, the bytes of the
+// last request; fail_at = k makes the k-th alloc() from now fail
+struct CountingMem {
+    static inline int64_t live = 0, peak = 0, allocs = 0, frees = 0, last_bytes = 0, fail_at = 0;
+    static void* alloc(size_t bytes) {
+        ++allocs;
+        last_bytes = (int64_t)bytes;
+        if (fail_at > 0 && --fail_at == 0) return nullptr;
+        if (++live > peak) peak = live;
+        return malloc(bytes ? bytes : 1);
+    }
+    static void free(void* p) { ++frees; --live; ::free(p); }
+};
+using TestBuffer = Buffer<uint64_t, CountingMem>;
+
+void shim_mem_reset(int64_t fail_at) {
+    CountingMem::peak = CountingMem::live;
+    CountingMem::allocs = CountingMem::frees = CountingMem::last_bytes = 0;
+    CountingMem::fail_at = fail_at;
+}
+void shim_mem_counters(int64_t out[5]) {
+    out[0] = CountingMem::live; out[1] = CountingMem::peak; out[2] = CountingMem::allocs; out[3] = CountingMem::frees;
+    out[4] = CountingMem::last_bytes;
+}
+void* shim_buf_new(void) { return new TestBuffer(); }
+void shim_buf_delete(void* b) { delete (TestBuffer*)b; }
+int shim_buf_reserve(void* b, uint64_t count, int64_t min_bytes) {
+    TestBuffer& t = *(TestBuffer*)b;
+    return (min_bytes < 0 ? t.reserve(count) : t.reserve(count, (size_t)min_bytes)) ? 1 : 0;
+}
+void shim_buf_reset(void* b) { ((TestBuffer*)b)->reset(); }
+void shim_buf_state(const void* b, uint64_t out[2]) {
+    out[0] = (uint64_t)(uintptr_t)((const TestBuffer*)b)->ptr;
+    out[1] = ((const TestBuffer*)b)->capacity;
+}
+void shim_buf_move_assign(void* dst, void* src) { *(TestBuffer*)dst = static_cast<TestBuffer&&>(*(TestBuffer*)src); }
+void* shim_buf_move_new(void* src) { return new TestBuffer(static_cast<TestBuffer&&>(*(TestBuffer*)src)); }
+void shim_buf_release_and_free(void* b) { CountingMem::free(((TestBuffer*)b)->release()); }
+int shim_buf_reserve_group(void* b0, void* b1, void* b2, uint64_t count) {
+    return reserve_group(count, *(TestBuffer*)b0, *(TestBuffer*)b1, *(TestBuffer*)b2);
 }
 
 // keys exactly as keygen_kernel stores them (before any final-pass un-inversion)
