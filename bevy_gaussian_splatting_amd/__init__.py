@@ -32,6 +32,13 @@ from .settings import (
 from .io_ply import parse_ply_3d, write_ply_3d
 from .io_gcloud import decode_gcloud, encode_gcloud, read_gcloud, write_gcloud
 from .sort_policy import SortConfig, SortTrigger, update_sort_trigger
+from .particles import (
+    PARTICLE_BEHAVIOR_DTYPE,
+    ParticleBehaviors,
+    ParticleBehaviorsHandle,
+    random_particle_behaviors,
+    step_reference,
+)
 from .plugin import (
     GaussianSplattingPlugin,
     PlanarGaussian3dHandle,
@@ -47,4 +54,5 @@ __all__ = [
     "RasterizeMode", "ShaderDefines", "SortMode", "compute_aabb",
     "parse_ply_3d", "write_ply_3d", "decode_gcloud", "encode_gcloud", "read_gcloud", "write_gcloud", "SortConfig", "SortTrigger", "update_sort_trigger",
     "GaussianSplattingPlugin", "PlanarGaussian3dHandle", "SortedEntries", "SORT_ENTRY_DTYPE",
+    "PARTICLE_BEHAVIOR_DTYPE", "ParticleBehaviors", "ParticleBehaviorsHandle", "random_particle_behaviors", "step_reference",
 ]

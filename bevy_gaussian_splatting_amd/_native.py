@@ -87,6 +87,7 @@ EXPORTED_SYMBOLS = (
     "bgs_comm_wait",
     "bgs_comm_stream",
     "bgs_comm_destroy",
+    "bgs_cloud_apply_particle_behaviors",
 )
 
 COMM_ID_BYTES = 128
@@ -329,6 +330,8 @@ def load() -> ctypes.CDLL:
     lib.bgs_comm_stream.restype = ctypes.c_int
     lib.bgs_comm_destroy.argtypes = [vp, vp]
     lib.bgs_comm_destroy.restype = None
+    lib.bgs_cloud_apply_particle_behaviors.argtypes = [vp, vp, vp, u32, ctypes.c_float]
+    lib.bgs_cloud_apply_particle_behaviors.restype = ctypes.c_int
     # the handshake a binding owes the library (a stale struct layout is refused here, not read past)
     rc = lib.bgs_abi_check(ABI_VERSION, ctypes.sizeof(BgsView), ctypes.sizeof(BgsSettings), ctypes.sizeof(BgsStats))
     if rc != BGS_OK:

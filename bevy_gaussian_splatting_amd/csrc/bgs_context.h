@@ -235,6 +235,9 @@ struct bgs_ctx {
     int next = 0;     // lane the next frame goes to
     int recent = 0;   // lane of the most recently enqueued frame
     uint64_t seq = 0;
+    // recorded behind the last particle step (apply_particle_step): every stream of the context waits for it, one created
+    // later included (assign_streams)
+    hipEvent_t step_done = nullptr;
 
     uint32_t binning = BINNING_SCAN;
     uint32_t debug_flags = 0;
@@ -337,6 +340,7 @@ int ensure_scratch(bgs_ctx* ctx, Lane& L, uint32_t n, uint64_t inst_cap);
 int enqueue_frame(bgs_ctx* ctx, Lane& L, const FrameInputs& in);
 int ensure_entries(bgs_ctx* ctx, Lane& L, uint32_t n);
 int run(bgs_ctx* ctx, const bgs_cloud* cloud, const bgs_view* view, const bgs_settings* s, bool render);   // bgs_sort / bgs_render
+int apply_particle_step(bgs_ctx* ctx, bgs_cloud* cloud, void* behaviors, uint32_t count, float dt);        // bgs_cloud_apply_particle_behaviors
 extern int g_queue_holders_mode;           // bgs_set_queue_holders
 extern std::mutex g_queue_holders_mutex;
 }  // namespace bgs_host

@@ -57,6 +57,8 @@ int assign_streams(bgs_ctx* ctx) {
                     for (auto& qh : g_queue_holders[ctx->device]) HIP_TRY(ctx, hipStreamCreateWithFlags(&qh, hipStreamNonBlocking));
             }
             HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->streams[si], hipStreamNonBlocking));
+            // a particle step may still be running on an older stream: the new one starts behind it, like its siblings
+            if (ctx->step_done) HIP_TRY(ctx, hipStreamWaitEvent(ctx->streams[si], ctx->step_done, 0));
         }
         L.stream = ctx->streams[si];
     }
@@ -1113,6 +1115,45 @@ int run(bgs_ctx* ctx, const bgs_cloud* cloud, const bgs_view* view, const bgs_se
         }
         if (ctx->learning.size() >= (1u << 16)) ctx->learning.clear();   // (a host that hashes noise into its settings)
     }
+    return BGS_OK;
+}
+
+// One step of particle behaviours on a resident cloud (bgs_cloud_apply_particle_behaviors; the arguments are checked there).
+// The step WRITES what every frame reads, so it is a pipeline barrier like bgs_cloud_free:
+//   1. Frames in flight are completed first. They were enqueued against the old positions, and a frame that finish_lane
+//      re-runs because a capacity was short must be re-run against those. Completed frames stay in the ring
+//      (bgs_pipeline_pop still hands them out, oldest first): unlike finish_all this only waits.
+//   2. The kernel goes on lane 0's stream, an event behind it, and every stream of the context waits for that event on
+//      the device. The host does not wait: the next bgs_sort / bgs_render on any lane runs behind the step, the call
+//      returns while the kernel may still be running.
+// What the context has learnt about the cloud stays as it is. Every item is a hint that the frame's own kernels check:
+//   - splitter tables (split_slots, keyed on the cloud): quantile keys of an earlier sorted list. Moved splats make the
+//     buckets uneven; a bucket that outgrows its slots sets sort_overflow and the frame is re-run on the digit passes, the
+//     table dropped (check_capacities) — the path a camera cut takes. A re-run sees the same, stepped, positions.
+//   - draw-count hint, list capacity, supertile level: grid sizes and capacities; kernels loop over tickets and count
+//     true totals, a short capacity re-runs the frame.
+//   - heavy-tile lists, tile costs and the raster order: balance only, every tile is drawn exactly once whatever they hold.
+//   - captured frame graphs: their nodes hold the ADDRESSES of the two position copies (GraphKey::cloud), which a step
+//     does not change; the positions are read when the graph runs, behind the event above.
+// So staleness is slow at worst, never wrong, and a small step (the usual case) keeps every hint useful.
+int apply_particle_step(bgs_ctx* ctx, bgs_cloud* cloud, void* behaviors, uint32_t count, float dt) {
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, BGS_EHIP, "hipSetDevice failed");
+    for (;;) {   // oldest first, so that the stats left behind are those of the most recent frame
+        int best = -1;
+        for (int i = 0; i < MAX_LANES; ++i)
+            if (ctx->lanes[i].pending && (best < 0 || ctx->lanes[i].seq < ctx->lanes[best].seq)) best = i;
+        if (best < 0) break;
+        int rc = finish_lane(ctx, ctx->lanes[best]);
+        if (rc != BGS_OK) return rc;
+        ctx->lanes[best].ready = true;
+    }
+    if (!ctx->step_done) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->step_done, hipEventDisableTiming));
+    hipStream_t st = ctx->lanes[0].stream;
+    launch_particle_step(st, behaviors, count, cloud->ptrs, dt);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(ctx->step_done, st));
+    for (hipStream_t other : ctx->streams)
+        if (other && other != st) HIP_TRY(ctx, hipStreamWaitEvent(other, ctx->step_done, 0));
     return BGS_OK;
 }
 

@@ -224,6 +224,12 @@ void launch_encode_srgb8(hipStream_t stream, const float4* framebuffer, uint32_t
 void launch_pack_cloud(hipStream_t stream, const uint4* pos, const uint4* a, uint32_t v4_a, const uint4* b, uint32_t v4_b,
                        const uint4* c, uint32_t v4_c, uint4* out, uint32_t stride_v4, uint32_t n);
 
+// One step of `count` particle behaviours (64-byte records in caller-owned device memory, particle_math.h) on a resident
+// cloud: p += dp in BOTH copies of the position (the plane and word 0 of the packed record), v += dv and a += da in the
+// record. Records with a negative (i32) or out-of-range index are skipped entirely. The cloud is written: the caller orders
+// the launch against every frame that reads it (bgs_cloud_apply_particle_behaviors).
+void launch_particle_step(hipStream_t stream, void* behaviors, uint32_t count, const CloudPtrs& cloud, float dt);
+
 // STREAM-triad on float4: a = b + s * c (HBM ceiling probe, bgs_hbm_probe).
 void launch_triad(hipStream_t stream, float4* a, const float4* b, const float4* c, float s, size_t n4,
                   int blocks);

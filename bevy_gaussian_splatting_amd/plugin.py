@@ -21,6 +21,7 @@ import numpy as np
 from . import _native
 from .camera import View
 from .gaussian import PlanarGaussian3d, PlanarGaussian3dF16
+from .particles import PARTICLE_BEHAVIOR_DTYPE, ParticleBehaviors, ParticleBehaviorsHandle
 from .settings import CloudSettings
 
 SORT_ENTRY_DTYPE = np.dtype([("key", np.uint32), ("index", np.uint32)])
@@ -172,6 +173,36 @@ class GaussianSplattingPlugin:
         else:
             raise TypeError("cloud must be PlanarGaussian3d or PlanarGaussian3dF16")
         return PlanarGaussian3dHandle(self, out, n, fmt, cloud.nbytes())
+
+    # -- particle behaviours (src/morph/particle.rs) -----------------------------------
+    def upload_particle_behaviors(self, behaviors) -> ParticleBehaviorsHandle:
+        """Put a behaviours buffer into device memory (`bgs_device_alloc` + `bgs_upload`). `behaviors` is a
+        `ParticleBehaviors` (validated against its cloud when it was built) or a bare array of PARTICLE_BEHAVIOR_DTYPE,
+        which goes up as it is: the C ABI's precondition (distinct indices of active records) is then the caller's."""
+        rec = behaviors.records if isinstance(behaviors, ParticleBehaviors) else np.ascontiguousarray(behaviors)
+        if rec.dtype != PARTICLE_BEHAVIOR_DTYPE or rec.ndim != 1:
+            raise TypeError("behaviors must be ParticleBehaviors or a 1-D array of PARTICLE_BEHAVIOR_DTYPE")
+        ptr = self.device_alloc(max(rec.nbytes, 64))
+        if rec.nbytes:
+            self.upload_bytes(ptr, rec)
+        return ParticleBehaviorsHandle(self, ptr, rec.shape[0])
+
+    def apply_particle_behaviors(self, handle: PlanarGaussian3dHandle, behaviors: ParticleBehaviorsHandle, dt: float) -> None:
+        """One step of the behaviours on the resident cloud (`bgs_cloud_apply_particle_behaviors`): positions (and
+        visibility) of the named splats move, velocity and acceleration of the records advance, on the device. Call it
+        before the frame's `render`, as the reference runs `run_particle_behaviors` before the prepass. Completes the
+        frames in flight (they keep their place in the ring), then only enqueues the step."""
+        self._check(self._lib.bgs_cloud_apply_particle_behaviors(
+            self._ctx, handle._ptr, ctypes.c_void_p(behaviors.ptr or 0), int(behaviors.count), ctypes.c_float(dt)))
+
+    def download_particle_behaviors(self, behaviors: ParticleBehaviorsHandle) -> np.ndarray:
+        """The records as the steps so far left them (`bgs_synchronize`, which completes the frames in flight, then
+        `bgs_download`)."""
+        out = np.empty(behaviors.count, PARTICLE_BEHAVIOR_DTYPE)
+        self.synchronize()
+        if out.nbytes:
+            self.download(behaviors.ptr, out)
+        return out
 
     # -- hot path --------------------------------------------------------------------
     def sort(self, handle: PlanarGaussian3dHandle, view: View, settings: CloudSettings,

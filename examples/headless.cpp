@@ -10,6 +10,10 @@
 // test: --cloud <file> (u32 n, then the four f32 planes) and --dump-f32 <file> (the last frame, RGBA f32).
 // --input-cloud <file.ply | file.gcloud> loads an INRIA .ply or a .gcloud container (the reference viewer's --input-cloud), --f16 uploads the cloud
 // in the f16 planar format.
+// --particle-count N (the reference viewer's flag, src/utils.rs:76-77; default 0) puts N random particle behaviours on
+// splats 0 .. N-1 (seeded with --gaussian-seed) and applies one step of --particle-dt seconds (default 1/60) before each
+// of the `frames` frames; --dump-particle-behaviors <file> writes the records as generated (64 bytes each), for the
+// parity test.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -100,8 +104,10 @@ bgs::PlanarGaussian3d read_planes(const std::string& path) {
 int main(int argc, char** argv) {
     uint32_t count = 10000, width = 1920, height = 1080, frames = 40, depth = 6;
     uint32_t msaa_samples = 0;   // 0 = not given: the view keeps Bevy's default Msaa (4 samples), as examples/headless.rs does
+    uint32_t particle_count = 0;
+    float particle_dt = 1.0f / 60.0f;
     uint64_t seed = 0;
-    std::string out_dir = "headless_output", cloud_path, dump_path, ply_path;
+    std::string out_dir = "headless_output", cloud_path, dump_path, ply_path, particle_dump_path;
     bool f16 = false, trained_like = false;
     bgs::CloudSettings settings;   // CloudSettings::default()
     // value names as clap's ValueEnum derives them from the reference's enums (kebab case; src/gaussian/settings.rs:17-57)
@@ -151,6 +157,9 @@ int main(int argc, char** argv) {
         else if (a == "--dump-f32") dump_path = next();
         else if (a == "--input-cloud") ply_path = next();
         else if (a == "--f16") f16 = true;
+        else if (a == "--particle-count") particle_count = (uint32_t)std::stoul(next());
+        else if (a == "--particle-dt") particle_dt = std::stof(next());
+        else if (a == "--dump-particle-behaviors") particle_dump_path = next();
         else { std::fprintf(stderr, "unknown flag %s\n", a.c_str()); return 2; }
     }
     try {
@@ -168,6 +177,17 @@ int main(int argc, char** argv) {
         if (msaa_samples) view.set_msaa_samples(msaa_samples);
         const bgs_settings native = settings.to_native();
 
+        // gaussian cloud particle effects (src/morph/particle.rs): behaviours on the first particle_count splats
+        std::optional<bgs::ParticleBehaviors> particles;
+        if (particle_count) {
+            const auto records = bgs::random_particle_behaviors(std::min<size_t>(particle_count, cloud.size()), seed);
+            if (!particle_dump_path.empty()) {
+                std::ofstream f(particle_dump_path, std::ios::binary);
+                f.write((const char*)records.data(), (std::streamsize)(records.size() * sizeof(bgs::ParticleBehavior)));
+            }
+            particles.emplace(plugin, records, handle);
+        }
+
         plugin.set_output_srgb8(true);  // the reference's target is TextureFormat::Rgba8UnormSrgb
         plugin.set_profiling(0);
         plugin.set_pipeline_depth(depth);
@@ -175,7 +195,10 @@ int main(int argc, char** argv) {
         for (uint32_t f = 0; f < 8; ++f) plugin.render(handle, view, native);  // allocations, hints
         plugin.synchronize();
         const auto t0 = std::chrono::steady_clock::now();
-        for (uint32_t f = 0; f < frames; ++f) plugin.render(handle, view, native);
+        for (uint32_t f = 0; f < frames; ++f) {
+            if (particles) particles->apply(handle, particle_dt);   // run_particle_behaviors runs before the frame's passes
+            plugin.render(handle, view, native);
+        }
         plugin.synchronize();
         const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 

@@ -44,7 +44,9 @@ extern "C" {
 
 #define BGS_VERSION_MAJOR 0
 #define BGS_VERSION_MINOR 4 /* 0.4: bgs_abi_check, bgs_comm_* (the multi-GPU frame gather), sample_count 0 = default; struct layouts as 0.3
-                               (0.3: bgs_view gained sample_count + depth_device_ptr, 16 bytes longer; bgs_stats 16 bytes longer than 0.2's) */
+                               (0.3: bgs_view gained sample_count + depth_device_ptr, 16 bytes longer; bgs_stats 16 bytes longer than 0.2's).
+                               Still 0.4 with the particle behaviours: purely additive (one function, one POD typedef; bgs_view,
+                               bgs_settings and bgs_stats as they were), so a 0.4 binding keeps working unchanged */
 
 typedef enum bgs_status {
     BGS_OK = 0,
@@ -246,6 +248,41 @@ int bgs_cloud_upload_cov3d_f32(bgs_ctx* ctx, uint32_t n, const float* position_v
                                bgs_cloud** out);
 void bgs_cloud_free(bgs_ctx* ctx, bgs_cloud* cloud);
 uint32_t bgs_cloud_len(const bgs_cloud* cloud);
+
+/* ---- particle behaviours: move splats of a resident cloud on the device -------------- */
+/* ParticleBehavior (src/morph/particle.rs:349-358, #[repr(C)] Pod: 64 bytes; src/morph/particle.wgsl:14-19) */
+typedef struct bgs_particle_behavior {
+    uint32_t indicies[4]; /* [0] = splat index, read as int32: negative = inactive (particle.wgsl:46); [1..3] unused.
+                             The reference's spelling. */
+    float velocity[4];
+    float acceleration[4];
+    float jerk[4];
+} bgs_particle_behavior;
+/* One run of apply_particle_behaviors (src/morph/particle.wgsl:23-53) with globals.delta_time = delta_time, the compute
+ * pass the reference runs before the draw (run_particle_behaviors, src/morph/particle.rs): call it before the frame's
+ * bgs_render. behaviors_device_ptr: `count` bgs_particle_behavior records in CALLER-OWNED device memory, 16-byte aligned
+ * (bgs_device_alloc / bgs_upload / bgs_download serve hosts without a HIP runtime), as the reference binds a storage
+ * buffer of behaviours to the pass. For every record b in [0, count), with i = (int32)indicies[0] and n = bgs_cloud_len:
+ *   i < 0 or i >= n: the record is skipped entirely (no position write, velocity and acceleration untouched);
+ *   otherwise, on all four lanes (x, y, z AND w: the visibility moves too), in f32, every operation rounded once, in this order:
+ *     position[i]  += ((v*dt) + (((0.5*a)*dt)*dt)) + ((((c6*j)*dt)*dt)*dt)     c6 = (float)(1.0 / 6.0)
+ *     velocity     += (a*dt) + (((0.5*j)*dt)*dt)
+ *     acceleration += j*dt
+ *   with v, a, j the record's values before the call. jerk and indicies are never written.
+ * Exactly `count` records act (the reference dispatches whole 32 x 32 workgroups past its buffer's end), and an index >= n
+ * skips the record (the reference leaves that to WebGPU's robustness rules).
+ * PRECONDITION: the indices of the active records are distinct. Two records that name one splat race in the reference;
+ * here the result for that splat is then unspecified (the C++ and Python layers check it on the host before upload).
+ * Works on every cloud format (position_visibility is f32 in all of them). position_min / position_max of bgs_settings
+ * stay the caller's: no AABB is refreshed (the reference's TODO, src/gaussian/cloud.rs:43).
+ * ORDERING: the step is a pipeline barrier. Frames in flight are completed first (they — and a re-run of them — draw the
+ * positions they were enqueued with; they stay in the ring for bgs_pipeline_pop); every bgs_sort / bgs_render after the
+ * call sees the stepped cloud. The call only ENQUEUES the step and returns: the behaviours' memory must stay valid, and
+ * must not be written or read back, until a frame enqueued after the call has completed or bgs_synchronize has returned.
+ * BGS_EINVAL: ctx or cloud NULL, a NULL or misaligned pointer with count > 0, a delta_time that is not finite.
+ * count == 0: BGS_OK, nothing happens. */
+int bgs_cloud_apply_particle_behaviors(bgs_ctx* ctx, bgs_cloud* cloud, void* behaviors_device_ptr, uint32_t count,
+                                       float delta_time);
 
 /* ---- the hot path ----------------------------------------------------------------- */
 /* Depth sort for one view. Result is kept on the device (consumed by the next

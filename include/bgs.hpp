@@ -10,6 +10,7 @@
 //   PlanarGaussian3dHandle    (formats/planar_3d.rs)   bgs::PlanarGaussian3dHandle (device-resident cloud)
 //   SortEntry                 (src/sort/mod.rs:324)    bgs_sort_entry
 //   Camera3d + GaussianCamera (examples/headless.rs)   bgs::View::perspective / View::headless
+//   ParticleBehavior(s)       (src/morph/particle.rs)  bgs::ParticleBehavior, bgs::ParticleBehaviors (device-resident)
 //
 // Every failure of the C ABI becomes a bgs::Error carrying the status and bgs_last_error().
 #ifndef BGS_HPP
@@ -296,6 +297,7 @@ class PlanarGaussian3dHandle {
     }
     uint32_t size() const { return cloud_ ? bgs_cloud_len(cloud_) : 0; }
     const bgs_cloud* get() const { return cloud_; }
+    bgs_cloud* native() const { return cloud_; }   // for the calls that change the cloud (particle behaviours)
 
   private:
     friend class GaussianSplattingPlugin;
@@ -403,6 +405,9 @@ class GaussianSplattingPlugin {
         return p;
     }
     void device_free(void* p) { check(bgs_device_free(ctx_, p), "bgs_device_free"); }
+    void upload_bytes(void* device_ptr, const void* host_in, uint64_t bytes) {
+        check(bgs_upload(ctx_, device_ptr, host_in, bytes), "bgs_upload");
+    }
     void set_srgb8_target(void* device_ptr) { check(bgs_set_srgb8_target(ctx_, device_ptr), "bgs_set_srgb8_target"); }
     void set_profiling(int level) { check(bgs_set_profiling(ctx_, level), "bgs_set_profiling"); }
     void synchronize() { check(bgs_synchronize(ctx_), "bgs_synchronize"); }
@@ -456,6 +461,86 @@ class GaussianSplattingPlugin {
         if (rc != BGS_OK) throw Error(rc, std::string(what) + ": " + bgs_last_error(ctx_));
     }
     bgs_ctx* ctx_ = nullptr;
+};
+
+// ParticleBehavior (src/morph/particle.rs:349-358): layout-identical to bgs_particle_behavior.
+struct ParticleBehavior {
+    std::array<uint32_t, 4> indicies{};   // [0] = splat index, read as int32: negative = inactive (the reference's spelling)
+    std::array<float, 4> velocity{}, acceleration{}, jerk{};
+};
+static_assert(sizeof(ParticleBehavior) == 64 && sizeof(bgs_particle_behavior) == 64, "ParticleBehavior is 64 bytes");
+
+// The precondition of bgs_cloud_apply_particle_behaviors, checked on the host for a cloud of n splats: every active record
+// (index >= 0 as int32) names a splat of the cloud, and no two of them the same one (a data race on the device).
+inline void validate_particle_behaviors(const std::vector<ParticleBehavior>& records, uint32_t n) {
+    std::vector<uint32_t> active;
+    active.reserve(records.size());
+    for (const auto& r : records) {
+        if (static_cast<int32_t>(r.indicies[0]) < 0) continue;
+        if (r.indicies[0] >= n)
+            throw Error(BGS_EINVAL, "particle behaviour names splat " + std::to_string(r.indicies[0]) + ", the cloud has " + std::to_string(n));
+        active.push_back(r.indicies[0]);
+    }
+    std::sort(active.begin(), active.end());
+    if (std::adjacent_find(active.begin(), active.end()) != active.end())
+        throw Error(BGS_EINVAL, "two active particle behaviours name the same splat");
+}
+
+// Behaviours resident in device memory (the storage buffer the reference binds to its particle pass): owns the
+// allocation and the count. Move-only. The plugin must outlive it.
+class ParticleBehaviors {
+  public:
+    // validates `records` against the cloud they are for (validate_particle_behaviors), then uploads them
+    ParticleBehaviors(GaussianSplattingPlugin& plugin, const std::vector<ParticleBehavior>& records, const PlanarGaussian3dHandle& cloud)
+        : plugin_(&plugin), count_(static_cast<uint32_t>(records.size())) {
+        validate_particle_behaviors(records, cloud.size());
+        ptr_ = plugin.device_alloc(std::max<uint64_t>(records.size() * sizeof(ParticleBehavior), 64));
+        if (count_) {
+            try {
+                plugin.upload_bytes(ptr_, records.data(), records.size() * sizeof(ParticleBehavior));
+            } catch (...) {
+                plugin.device_free(ptr_);
+                throw;
+            }
+        }
+    }
+    ParticleBehaviors(ParticleBehaviors&& o) noexcept : plugin_(o.plugin_), ptr_(o.ptr_), count_(o.count_) { o.ptr_ = nullptr; }
+    ParticleBehaviors& operator=(ParticleBehaviors&& o) noexcept {
+        if (this != &o) {
+            reset();
+            plugin_ = o.plugin_; ptr_ = o.ptr_; count_ = o.count_;
+            o.ptr_ = nullptr;
+        }
+        return *this;
+    }
+    ParticleBehaviors(const ParticleBehaviors&) = delete;
+    ParticleBehaviors& operator=(const ParticleBehaviors&) = delete;
+    ~ParticleBehaviors() { reset(); }
+    void reset() {
+        if (ptr_) bgs_device_free(plugin_->native(), ptr_);   // (completes the frames in flight first)
+        ptr_ = nullptr;
+    }
+    uint32_t size() const { return count_; }
+    void* device_ptr() const { return ptr_; }
+
+    // One step on the resident cloud, before the frame's render (run_particle_behaviors runs before the prepass): the
+    // named splats move in the cloud, velocity and acceleration advance in this buffer. Enqueues and returns.
+    void apply(PlanarGaussian3dHandle& cloud, float delta_time) {
+        const int rc = bgs_cloud_apply_particle_behaviors(plugin_->native(), cloud.native(), ptr_, count_, delta_time);
+        if (rc != BGS_OK) throw Error(rc, std::string("bgs_cloud_apply_particle_behaviors: ") + bgs_last_error(plugin_->native()));
+    }
+    // the records as the steps so far left them (synchronises: completes the frames in flight)
+    std::vector<ParticleBehavior> download() {
+        std::vector<ParticleBehavior> out(count_);
+        plugin_->synchronize();
+        if (count_) plugin_->download(ptr_, out.data(), out.size() * sizeof(ParticleBehavior));
+        return out;
+    }
+
+  private:
+    GaussianSplattingPlugin* plugin_ = nullptr;
+    void* ptr_ = nullptr;
+    uint32_t count_ = 0;
 };
 
 }  // namespace bgs

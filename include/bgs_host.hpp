@@ -160,6 +160,22 @@ inline void sort_cameras(GaussianSplattingPlugin& plugin, const PlanarGaussian3d
     }
 }
 
+// random_particle_behaviors (src/morph/particle.rs:374-410) for splats 0 .. n-1: velocity ~ U(-1, 1), acceleration ~
+// U(-0.01, 0.01), jerk ~ U(-1e-4, 1e-4) on all four lanes, indicies = (i, 0, 0, 0). The reference draws from the thread
+// RNG; this is seeded (std::mt19937_64; the Python twin uses numpy's PCG64: the same statistics, not the same bits).
+inline std::vector<ParticleBehavior> random_particle_behaviors(size_t n, uint64_t seed) {
+    std::mt19937_64 rng(seed);
+    auto uni = [&](float lo, float hi) { return std::uniform_real_distribution<float>(lo, hi)(rng); };
+    std::vector<ParticleBehavior> out(n);
+    for (size_t i = 0; i < n; ++i) {
+        out[i].indicies = {static_cast<uint32_t>(i), 0u, 0u, 0u};
+        for (auto& v : out[i].velocity) v = uni(-1.0f, 1.0f);
+        for (auto& v : out[i].acceleration) v = uni(-0.01f, 0.01f);
+        for (auto& v : out[i].jerk) v = uni(-1e-4f, 1e-4f);
+    }
+    return out;
+}
+
 // (min, max) the reference hands to the shaders for a cloud: compute_aabb (src/gaussian/interface.rs:22-63,
 // position -/+ 0.1 per splat) -> Bevy Aabb {center, half_extents} (src/gaussian/cloud.rs:56-59) ->
 // aabb.min() / max() = center -/+ half_extents (src/render/mod.rs:1070-1071), all in f32.
