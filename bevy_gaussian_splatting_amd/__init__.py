@@ -40,6 +40,8 @@ from .particles import (
     step_reference,
 )
 from .plugin import (
+    DeviceEntriesChunk,
+    DeviceSortedEntries,
     GaussianSplattingPlugin,
     PlanarGaussian3dHandle,
     SortedEntries,
@@ -54,5 +56,6 @@ __all__ = [
     "RasterizeMode", "ShaderDefines", "SortMode", "compute_aabb",
     "parse_ply_3d", "write_ply_3d", "decode_gcloud", "encode_gcloud", "read_gcloud", "write_gcloud", "SortConfig", "SortTrigger", "update_sort_trigger",
     "GaussianSplattingPlugin", "PlanarGaussian3dHandle", "SortedEntries", "SORT_ENTRY_DTYPE",
+    "DeviceEntriesChunk", "DeviceSortedEntries",
     "PARTICLE_BEHAVIOR_DTYPE", "ParticleBehaviors", "ParticleBehaviorsHandle", "random_particle_behaviors", "step_reference",
 ]

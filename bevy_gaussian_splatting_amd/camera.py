@@ -33,9 +33,10 @@ class BgsView(ctypes.Structure):
         ("previous_clip_from_world", ctypes.c_float * 16),
         ("delta_time", ctypes.c_float),
         ("sample_count", ctypes.c_uint32),
-        ("reserved", ctypes.c_uint32 * 2),
+        ("entry_count", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32 * 1),
         ("depth_device_ptr", ctypes.c_uint64),
-        ("reserved_ptr", ctypes.c_uint64),
+        ("entries_device_ptr", ctypes.c_uint64),
     ]
 
 
@@ -109,6 +110,10 @@ class View:
     # against with GreaterEqual (src/render/mod.rs:959-974), or 0: no scene depth. GaussianSplattingPlugin.upload_depth
     # puts a host array there.
     depth_device_ptr: int = 0
+    # The camera's chunk of sorted entries kept on the device (`bgs_view.entries_device_ptr` / `entry_count`): anything with
+    # `ptr` and `count` — a `DeviceEntriesChunk` from `DeviceSortedEntries.chunk(camera_index)` — or None. `sort` writes its
+    # result there as well, `render` draws the chunk as it is instead of sorting (include/bgs.h).
+    entries: Optional[object] = None
 
     @property
     def width(self) -> int:
@@ -168,4 +173,7 @@ class View:
         v.delta_time = float(self.delta_time)
         v.sample_count = int(self.msaa_samples)
         v.depth_device_ptr = int(self.depth_device_ptr)
+        if self.entries is not None:
+            v.entries_device_ptr = int(self.entries.ptr)
+            v.entry_count = int(self.entries.count)
         return v

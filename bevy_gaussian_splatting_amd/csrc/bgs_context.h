@@ -123,7 +123,9 @@ struct FramePlan {
     uint32_t n = 0, places = 0, rec_bytes = 0, cloud_format = 0;
     // depth sort: bucket or digit passes; 256 * bucket_sub buckets (the sub of the splitter slot's table); the quantile
     // table the frame LEAVES has 256 * split_sub_out - 1 keys; the slot (-1: none, or a guessed table) and its epoch
-    bool bucket = false, wide = false;
+    // kept: no keys and no depth sort at all — the frame draws the caller's entries (bgs_view.entries_device_ptr) through
+    // the compaction of entries_kernels.hip (places = 0, never bucket)
+    bool bucket = false, wide = false, kept = false;
     uint32_t bucket_sub = 1, split_sub_out = 1;
     int split_slot = -1;
     uint64_t split_epoch = 0;
@@ -200,7 +202,7 @@ struct Lane {
     PinnedBuffer<Control> h_ctl;  // filled by a copy enqueued with the frame, or by the rasteriser
     Control* h_ctl_dev = nullptr;  // the same memory as the device sees it
     hipEvent_t ev_ring[EV_RING][EV_COUNT] = {};
-    uint8_t ev_kind[EV_RING] = {};  // 0 unused, 1 sort-only frame, 2 render/scan, 3 render/sort-binning
+    uint8_t ev_kind[EV_RING] = {};  // 0 unused, 1 sort-only frame, 2 render/scan, 3 render/sort-binning, 4 / 5: 2 / 3 drawn in a kept order
     uint32_t ev_head = 0;
     uint32_t frames_timed = 0;  // timed frames since the last stats read-back
 

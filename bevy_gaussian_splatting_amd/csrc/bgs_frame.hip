@@ -225,6 +225,16 @@ int validate(bgs_ctx* ctx, const bgs_cloud* cloud, const bgs_view* view, const b
     if (s->draw_mode > BGS_DRAW_HIGHLIGHT_SELECTED) return fail(ctx, BGS_EINVAL, "unknown draw_mode");
     if (s->rasterize_mode == BGS_RASTERIZE_CLASSIFICATION && s->num_classes == 0)
         return fail(ctx, BGS_EINVAL, "num_classes must be >= 1");
+    // the camera's chunk of sorted entries on the device: bgs_sort's second output, bgs_render's draw order
+    if (view->entries_device_ptr) {
+        if (view->entries_device_ptr % sizeof(bgs_sort_entry) != 0u)
+            return fail(ctx, BGS_EINVAL, "bgs_view.entries_device_ptr must be aligned to 8 bytes (one bgs_sort_entry)");
+        if (view->entry_count != cloud->ptrs.n)
+            return fail(ctx, BGS_EINVAL, "bgs_view.entry_count must equal bgs_cloud_len(cloud) when entries_device_ptr is set; got " +
+                                             std::to_string(view->entry_count) + " for a cloud of " + std::to_string(cloud->ptrs.n));
+    } else if (view->entry_count != 0u) {
+        return fail(ctx, BGS_EINVAL, "bgs_view.entry_count is " + std::to_string(view->entry_count) + " but bgs_view.entries_device_ptr is 0");
+    }
     if (render && cloud->ptrs.format == CLOUD_COV3D &&
         (s->gaussian_mode != BGS_GAUSSIAN_3D || s->rasterize_mode == BGS_RASTERIZE_NORMAL))
         return fail(ctx, BGS_EINVAL, "a precomputed-covariance cloud has no rotation / scale: 3D gaussian mode only, no Normal raster mode");
@@ -519,7 +529,7 @@ void fill_stats(const bgs_ctx* ctx, Lane& L, const FrameTotals& t) {
     stt.splat_count = p.n;
     stt.visible_count = render ? h.visible_count : h.draw_count;
     stt.draw_count = h.draw_count;
-    stt.sort_path = p.bucket ? 1u : 0u;
+    stt.sort_path = p.kept ? 2u : (p.bucket ? 1u : 0u);
     stt.list_capacity = (render && scan) ? L.pending_coarse_cap : 0u;
     stt.instance_count = render ? t.instances : 0;
     stt.instance_capacity = L.inst[0].capacity;
@@ -539,6 +549,8 @@ void fill_stats(const bgs_ctx* ctx, Lane& L, const FrameTotals& t) {
     // (keygen reads N positions and writes the D drawable pairs; the N - D culled pairs only in frames that
     // have a reader for them)
     uint64_t bytes = N * 16 + D * 8 + (p.culled_tail ? (N - D) * 8 : 0) + (p.bucket ? D * 24 : k * D * 16);
+    // a kept order: no positions read, no keys sorted — the N entries of the caller's chunk read, the D drawable ones written
+    if (p.kept) bytes = N * 8 + D * 8 + (p.culled_tail ? (N - D) * 8 : 0);
     if (render) {
         const uint64_t B = p.cloud_format == CLOUD_F16 ? 128 : 240, R = p.rec_bytes, V = h.visible_count, I = t.instances;
         const uint64_t P = (uint64_t)(uint32_t)p.fp.width * (uint32_t)p.fp.height;
@@ -549,7 +561,7 @@ void fill_stats(const bgs_ctx* ctx, Lane& L, const FrameTotals& t) {
     }
     stt.algorithmic_bytes = bytes;
     L.has_result = true;
-    L.result_kind = (uint8_t)(!render ? 1 : (scan ? 2 : 3));
+    L.result_kind = (uint8_t)(!render ? 1 : (scan ? 2 : 3) + (p.kept ? 2 : 0));
 }
 
 // Complete the frame pending on a lane: wait for it, check the watchdog word of the Control copy that
@@ -588,12 +600,19 @@ int finish_lane(bgs_ctx* ctx, Lane& L) {
         // after a render only the drawable prefix of the list is materialised (the culled tail stays
         // in its side buffer); bgs_sort appends it so that callers get the reference's full list
         L.last_sorted_n = p.render ? h.draw_count : p.n;
-        if (!p.render && h.draw_count < p.n) {
+        const bool append_tail = !p.render && h.draw_count < p.n;
+        // bgs_sort with the camera's chunk named (bgs_view.entries_device_ptr): the whole list goes there too, on the stream
+        const bool to_chunk = !p.render && L.in.view.entries_device_ptr && p.n > 0;
+        if (append_tail) {
             // bgs_sort contract: one contiguous list, culled entries last (ascending index)
             HIP_TRY(ctx, hipMemcpyAsync(const_cast<uint2*>(L.last_sorted) + h.draw_count, L.culled.ptr,
                                         (size_t)(p.n - h.draw_count) * sizeof(uint2), hipMemcpyDeviceToDevice, L.stream));
-            HIP_TRY(ctx, hipStreamSynchronize(L.stream));
         }
+        if (to_chunk)
+            HIP_TRY(ctx, hipMemcpyAsync(reinterpret_cast<void*>((uintptr_t)L.in.view.entries_device_ptr), L.last_sorted,
+                                        (size_t)p.n * sizeof(uint2), hipMemcpyDeviceToDevice, L.stream));
+        // (the chunk is complete when bgs_sort returns: frames of any lane may read it next)
+        if (append_tail || to_chunk) HIP_TRY(ctx, hipStreamSynchronize(L.stream));
         fill_stats(ctx, L, t);
     }
     return BGS_OK;
@@ -622,7 +641,7 @@ int collect_stats(bgs_ctx* ctx) {
     bgs_stats& stt = ctx->stats;
     if (ctx->profiling >= 1) {
         const uint8_t kind = R.result_kind;
-        const bool render = kind != 1, scan = kind == 2;
+        const bool render = kind != 1, scan = kind == 2 || kind == 4, kept = kind >= 4;
         const int last = render ? 6 : 2;
         uint32_t used = 0;
         float acc[BGS_STAGE_COUNT] = {0, 0, 0, 0, 0, 0}, acc_total = 0.0f;
@@ -634,8 +653,9 @@ int collect_stats(bgs_ctx* ctx) {
                 hipEvent_t* const ev = L.ev_ring[slot];
                 auto ms = [&](int a, int b) { float t = 0; (void)hipEventElapsedTime(&t, ev[a], ev[b]); return t; };
                 if (ctx->profiling >= 2) {
-                    acc[BGS_STAGE_KEYGEN] += ms(0, 1);
-                    acc[BGS_STAGE_DEPTH_SORT] += ms(1, 2);
+                    // (a kept order: the compaction is the whole front end, there is no depth sort)
+                    acc[BGS_STAGE_KEYGEN] += kept ? ms(0, 2) : ms(0, 1);
+                    acc[BGS_STAGE_DEPTH_SORT] += kept ? 0.0f : ms(1, 2);
                     if (render && scan) {
                         acc[BGS_STAGE_PROJECT] += ms(2, 3);
                         acc[BGS_STAGE_RASTER] += ms(3, 6);
@@ -671,8 +691,12 @@ FramePlan plan_frame(const bgs_ctx& ctx, const Lane& L, const FrameInputs& in) {
     fp.debug = flags;
     fp.srgb8_target = (uint64_t)(uintptr_t)in.srgb8_target;
     const uint32_t n = p.n = fp.n;
-    p.places = depth_places(s);
     p.render = in.render;
+    // A kept order (bgs_view.entries_device_ptr on a render): the caller's entries are the draw order. No keys, no digit
+    // places, no bucket sort, no splitter table read or left (learn_splitters wants 4 places): sort_mode and
+    // radix_depth_bits do not reach such a frame.
+    p.kept = in.render && in.view.entries_device_ptr != 0u && fp.n > 0u;
+    p.places = p.kept ? 0u : depth_places(s);
     p.scan = ctx.binning == BINNING_SCAN;
     p.surfel = in.render && fp.gaussian_mode == 0u && fp.aabb != 0u;
     p.rec_bytes = p.surfel ? sizeof(RecordSurfel) : sizeof(Record);
@@ -681,6 +705,7 @@ FramePlan plan_frame(const bgs_ctx& ctx, const Lane& L, const FrameInputs& in) {
     // readers: bgs_sort's full list and RasterizeMode::Depth (sorted[N-1] of the full list, gaussian.wgsl:331-340).
     // Every other rendered frame skips the writes; bgs_sorted_entries_device_ptr after a render has always meant the
     // drawable prefix only.
+    // (a kept order: the skipped entries, in list order, for the same reader)
     p.culled_tail = !in.render || s->rasterize_mode == BGS_RASTERIZE_DEPTH;
 
     // Depth-sort path. The bucket sort needs 32-bit keys (shorter keys are mostly ties, which it ranks
@@ -713,6 +738,7 @@ FramePlan plan_frame(const bgs_ctx& ctx, const Lane& L, const FrameInputs& in) {
     }
     if (p.bucket && slot >= 0) { p.split_slot = slot; p.split_epoch = ctx.split_slots[slot].epoch; }
     fp.sort_path = p.bucket ? 1u : 0u;
+    if (p.kept) { fp.sort_mode = SORT_NONE; fp.key_shift = 0u; }   // (what the frame is to its kernels: a list drawn in entry order)
 
     // Supertile edge (in tiles): four levels (supertile_edges, frame_params.h). Every tile scans its supertile's whole
     // list, so small splats want short lists (level 0: scene-like frame 91.7 -> 87.9 us against level 1); a splat that
@@ -792,8 +818,9 @@ FramePlan plan_frame(const bgs_ctx& ctx, const Lane& L, const FrameInputs& in) {
     // Measured: 7 launches cost 19 us of host time (30 us with stage events), a replay 10 us; on the
     // GPU a replayed frame is ~5 % SLOWER than the same launches issued directly (178 vs 171 us per
     // frame back to back on one stream), so it is for hosts that cannot spare the CPU time.
+    // A kept-order frame is launched directly, as timed frames are: the captured graph's one updatable node is keygen's.
     p.graph_ok = in.allow_graph && ctx.use_graphs && p.raster_cleans && p.bucket_sub <= BUCKET_SUB_KERNARG &&
-                 !(flags & BGS_DEBUG_NO_GRAPHS) && !ctx.tile_trace;
+                 !(flags & BGS_DEBUG_NO_GRAPHS) && !ctx.tile_trace && !p.kept;
     return p;
 }
 
@@ -942,7 +969,8 @@ int enqueue_frame(bgs_ctx* ctx, Lane& L, const FrameInputs& in) {
         kg.split.wide = p.wide ? 1u : 0u;
     }
     kg.wide = p.wide_bin;
-    const bool have_keygen = kg.prepare(ctx->num_cus * 4);
+    const bool have_keygen = !p.kept && kg.prepare(ctx->num_cus * 4);
+    const uint2* const kept_entries = reinterpret_cast<const uint2*>((uintptr_t)in.view.entries_device_ptr);
     FrameCleanup cl{};
     if (p.raster_cleans) {
         cl.part_status = part_status;
@@ -973,7 +1001,7 @@ int enqueue_frame(bgs_ctx* ctx, Lane& L, const FrameInputs& in) {
     const int last_mark = render ? 6 : 2;
     if (prof) {  // untimed frames do not consume a ring slot
         L.ev_head = (L.ev_head + 1) % EV_RING;
-        L.ev_kind[L.ev_head] = (uint8_t)(!render ? 1 : (scan ? 2 : 3));
+        L.ev_kind[L.ev_head] = (uint8_t)(!render ? 1 : (scan ? 2 : 3) + (p.kept ? 2 : 0));
         L.frames_timed += 1;
     }
     hipEvent_t* const ev = L.ev_ring[L.ev_head];
@@ -992,6 +1020,11 @@ int enqueue_frame(bgs_ctx* ctx, Lane& L, const FrameInputs& in) {
                 if (ce != hipSuccess) return ce;
             }
             hipError_t e = kg.launch(st);
+            if (e != hipSuccess) return e;
+        }
+        if (p.kept) {   // in keygen's place, and leaving what keygen leaves (entries_kernels.hip)
+            const hipError_t e = launch_entries_compact(st, fp, kept_entries, draw_list, kg.culled, ctl, part_status, kg.ticket_slot,
+                                                        L.d_fp.ptr, kg.zero_word);
             if (e != hipSuccess) return e;
         }
         mark(1);
@@ -1042,7 +1075,7 @@ int enqueue_frame(bgs_ctx* ctx, Lane& L, const FrameInputs& in) {
     } else {
         if (need_memset) HIP_TRY(ctx, hipMemsetAsync(scratch, 0, lay.bytes, st));
         // no keygen (empty cloud): the kernels behind it still read the frame's parameters
-        if (!have_keygen) HIP_TRY(ctx, hipMemcpyAsync(L.d_fp.ptr, &fp, sizeof fp, hipMemcpyHostToDevice, st));
+        if (!have_keygen && !p.kept) HIP_TRY(ctx, hipMemcpyAsync(L.d_fp.ptr, &fp, sizeof fp, hipMemcpyHostToDevice, st));
         HIP_TRY(ctx, issue());
     }
     // the Control block travels back with the frame; it is looked at when the lane is completed.

@@ -112,6 +112,13 @@ struct KeygenLaunch {
 #endif
 inline uint32_t keygen_tile_splats(uint32_t n) { return n >= (1u << BGS_KEYGEN_HUGE_LOG2) ? 8192u : (n >= (1u << 19) ? 4096u : 2048u); }
 
+// The front end of a kept-order frame (bgs_view.entries_device_ptr; entries_kernels.hip) in keygen's place: the caller's
+// fp.n sorted entries -> draw_list, order kept, without the entries that cannot be drawn (key all-ones, index >= n);
+// ctl->draw_count = how many stayed. tail (or null): the skipped entries, in order (RasterizeMode::Depth reads them).
+// part_status, ticket_slot, fp_out, zero_word: as for keygen. Nothing is launched for fp.n == 0.
+hipError_t launch_entries_compact(hipStream_t stream, const FrameParams& fp, const uint2* entries, uint2* draw_list, uint2* tail,
+                                  Control* ctl, uint32_t* part_status, uint32_t ticket_slot, FrameParams* fp_out, uint32_t* zero_word);
+
 // Standalone digit histograms of existing pairs (used by bgs_radix_sort_pairs).
 void launch_histogram(hipStream_t stream, const uint2* pairs, uint32_t n, uint32_t* hist /*[4][256]*/,
                       uint32_t passes);

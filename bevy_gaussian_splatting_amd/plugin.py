@@ -66,6 +66,85 @@ class SortedEntries:
 
 
 @dataclass
+class DeviceEntriesChunk:
+    """One camera's chunk of a `DeviceSortedEntries`: `count` (key, index) records at the device address `ptr`
+    (`bgs_view.entries_device_ptr` / `entry_count`)."""
+
+    ptr: int
+    count: int
+
+
+class DeviceSortedEntries:
+    """`SortedEntries` resident on the device: `camera_count` chunks of `gaussians` = cloud.len() entries each in ONE
+    `bgs_device_alloc` block, camera `c` at byte offset `c * 8 * gaussians` — the dynamic offset the reference's draw binds
+    (src/render/mod.rs:1548-1554). `sort(..., into=chunk)` fills a chunk, `render(..., entries=chunk)` draws it as it is.
+    New chunks hold the asset's initial content, key 1 / index i (src/sort/mod.rs:347-354). The caller orders a sort into
+    a chunk against frames in flight that read it (`bgs_sort` completes the frames in flight first)."""
+
+    ENTRY_BYTES = 8
+
+    def __init__(self, plugin: "GaussianSplattingPlugin", camera_count: int, gaussians: int):
+        if camera_count < 1 or gaussians < 0:
+            raise ValueError("camera_count must be >= 1 and gaussians >= 0")
+        self._plugin = plugin
+        self.camera_count = int(camera_count)
+        self.gaussians = int(gaussians)
+        self.ptr = plugin.device_alloc(max(self.nbytes, self.ENTRY_BYTES))
+        if self.gaussians:
+            init = np.empty(self.camera_count * self.gaussians, dtype=SORT_ENTRY_DTYPE)
+            init["key"] = 1
+            init["index"] = np.tile(np.arange(self.gaussians, dtype=np.uint32), self.camera_count)
+            plugin.upload_bytes(self.ptr, init)
+
+    @staticmethod
+    def chunk_offset(camera_index: int, gaussians: int) -> int:
+        """Byte offset of camera `camera_index`'s chunk: `camera_index * 8 * gaussians` (always a multiple of 8)."""
+        return int(camera_index) * DeviceSortedEntries.ENTRY_BYTES * int(gaussians)
+
+    @property
+    def nbytes(self) -> int:
+        return self.chunk_offset(self.camera_count, self.gaussians)
+
+    def chunk(self, camera_index: int) -> DeviceEntriesChunk:
+        if self.ptr is None:
+            raise ValueError("the entries have been freed")
+        if camera_index < 0 or camera_index >= self.camera_count:
+            raise IndexError("camera chunk out of range")  # `.nth(camera_index).unwrap()` panics
+        return DeviceEntriesChunk(self.ptr + self.chunk_offset(camera_index, self.gaussians), self.gaussians)
+
+    def upload(self, camera_index: int, entries: np.ndarray) -> None:
+        """Overwrite a chunk with host entries (hand-built orders; blocking)."""
+        e = np.ascontiguousarray(entries, dtype=SORT_ENTRY_DTYPE)
+        if e.shape != (self.gaussians,):
+            raise ValueError("a chunk holds exactly cloud.len() entries")
+        if e.nbytes:
+            self._plugin.upload_bytes(self.chunk(camera_index).ptr, e)
+
+    def download(self, camera_index: int) -> np.ndarray:
+        """A chunk's entries (completes the frames in flight first; blocking)."""
+        out = np.empty(self.gaussians, dtype=SORT_ENTRY_DTYPE)
+        self._plugin.synchronize()
+        if out.nbytes:
+            self._plugin.download(self.chunk(camera_index).ptr, out)
+        return out
+
+    def free(self) -> None:
+        if self.ptr is not None and self._plugin._ctx is not None:
+            self._plugin.device_free(self.ptr)   # (completes the frames in flight first)
+        self.ptr = None
+
+
+def _with_entries(v, chunk):
+    """A copy of the native view `v` that names `chunk` (the caller's struct — a PreparedView's — stays as it is)."""
+    if chunk is None:
+        return v
+    v = type(v).from_buffer_copy(v)
+    v.entries_device_ptr = int(chunk.ptr)
+    v.entry_count = int(chunk.count)
+    return v
+
+
+@dataclass
 class PreparedView:
     """C-struct images of one (View, CloudSettings) pair (GaussianSplattingPlugin.prepare)."""
 
@@ -206,10 +285,11 @@ class GaussianSplattingPlugin:
 
     # -- hot path --------------------------------------------------------------------
     def sort(self, handle: PlanarGaussian3dHandle, view: View, settings: CloudSettings,
-             download: bool = True) -> Optional[np.ndarray]:
+             download: bool = True, into: Optional[DeviceEntriesChunk] = None) -> Optional[np.ndarray]:
         """Depth sort for one camera. Returns the (key, index) entries of this camera's
-        chunk in draw order (structured array), or None if `download` is False."""
-        v, s = view.to_native(), settings.to_native()
+        chunk in draw order (structured array), or None if `download` is False. `into` (default: `view.entries`): a chunk
+        of a `DeviceSortedEntries` that receives the same entries on the device."""
+        v, s = _with_entries(view.to_native(), into), settings.to_native()
         if download:
             out = np.empty(handle.n, dtype=SORT_ENTRY_DTYPE)
             ptr = out.ctypes.data_as(ctypes.POINTER(_native.BgsSortEntry))
@@ -250,14 +330,16 @@ class GaussianSplattingPlugin:
         return PreparedView(view.to_native(), settings.to_native(), view.width, view.height)
 
     def render(self, handle: PlanarGaussian3dHandle, view, settings: Optional[CloudSettings] = None,
-               download: bool = True) -> Optional[np.ndarray]:
+               download: bool = True, entries: Optional[DeviceEntriesChunk] = None) -> Optional[np.ndarray]:
         """Sort + project + bin + rasterize one view. Returns [H, W, 4] float32
         (premultiplied linear RGBA, unclamped, row 0 = top) or None if not downloaded.
-        `view` is a View (with `settings`) or a PreparedView from `prepare()`."""
+        `view` is a View (with `settings`) or a PreparedView from `prepare()`. `entries` (default: `view.entries`): draw
+        this chunk of a `DeviceSortedEntries` as it is instead of sorting — the reference's frames between two sorts."""
         if isinstance(view, PreparedView):
             v, s = view.view, view.settings
         else:
             v, s = view.to_native(), settings.to_native()
+        v = _with_entries(v, entries)
         if download:
             out = np.empty((view.height, view.width, 4), dtype=np.float32)
             ptr = _fptr(out)
@@ -265,6 +347,20 @@ class GaussianSplattingPlugin:
             out, ptr = None, None
         self._check(self._lib.bgs_render(self._ctx, handle._ptr, ctypes.byref(v), ctypes.byref(s), ptr))
         return out
+
+    def device_sorted_entries(self, camera_count: int, handle: PlanarGaussian3dHandle) -> DeviceSortedEntries:
+        """`SortedEntries` for `camera_count` cameras of this cloud, kept on the device."""
+        return DeviceSortedEntries(self, camera_count, handle.n)
+
+    def render_with_trigger(self, handle: PlanarGaussian3dHandle, view: View, settings: CloudSettings, trigger,
+                            chunk: DeviceEntriesChunk, download: bool = True) -> Optional[np.ndarray]:
+        """One frame the way the reference draws it: sort into the camera's chunk iff `trigger.needs_sort`
+        (`sort_policy.update_sort_trigger` raised it; it is cleared, as the sort systems do), then draw from the chunk —
+        freshly sorted or as the last sort left it."""
+        if trigger.needs_sort:
+            self.sort(handle, view, settings, download=False, into=chunk)
+            trigger.needs_sort = False
+        return self.render(handle, view, settings, download=download, entries=chunk)
 
     def radix_sort_pairs(self, keys: np.ndarray, passes: int = 4) -> np.ndarray:
         """Run the device Onesweep kernel on arbitrary (key, index=i) pairs (test hook)."""
@@ -549,7 +645,7 @@ class GaussianSplattingPlugin:
             "tile_passes": int(st.tile_passes),
             "algorithmic_bytes": int(st.algorithmic_bytes),
             "regrow_count": int(st.regrow_count),
-            "sort_path": "bucket" if st.sort_path else "onesweep",
+            "sort_path": ("onesweep", "bucket", "kept")[int(st.sort_path)],
             "list_capacity": int(st.list_capacity),
             "binning": "sort" if st.binning_mode else "scan",
             "frames_averaged": int(st.frames_averaged),

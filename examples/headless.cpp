@@ -14,6 +14,9 @@
 // splats 0 .. N-1 (seeded with --gaussian-seed) and applies one step of --particle-dt seconds (default 1/60) before each
 // of the `frames` frames; --dump-particle-behaviors <file> writes the records as generated (64 bytes each), for the
 // parity test.
+// --sort-period-frames K (NOT a flag of the reference, whose SortConfig counts milliseconds; default 0 = sort every frame):
+// keep the sorted entries on the device, sort into them on frames 0, K, 2K, ... and draw every frame — the ones in between
+// too, and the --dump-f32 frame — from the entries as the last sort left them, as the reference does between two sorts.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -104,7 +107,7 @@ bgs::PlanarGaussian3d read_planes(const std::string& path) {
 int main(int argc, char** argv) {
     uint32_t count = 10000, width = 1920, height = 1080, frames = 40, depth = 6;
     uint32_t msaa_samples = 0;   // 0 = not given: the view keeps Bevy's default Msaa (4 samples), as examples/headless.rs does
-    uint32_t particle_count = 0;
+    uint32_t particle_count = 0, sort_period_frames = 0;
     float particle_dt = 1.0f / 60.0f;
     uint64_t seed = 0;
     std::string out_dir = "headless_output", cloud_path, dump_path, ply_path, particle_dump_path;
@@ -160,6 +163,15 @@ int main(int argc, char** argv) {
         else if (a == "--particle-count") particle_count = (uint32_t)std::stoul(next());
         else if (a == "--particle-dt") particle_dt = std::stof(next());
         else if (a == "--dump-particle-behaviors") particle_dump_path = next();
+        else if (a == "--sort-period-frames") sort_period_frames = (uint32_t)std::stoul(next());
+        else if (a == "--help" || a == "-h") {
+            std::printf("headless: flags of the reference's viewer (--gaussian-count, --gaussian-seed, --gaussian-mode, --rasterization-mode,\n"
+                        "--radix-sort-depth-bits, --msaa-samples, --width, --height, --input-cloud, --particle-count) plus this build's\n"
+                        "--frames, --depth, --output-dir, --cloud, --dump-f32, --f16, --trained-like, --particle-dt, --dump-particle-behaviors and\n"
+                        "--sort-period-frames K  (not a reference flag) sort on frames 0, K, 2K, ... only; the other frames draw the\n"
+                        "                        entries the last sort left on the device\n");
+            return 0;
+        }
         else { std::fprintf(stderr, "unknown flag %s\n", a.c_str()); return 2; }
     }
     try {
@@ -195,9 +207,16 @@ int main(int argc, char** argv) {
         for (uint32_t f = 0; f < 8; ++f) plugin.render(handle, view, native);  // allocations, hints
         plugin.synchronize();
         const auto t0 = std::chrono::steady_clock::now();
+        std::optional<bgs::DeviceSortedEntries> kept;
+        if (sort_period_frames) kept.emplace(plugin, 1, handle.size());
         for (uint32_t f = 0; f < frames; ++f) {
             if (particles) particles->apply(handle, particle_dt);   // run_particle_behaviors runs before the frame's passes
-            plugin.render(handle, view, native);
+            if (kept) {
+                if (f % sort_period_frames == 0) plugin.sort_into(handle, view, native, kept->chunk(0));
+                plugin.render_from(handle, view, native, kept->chunk(0));
+            } else {
+                plugin.render(handle, view, native);
+            }
         }
         plugin.synchronize();
         const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -207,7 +226,8 @@ int main(int argc, char** argv) {
         if (!dump_path.empty()) {
             plugin.set_async(false);
             std::vector<float> rgba;
-            plugin.render(handle, view, settings, &rgba);
+            if (kept) plugin.render_from(handle, view, native, kept->chunk(0), &rgba);
+            else plugin.render(handle, view, settings, &rgba);
             std::ofstream f(dump_path, std::ios::binary);
             f.write((const char*)rgba.data(), (std::streamsize)(rgba.size() * sizeof(float)));
         }

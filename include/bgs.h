@@ -46,7 +46,10 @@ extern "C" {
 #define BGS_VERSION_MINOR 4 /* 0.4: bgs_abi_check, bgs_comm_* (the multi-GPU frame gather), sample_count 0 = default; struct layouts as 0.3
                                (0.3: bgs_view gained sample_count + depth_device_ptr, 16 bytes longer; bgs_stats 16 bytes longer than 0.2's).
                                Still 0.4 with the particle behaviours: purely additive (one function, one POD typedef; bgs_view,
-                               bgs_settings and bgs_stats as they were), so a 0.4 binding keeps working unchanged */
+                               bgs_settings and bgs_stats as they were), so a 0.4 binding keeps working unchanged.
+                               Still 0.4 with the kept sort order: two RESERVED fields of bgs_view got names (entries_device_ptr,
+                               entry_count; size and offsets as they were); zero in both — what a 0.4 binding passes and what
+                               bgs_view_perspective sets — is the behaviour of before, bit for bit */
 
 typedef enum bgs_status {
     BGS_OK = 0,
@@ -85,7 +88,8 @@ typedef struct bgs_view {
      * the image handed back is the resolved one (mean of the samples). 0 (a zero-initialised bgs_view) means "not set"
      * and renders with Msaa::default() = 4; anything else is BGS_EINVAL. bgs_view_perspective sets 4. */
     uint32_t sample_count;
-    uint32_t reserved[2];
+    uint32_t entry_count;      /* records behind entries_device_ptr: bgs_cloud_len(cloud) when that is set, else 0 */
+    uint32_t reserved[1];
     /* The view's depth attachment the draw is tested against (src/render/mod.rs:959-974: Depth32Float,
      * CompareFunction::GreaterEqual — reverse-Z —, depth_write_enabled false): a DEVICE pointer to
      * viewport.w * viewport.h * sample_count floats laid out [y][x][sample] (sample order: the standard pattern's) (what Bevy's opaque passes left), or
@@ -93,7 +97,38 @@ typedef struct bgs_view {
      * splat's constant NDC z (src/render/gaussian.wgsl:429-433). The memory must stay valid and unchanged until
      * the frame has completed (bgs_device_alloc / bgs_upload below serve hosts without a HIP runtime). */
     uint64_t depth_device_ptr;
-    uint64_t reserved_ptr;
+    /* The camera's chunk of `SortedEntries` KEPT ON THE DEVICE (src/sort/mod.rs:331-393; the draw binds it per camera,
+     * src/render/mod.rs:1548-1554): a DEVICE pointer to entry_count bgs_sort_entry records in CALLER-OWNED memory, 8-byte
+     * aligned (bgs_device_alloc / bgs_upload, or any device memory of the caller), or 0 = none: then bgs_sort and
+     * bgs_render behave as they always have. The reference sorts only when its SortTrigger says so (update_sort_trigger,
+     * src/sort/mod.rs:153-194) and draws every frame in between from the chunk as the last sort left it; with this field
+     * a host does the same: bgs_sort with the chunk when `needs_sort`, bgs_render with the chunk every frame.
+     *   entry_count must equal bgs_cloud_len(cloud) when the pointer is set, and be 0 when it is not.
+     *   bgs_sort, pointer set: OUTPUT. After the sort its n entries are also copied to the chunk (device to device, on the
+     *     stream, behind the sort), in the order contract of bgs_sort: Radix ascending key, ties by index, culled entries
+     *     last with key all-ones; Rayon / Std their order; None (1, i). host_out works as before. The chunk is complete
+     *     when the call returns.
+     *   bgs_render, pointer set: INPUT. The frame computes no keys and runs no depth sort: it draws entries[0 .. n) in that
+     *     order, entry 0 first (furthest back). Entries with key == 0xFFFFFFFF are skipped (vs_points,
+     *     src/render/gaussian.wgsl:191-195), and so are entries with index >= n (the reference leaves those to WebGPU's
+     *     robustness rules). Every other per-splat test stays in the vertex stage, at the CURRENT camera: the frustum,
+     *     DrawMode, the depth attachment. A splat named twice is drawn twice. settings.sort_mode and radix_depth_bits do
+     *     not influence such a frame. RasterizeMode::Depth normalises by entries 1 and n - 1 of the list read as [entries
+     *     that are drawn, in order] ++ [skipped entries, in order] — for a chunk bgs_sort wrote that IS the list —, an
+     *     index >= n among them read as n - 1.
+     *     Works with both binning modes, every cloud format, sample count, raster / draw mode, the depth attachment, the
+     *     packed outputs, particle steps, and asynchronous frames on every lane (no host round trip). Under
+     *     bgs_set_graphs(1) such a frame is launched directly, as timed frames are.
+     *     Stats: sort_path = 2, depth_passes = 0, stage_ms[BGS_STAGE_KEYGEN] = the compaction of the chunk into the draw
+     *     list, stage_ms[BGS_STAGE_DEPTH_SORT] = 0, draw_count = entries that pass the key / index test, visible_count
+     *     as in every rendered frame (drawn splats that pass the vertex stage's tests). bgs_sorted_entries_device_ptr
+     *     after it: the drawable prefix, as after any render.
+     *   The memory must stay valid and UNWRITTEN until the frame has completed (the rule of depth_device_ptr): a host
+     *   that sorts into a chunk while frames that read it are in flight orders the two itself (bgs_sort completes the
+     *   frames in flight before it runs).
+     *   BGS_EINVAL, naming the field: a misaligned pointer, entry_count != n with the pointer set, entry_count != 0
+     *   without it. */
+    uint64_t entries_device_ptr;
 } bgs_view;
 
 /* gaussian_mode: src/gaussian/settings.rs:17-22 */
@@ -173,7 +208,8 @@ typedef struct bgs_stats {
     uint32_t draw_count;         /* D: entries that go through the radix passes / reach the
                                     vertex stage (key != culled sentinel)               */
     uint32_t sort_path;          /* depth sort of the call: 0 = onesweep digit passes, 1 = bucket sort
-                                    (one launch; chosen per frame)        */
+                                    (one launch; chosen per frame), 2 = kept: none, the frame drew the
+                                    caller's entries (bgs_view.entries_device_ptr)        */
     uint64_t instance_count;     /* I: (tile, splat) instances emitted                 */
     uint64_t instance_capacity;  /* BGS_BINNING_SORT: tile instances the lane's buffers hold (0 until that mode ran) */
     uint32_t tiles_x, tiles_y;
@@ -219,7 +255,7 @@ void bgs_settings_default(bgs_settings* out);
 /* Convenience: build a bgs_view the way Bevy builds its View uniform for
  * `Camera3d::default()` (infinite reverse-Z right-handed perspective) from a camera
  * world transform. Pure host arithmetic in f32. clear_color is set to opaque black, sample_count to 4
- * (Msaa::default() = Sample4), depth_device_ptr to 0. */
+ * (Msaa::default() = Sample4), depth_device_ptr, entries_device_ptr and entry_count to 0. */
 void bgs_view_perspective(const float world_from_view[16], float fov_y_radians,
                           float near_plane, uint32_t width, uint32_t height,
                           bgs_view* out);
@@ -285,15 +321,15 @@ int bgs_cloud_apply_particle_behaviors(bgs_ctx* ctx, bgs_cloud* cloud, void* beh
                                        float delta_time);
 
 /* ---- the hot path ----------------------------------------------------------------- */
-/* Depth sort for one view. Result is kept on the device (consumed by the next
- * bgs_render with the same cloud/view/settings) and, if host_out != NULL, copied to
+/* Depth sort for one view. Result is kept on the device (until the next call; and, with
+ * view->entries_device_ptr set, copied to that caller-owned chunk, see bgs_view) and, if host_out != NULL, copied to
  * host_out[n]. Order contract for BGS_SORT_RADIX: ascending key, ties by ascending
  * splat index, culled splats (key all-ones) last  (src/sort/radix.wgsl:109-279). */
 int bgs_sort(bgs_ctx* ctx, const bgs_cloud* cloud, const bgs_view* view,
              const bgs_settings* settings, bgs_sort_entry* host_out);
 
-/* Sort (always re-done: the benchmark sorts every frame) + project + bin +
- * rasterize one view. Output: viewport.w x viewport.h RGBA f32, premultiplied, linear,
+/* Sort (re-done with every call unless view->entries_device_ptr hands the frame a kept order, see bgs_view; the
+ * benchmark sorts every frame) + project + bin + rasterize one view. Output: viewport.w x viewport.h RGBA f32, premultiplied, linear,
  * unclamped, row 0 = top. rgba_host_out may be NULL (result stays on the device). */
 int bgs_render(bgs_ctx* ctx, const bgs_cloud* cloud, const bgs_view* view,
                const bgs_settings* settings, float* rgba_host_out);

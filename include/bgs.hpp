@@ -270,6 +270,18 @@ struct View {
     void set_msaa_samples(uint32_t samples) { native.sample_count = samples; }
     // The view's depth attachment as device memory ([y][x][sample] floats, reverse-Z; src/render/mod.rs:959-974), 0 = none.
     void set_depth(const void* device_ptr) { native.depth_device_ptr = (uint64_t)(uintptr_t)device_ptr; }
+    // The camera's chunk of sorted entries kept on the device (bgs_view.entries_device_ptr / entry_count; `count` = the
+    // cloud's length): bgs_sort writes its result there too, bgs_render draws it as it is instead of sorting. nullptr = none.
+    void set_entries(const void* device_ptr, uint32_t count) {
+        native.entries_device_ptr = (uint64_t)(uintptr_t)device_ptr;
+        native.entry_count = device_ptr ? count : 0u;
+    }
+};
+
+// One camera's chunk of a DeviceSortedEntries: `count` bgs_sort_entry records in device memory.
+struct DeviceEntriesChunk {
+    void* ptr = nullptr;
+    uint32_t count = 0;
 };
 
 class GaussianSplattingPlugin;
@@ -352,6 +364,21 @@ class GaussianSplattingPlugin {
     void render(const PlanarGaussian3dHandle& h, const View& v, const bgs_settings& ns, std::vector<float>* rgba_out = nullptr) {
         if (rgba_out) rgba_out->resize(static_cast<size_t>(v.width) * v.height * 4);
         check(bgs_render(ctx_, h.get(), &v.native, &ns, rgba_out ? rgba_out->data() : nullptr), "bgs_render");
+    }
+    // The reference's two halves of a frame with the entries kept on the device (bgs_view.entries_device_ptr): sort the
+    // view INTO the camera's chunk (when its SortTrigger asks for it), draw the view FROM the chunk as it is (every frame).
+    void sort_into(const PlanarGaussian3dHandle& h, const View& v, const bgs_settings& ns, const DeviceEntriesChunk& chunk,
+                   std::vector<bgs_sort_entry>* entries_out = nullptr) {
+        View with = v;
+        with.set_entries(chunk.ptr, chunk.count);
+        if (entries_out) entries_out->resize(h.size());
+        check(bgs_sort(ctx_, h.get(), &with.native, &ns, entries_out ? entries_out->data() : nullptr), "bgs_sort");
+    }
+    void render_from(const PlanarGaussian3dHandle& h, const View& v, const bgs_settings& ns, const DeviceEntriesChunk& chunk,
+                     std::vector<float>* rgba_out = nullptr) {
+        View with = v;
+        with.set_entries(chunk.ptr, chunk.count);
+        render(h, with, ns, rgba_out);
     }
 
     // Frames in flight: lanes = buffer sets, multiplexed onto `streams` HIP streams.
@@ -461,6 +488,41 @@ class GaussianSplattingPlugin {
         if (rc != BGS_OK) throw Error(rc, std::string(what) + ": " + bgs_last_error(ctx_));
     }
     bgs_ctx* ctx_ = nullptr;
+};
+
+// SortedEntries resident on the device: camera_count chunks of `gaussians` = cloud.len() entries in one bgs_device_alloc
+// block, camera c at byte offset c * 8 * gaussians (the dynamic offset the reference's draw binds,
+// src/render/mod.rs:1548-1554), every chunk initialised to key 1 / identity order (src/sort/mod.rs:347-354). Move-only.
+class DeviceSortedEntries {
+  public:
+    DeviceSortedEntries(GaussianSplattingPlugin& plugin, size_t camera_count, uint32_t gaussians)
+        : plugin_(&plugin), camera_count_(camera_count), gaussians_(gaussians) {
+        if (camera_count == 0) throw Error(BGS_EINVAL, "DeviceSortedEntries needs at least one camera");
+        ptr_ = static_cast<uint8_t*>(plugin.device_alloc(std::max<uint64_t>(chunk_offset(camera_count, gaussians), 8u)));
+        std::vector<bgs_sort_entry> init(camera_count * (size_t)gaussians);
+        for (size_t i = 0; i < init.size(); ++i) init[i] = bgs_sort_entry{1u, (uint32_t)(i % gaussians)};
+        if (!init.empty()) plugin.upload_bytes(ptr_, init.data(), init.size() * sizeof(bgs_sort_entry));
+    }
+    DeviceSortedEntries(DeviceSortedEntries&& o) noexcept
+        : plugin_(o.plugin_), ptr_(o.ptr_), camera_count_(o.camera_count_), gaussians_(o.gaussians_) { o.ptr_ = nullptr; }
+    DeviceSortedEntries& operator=(DeviceSortedEntries&&) = delete;
+    DeviceSortedEntries(const DeviceSortedEntries&) = delete;
+    DeviceSortedEntries& operator=(const DeviceSortedEntries&) = delete;
+    ~DeviceSortedEntries() { if (ptr_) bgs_device_free(plugin_->native(), ptr_); }   // (completes the frames in flight first)
+    static uint64_t chunk_offset(size_t camera_index, uint32_t gaussians) { return (uint64_t)camera_index * 8u * gaussians; }
+    size_t camera_count() const { return camera_count_; }
+    uint32_t gaussians() const { return gaussians_; }
+    // throws where the reference's `.nth(camera_index).unwrap()` panics
+    DeviceEntriesChunk chunk(size_t camera_index) const {
+        if (camera_index >= camera_count_) throw Error(BGS_EINVAL, "camera chunk out of range");
+        return DeviceEntriesChunk{ptr_ + chunk_offset(camera_index, gaussians_), gaussians_};
+    }
+
+  private:
+    GaussianSplattingPlugin* plugin_;
+    uint8_t* ptr_ = nullptr;
+    size_t camera_count_;
+    uint32_t gaussians_;
 };
 
 // ParticleBehavior (src/morph/particle.rs:349-358): layout-identical to bgs_particle_behavior.

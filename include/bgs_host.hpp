@@ -160,6 +160,19 @@ inline void sort_cameras(GaussianSplattingPlugin& plugin, const PlanarGaussian3d
     }
 }
 
+// One frame the way the reference draws it: sort into the camera's chunk iff the trigger asks for it (update_sort_trigger
+// raised needs_sort; it is cleared, as the sort systems do), then draw from the chunk — freshly sorted or as the last sort
+// left it.
+inline void render_with_trigger(GaussianSplattingPlugin& plugin, const PlanarGaussian3dHandle& h, const View& v, const CloudSettings& s,
+                                SortTrigger& trigger, const DeviceEntriesChunk& chunk, std::vector<float>* rgba_out = nullptr) {
+    const bgs_settings ns = s.to_native();
+    if (trigger.needs_sort) {
+        plugin.sort_into(h, v, ns, chunk);
+        trigger.needs_sort = false;
+    }
+    plugin.render_from(h, v, ns, chunk, rgba_out);
+}
+
 // random_particle_behaviors (src/morph/particle.rs:374-410) for splats 0 .. n-1: velocity ~ U(-1, 1), acceleration ~
 // U(-0.01, 0.01), jerk ~ U(-1e-4, 1e-4) on all four lanes, indicies = (i, 0, 0, 0). The reference draws from the thread
 // RNG; this is seeded (std::mt19937_64; the Python twin uses numpy's PCG64: the same statistics, not the same bits).
