@@ -39,6 +39,14 @@ from .particles import (
     random_particle_behaviors,
     step_reference,
 )
+from .mesh_query import (
+    MeshQuery,
+    TriangleMesh,
+    crossings_reference,
+    cube_mesh,
+    icosphere_mesh,
+    mesh_from_points,
+)
 from .plugin import (
     DeviceEntriesChunk,
     DeviceSortedEntries,
@@ -58,4 +66,5 @@ __all__ = [
     "GaussianSplattingPlugin", "PlanarGaussian3dHandle", "SortedEntries", "SORT_ENTRY_DTYPE",
     "DeviceEntriesChunk", "DeviceSortedEntries",
     "PARTICLE_BEHAVIOR_DTYPE", "ParticleBehaviors", "ParticleBehaviorsHandle", "random_particle_behaviors", "step_reference",
+    "MeshQuery", "TriangleMesh", "crossings_reference", "cube_mesh", "icosphere_mesh", "mesh_from_points",
 ]

@@ -283,6 +283,28 @@ class GaussianSplattingPlugin:
             self.download(behaviors.ptr, out)
         return out
 
+    # -- point-in-mesh selection (src/query/raycast.rs; libbgs_query.so) ----------------
+    def keep_inside_mesh(self, chunk: DeviceEntriesChunk, points_ptr: int, mesh, matrix=None, outside: bool = False,
+                         n: Optional[int] = None) -> None:
+        """Cull from a kept chunk every entry whose splat lies outside `mesh` (a `mesh_query.MeshQuery`; with `outside`,
+        inside it): its key becomes 0xFFFFFFFF, which `render(..., entries=chunk)` skips wherever it stands. `points_ptr`
+        is the device address of the cloud's `position_visibility` plane in caller-owned memory (`n` points, default
+        `chunk.count`), `matrix` the 4x4 `mesh_query.mesh_from_points` (None = identity). Applies the ordering rule of
+        include/bgs_query.h: completes the frames in flight (they may read the chunk), enqueues the two query launches
+        on `bgs_stream`, and completes them before it returns."""
+        n = int(chunk.count if n is None else n)
+        self.synchronize()
+        if n == 0 or chunk.count == 0:
+            return
+        scratch = self.device_alloc(4 * n)
+        try:
+            stream = self.stream_handle()
+            mesh.crossings(stream, points_ptr, n, matrix, scratch)
+            mesh.entries_keep(stream, chunk.ptr, chunk.count, scratch, n, outside=outside)
+            self.synchronize()
+        finally:
+            self.device_free(scratch)
+
     # -- hot path --------------------------------------------------------------------
     def sort(self, handle: PlanarGaussian3dHandle, view: View, settings: CloudSettings,
              download: bool = True, into: Optional[DeviceEntriesChunk] = None) -> Optional[np.ndarray]:
