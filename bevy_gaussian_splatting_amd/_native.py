@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = (
     "bgs_set_tile_trace",
     "bgs_selftest_ln_f32",
     "bgs_selftest_pack",
+    "bgs_debug_frame_records",
     "bgs_settings_default",
     "bgs_view_perspective",
     "bgs_cloud_upload_f32",
@@ -123,6 +124,13 @@ class BgsStats(ctypes.Structure):
         ("strip_tiles", ctypes.c_uint32),
         ("tile_saturation", ctypes.c_uint32),
     ]
+
+
+class BgsFrameRecordsInfo(ctypes.Structure):
+    """bgs_frame_records_info (include/bgs_diag.h)."""
+
+    _fields_ = [("draw_count", ctypes.c_uint32), ("record_stride", ctypes.c_uint32), ("has_rects", ctypes.c_uint32),
+                ("visible_count", ctypes.c_uint32), ("color_max_bits", ctypes.c_uint32)]
 
 
 class BgsError(RuntimeError):
@@ -225,6 +233,8 @@ def load() -> ctypes.CDLL:
     lib.bgs_selftest_ln_f32.restype = ctypes.c_int
     lib.bgs_selftest_pack.argtypes = [vp, u32, vp, u32, vp]
     lib.bgs_selftest_pack.restype = ctypes.c_int
+    lib.bgs_debug_frame_records.argtypes = [vp, vp, ctypes.c_uint64, up, u32, ctypes.POINTER(BgsFrameRecordsInfo)]
+    lib.bgs_debug_frame_records.restype = ctypes.c_int
     lib.bgs_settings_default.argtypes = [ctypes.POINTER(BgsSettings)]
     lib.bgs_settings_default.restype = None
     lib.bgs_view_perspective.argtypes = [

@@ -216,6 +216,10 @@ struct Lane {
 
     const uint2* last_sorted = nullptr;
     uint32_t last_sorted_n = 0;
+    // The Control block (in `scratch`) the lane's last ENQUEUED render used — a re-run's is the re-run's —, for
+    // bgs_debug_frame_records: a frame's own block keeps what its project kernel left (visible_count, color_max_bits)
+    // until the lane's next frame. Null after a bgs_sort and after anything else that rewrites the scratch region.
+    const Control* last_ctl = nullptr;
 
     bgs_stats result{};      // counters of the last completed frame of this lane (no timings)
     bool has_result = false;

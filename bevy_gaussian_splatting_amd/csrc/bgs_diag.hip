@@ -15,6 +15,7 @@ int bgs_radix_sort_pairs(bgs_ctx* ctx, bgs_sort_entry* entries, uint32_t n, uint
     if (n == 0) return BGS_OK;
     if (!entries) return fail(ctx, BGS_EINVAL, "entries is NULL");
     Lane& L = ctx->lanes[0];
+    L.last_ctl = nullptr;   // (the last frame's Control block and tile rectangles go: bgs_debug_frame_records)
     if ((rc = ensure_entries(ctx, L, n)) != BGS_OK) return rc;
     if ((rc = ensure_scratch(ctx, L, n, L.inst[0].capacity)) != BGS_OK) return rc;
     hipStream_t st = L.stream;
@@ -168,6 +169,66 @@ int bgs_selftest_tile_order(bgs_ctx* ctx, const uint16_t* host_cost, uint32_t nt
         for (uint32_t x = 0; x < 8u; ++x) { host_sums[0] += pairs[2u * x]; host_sums[1] += pairs[2u * x + 1u]; }
     }
     if (!ok) { (void)hipGetLastError(); return fail(ctx, BGS_EHIP, "tile-order self-test failed on the device"); }
+    return BGS_OK;
+}
+
+// The Control block of the lane's last frame (Lane::last_ctl) is one of the two in the lane's scratch region. Where each
+// value the hook reads is final, from bgs_frame.hip (enqueue_frame, finish_lane) and render_kernels.hip:
+//   records      written by project_rank only (project_kernel / project_emit_kernel); bin_kernel and the rasterisers read them.
+//                A re-run projects the whole list again into the same buffer, so the buffer holds the last run's records.
+//   rects        written by project_kernel only (rects[j] for every j < count), read by bin_kernel; BINNING_SCAN frames only.
+//   draw_count   keygen / the compaction / the bucket sort; the project kernels read it as `sort_overflow ? 0 : draw_count`,
+//                which is what is reported here.
+//   visible_count, color_max_bits   accumulated by the project kernel of the run alone. A BINNING_SCAN frame's rasteriser
+//                zeroes the OTHER Control block (the lane's next frame's) and copies the header words to the pinned host
+//                copy, which does not carry color_max_bits: both words are read from the frame's own device block, which
+//                nothing writes until the lane's next frame runs (its rasteriser zeroes it as ITS other block). A
+//                BINNING_SORT frame copies its whole block to the host and leaves it in place until the next memset.
+int bgs_debug_frame_records(bgs_ctx* ctx, void* host_records, uint64_t records_capacity_bytes, uint32_t* host_rects,
+                            uint32_t rects_capacity_words, bgs_frame_records_info* info_out) {
+    if (!ctx) return fail(nullptr, BGS_EINVAL, "ctx is NULL");
+    if (!info_out) return fail(ctx, BGS_EINVAL, "frame records: info_out is NULL");
+    if (ctx->depth != 1) return fail(ctx, BGS_EINVAL, "frame records: the pipeline depth must be 1");
+    for (const Lane& lane : ctx->lanes)
+        if (lane.pending) return fail(ctx, BGS_EINVAL, "frame records: frames are in flight");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, BGS_EHIP, "hipSetDevice failed");
+    int rc = finish_all(ctx);
+    if (rc != BGS_OK) return rc;
+    Lane& L = ctx->lanes[0];
+    if (!L.has_result || !L.plan.render || !L.last_ctl || !L.stream)
+        return fail(ctx, BGS_EINVAL, "frame records: no frame has been rendered (or a bgs_sort / bgs_radix_sort_pairs ran since)");
+    if (L.in.allow_graph) return fail(ctx, BGS_EINVAL, "frame records: the last frame was an async frame");
+    hipStream_t st = L.stream;
+    uint32_t head[CONTROL_HEADER_WORDS] = {};
+    uint32_t cmax = 0u;
+    HIP_TRY(ctx, hipMemcpyAsync(head, L.last_ctl, sizeof head, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(&cmax, &L.last_ctl->color_max_bits, sizeof cmax, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    struct { uint32_t draw_count, visible_count, sort_overflow; } h{head[offsetof(Control, draw_count) / 4u], head[offsetof(Control, visible_count) / 4u],
+                                                                     head[offsetof(Control, sort_overflow) / 4u]};
+    static_assert(offsetof(Control, sort_overflow) / 4u < CONTROL_HEADER_WORDS, "the three words are in the header");
+    bgs_frame_records_info info{};
+    info.draw_count = h.sort_overflow ? 0u : h.draw_count;
+    info.record_stride = L.plan.rec_bytes;
+    info.has_rects = L.plan.scan ? 1u : 0u;
+    info.visible_count = h.visible_count;
+    info.color_max_bits = cmax;
+    *info_out = info;
+    if (!host_records && !host_rects) return BGS_OK;   // the sizes only
+    const uint64_t rec_bytes = (uint64_t)info.draw_count * info.record_stride;
+    if (info.draw_count > L.plan.n || rec_bytes > (uint64_t)L.records.capacity ||
+        (info.has_rects && info.draw_count > L.rects.capacity))
+        return fail(ctx, BGS_EINTERNAL, "frame records: the frame's draw count exceeds the lane's buffers");
+    if (!host_records || records_capacity_bytes < rec_bytes)
+        return fail(ctx, BGS_EINVAL, "frame records: host_records holds " + std::to_string(records_capacity_bytes) + " bytes, the frame's records are " +
+                                         std::to_string(rec_bytes));
+    if (info.has_rects && (!host_rects || rects_capacity_words < info.draw_count))
+        return fail(ctx, BGS_EINVAL, "frame records: host_rects holds " + std::to_string(rects_capacity_words) + " words, the frame has " +
+                                         std::to_string(info.draw_count) + " ranks");
+    if (rec_bytes) HIP_TRY(ctx, hipMemcpyAsync(host_records, L.records.ptr, rec_bytes, hipMemcpyDeviceToHost, st));
+    if (info.has_rects && info.draw_count)
+        HIP_TRY(ctx, hipMemcpyAsync(host_rects, L.rects.ptr, (size_t)info.draw_count * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
     return BGS_OK;
 }
 

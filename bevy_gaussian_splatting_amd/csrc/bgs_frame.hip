@@ -100,6 +100,7 @@ int ensure_scratch(bgs_ctx* ctx, Lane& L, uint32_t n, uint64_t inst_cap) {
     if (L.scratch.ptr && n <= L.layout.n && inst_cap <= L.layout.inst_cap) return BGS_OK;
     L.layout = scratch_layout(std::max(n, L.layout.n), std::max(inst_cap, L.layout.inst_cap));
     L.scratch_clean = false;
+    L.last_ctl = nullptr;   // (it pointed into the old region)
     if (!L.scratch.reserve(L.layout.bytes)) return fail(ctx, BGS_ENOMEM, "hipMalloc(scratch) failed");
     return BGS_OK;
 }
@@ -1093,6 +1094,7 @@ int enqueue_frame(bgs_ctx* ctx, Lane& L, const FrameInputs& in) {
     // ---- 6. the lane keeps the frame's inputs and plan
     L.last_sorted = draw_list;
     L.last_sorted_n = n;
+    L.last_ctl = render ? ctl : nullptr;
     L.fb_valid = !(p.out_format & OUT_SKIP_F32) || (flags & BGS_DEBUG_SEPARATE_ENCODE);
     L.fb8_is_f16 = (p.out_format & OUT_RGBA16F) != 0u;
     L.fb8_valid = p.want_srgb8;

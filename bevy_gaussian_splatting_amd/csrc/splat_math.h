@@ -14,6 +14,10 @@
 // build exists only for tests/test_device_math_host.py (a CPU pre-flight of this header
 // against the oracle, so transcription slips are caught without a GPU). It is not a
 // fallback: libbgs never calls these functions on the host.
+//
+// What enforces the contract on the DEVICE build: tests/test_vertex_stage_gpu.py reads back the records, tile rectangles,
+// visible_count and color_max_bits a frame's project kernel left (bgs_debug_frame_records) and compares them with the g++
+// build of project_splat, record by record and bit for bit — every field but the one power of srgb_to_linear1 below.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -52,8 +56,13 @@ BGS_HD uint32_t xcd_runs_item(const uint32_t b, const uint32_t n, const uint32_t
     return n;   // not reached for b < n
 }
 
+// (The optical-flow hue's atan2 is not libm's either, and for the same reason: atan2_f32_fixed below.)
 // The one transcendental that feeds only a COLOUR (never a cull decision, a sort key or a quad) — the 2.4 power of
-// srgb_to_linear — uses the hardware exp2/log2 on the device (~1 ulp); the host build keeps libm. Everything that
+// srgb_to_linear — uses the hardware exp2/log2 on the device; the host build keeps libm. With v_log_f32 and v_exp_f32 at
+// about 1 ulp each and the rounded product 2.4f * log2(b) between them, the log's error reaches the result multiplied by
+// ln2 * |2.4 log2 b|: the power is within 2^-23 * (1 + 2 ln2 * max(1, |2.4 log2 b|)) of b^2.4, relative — ~2 ulp near
+// b = 1, several ulp at the SH colour magnitudes of 5-15 the synthetic clouds reach (tests/test_vertex_stage_gpu.py
+// asserts twice that bound against float64; the measured ratio is in profiles/vertex_stage.md). Everything that
 // reaches a compare is +, -, *, /, sqrt (correctly rounded on gfx950) or ln_f32_cr (exact_log.h): ln(opacity) of
 // the adaptive cutoff goes into the 2DGS degeneracy tests, so it is the correctly rounded value on every side.
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -512,6 +521,41 @@ BGS_HD V3 class_to_rgb(const FrameParams& fp, float visualization, V3 sh_color) 
     return V3{sh_color.x * (1.0f - 0.5f) + c.x * 0.5f, sh_color.y * (1.0f - 0.5f) + c.y * 0.5f,
               sh_color.z * (1.0f - 0.5f) + c.z * 0.5f};
 }
+// atan2 for the optical-flow hue, the same bits on the device and in the host build: libm's atan2f is not — the device's
+// (ocml) and glibc's differ in the last place on a fifth of the inputs (tests/test_vertex_stage_gpu.py found it) —, so the
+// angle is formed here in binary64 from + - * / alone, in a fixed order (no contraction in these translation units):
+// t = min / max of the magnitudes, reduced past tan(pi/8) by atan t = pi/4 + atan((t - 1) / (t + 1)), then the odd
+// Taylor series to u^23 (|u| <= 0.4143: the first dropped term is below 2e-11), unfolded by octant and rounded to
+// binary32 once — within an ulp of the exact angle. Colour only: no decision reads it. Zero and infinite arguments go
+// where atan2f sends them; a NaN stays a NaN.
+BGS_HD float atan2_f32_fixed(float y, float x) {
+    const double ax = fabs((double)x), ay = fabs((double)y);
+    const double hi = ax > ay ? ax : ay, lo = ax > ay ? ay : ax;
+    double t = lo / hi;                                         // 0 / 0 and inf / inf: NaN, replaced below
+    if (hi == 0.0) t = 0.0;
+    if (hi == (double)INFINITY) t = lo == (double)INFINITY ? 1.0 : 0.0;
+    const bool reduce = t > 0.41421356237309503;
+    const double u = reduce ? (t - 1.0) / (t + 1.0) : t;
+    const double z = u * u;
+    double p = 1.0 / 23.0;
+    p = 1.0 / 21.0 - z * p;
+    p = 1.0 / 19.0 - z * p;
+    p = 1.0 / 17.0 - z * p;
+    p = 1.0 / 15.0 - z * p;
+    p = 1.0 / 13.0 - z * p;
+    p = 1.0 / 11.0 - z * p;
+    p = 1.0 / 9.0 - z * p;
+    p = 1.0 / 7.0 - z * p;
+    p = 1.0 / 5.0 - z * p;
+    p = 1.0 / 3.0 - z * p;
+    p = 1.0 - z * p;
+    double r = u * p;
+    if (reduce) r = 0.78539816339744831 + r;
+    if (ay > ax) r = 1.5707963267948966 - r;
+    if (x < 0.0f || (x == 0.0f && f2u(x) != 0u)) r = 3.1415926535897931 - r;   // (atan2f tells -0 from +0)
+    if (y < 0.0f || (y == 0.0f && f2u(y) != 0u)) r = -r;
+    return (float)r;
+}
 // RASTERIZE_OPTICAL_FLOW (gaussian.wgsl:369-375; src/material/optical_flow.wgsl:16-53). For a 3D cloud
 // previous_transformed_position == transformed_position (gaussian.wgsl:201), so the flow is the
 // camera's. hsv_to_rgb is bevy_render's (third party, restated: see hsv_channel).
@@ -522,7 +566,7 @@ BGS_HD V3 optical_flow_rgb(const FrameParams& fp, V3 tp) {
     const float mx = (a.x / a.w - b.x / b.w) * 0.5f, my = (a.y / a.w - b.y / b.w) * -0.5f;
     const float fx = mx / fp.delta_time, fy = my / fp.delta_time;
     const float radius = sqrtf(fx * fx + fy * fy);
-    float angle = atan2f(fy, fx);
+    float angle = atan2_f32_fixed(fy, fx);   // atan2(fy, fx): see above
     if (angle < 0.0f) angle += 6.283185307f;
     const float m = clamp1(radius, 0.0f, 1.0f);
     return V3{hsv_channel(5.0f, angle, m, 1.0f), hsv_channel(3.0f, angle, m, 1.0f), hsv_channel(1.0f, angle, m, 1.0f)};

@@ -423,6 +423,24 @@ class GaussianSplattingPlugin:
         code = fmt if isinstance(fmt, int) else {"srgb8": 1, "rgba16f": 2}[fmt]   # BGS_PACK_SRGB8 / BGS_PACK_RGBA16F
         self._check(self._lib.bgs_selftest_pack(self._ctx, code, device_in or None, int(pixels), device_out or None))
 
+    def debug_frame_records(self) -> dict:
+        """`bgs_debug_frame_records`: what the vertex stage of the last synchronous `render` left on the device, as it is:
+        `records` uint32[draw_count, stride / 4] (12 words: Record, 24: RecordSurfel; front-to-back rank order), `rects`
+        uint32[draw_count] (scan binning; None otherwise), and `draw_count`, `record_stride`, `visible_count`,
+        `color_max_bits`. Test hook; raises when there is no such frame (see include/bgs_diag.h)."""
+        info = _native.BgsFrameRecordsInfo()
+        self._check(self._lib.bgs_debug_frame_records(self._ctx, None, 0, None, 0, ctypes.byref(info)))
+        count, words = int(info.draw_count), int(info.record_stride) // 4
+        records = np.zeros((count, words), np.uint32)
+        rects = np.zeros(count, np.uint32)
+        self._check(self._lib.bgs_debug_frame_records(self._ctx, records.ctypes.data_as(ctypes.c_void_p), records.nbytes,
+                                                      _uptr(rects), count, ctypes.byref(info)))
+        if int(info.draw_count) != count:
+            raise RuntimeError("the frame changed between the two calls of bgs_debug_frame_records")
+        return {"draw_count": count, "record_stride": int(info.record_stride), "records": records,
+                "rects": rects if info.has_rects else None, "visible_count": int(info.visible_count),
+                "color_max_bits": int(info.color_max_bits)}
+
     def set_pipeline_streams(self, streams: int) -> None:
         """HIP streams the lanes are multiplexed onto (0 = one per lane); see bgs_set_pipeline_streams."""
         self._check(self._lib.bgs_set_pipeline_streams(self._ctx, int(streams)))

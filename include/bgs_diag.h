@@ -129,6 +129,26 @@ int bgs_selftest_tile_order(bgs_ctx* ctx, const uint16_t* host_cost, uint32_t nt
 enum bgs_pack_format { BGS_PACK_SRGB8 = 1, BGS_PACK_RGBA16F = 2 };
 int bgs_selftest_pack(bgs_ctx* ctx, uint32_t format, const void* device_in_rgba_f32, uint32_t pixels, void* device_out);
 
+/* What the vertex stage of lane 0's last completed, synchronous bgs_render left on the device, copied to host memory as
+ * it is (tests/test_vertex_stage_gpu.py compares it, record by record, with the host build of csrc/splat_math.h):
+ *   info_out       draw_count: the ranks the frame projected (0 after a voided draw list); record_stride: 48 (Record) or
+ *                  96 bytes (RecordSurfel, csrc/bgs_device.h); has_rects: 1 for a BGS_BINNING_SCAN frame; visible_count and
+ *                  color_max_bits (the bits of the largest |r|, |g|, |b| of the drawn records) as the frame's last run
+ *                  left them — after a re-run, the re-run's;
+ *   host_records   the first draw_count records, front-to-back rank order (rank j = draw list entry draw_count - 1 - j);
+ *                  a rank that is not drawn keeps whatever the buffer held;
+ *   host_rects     BGS_BINNING_SCAN frames: the packed tile rectangle x0 | x1 << 8 | y0 << 16 | y1 << 24 of every rank,
+ *                  0x000000FF for a rank that is not drawn. Other frames have none and leave it untouched.
+ * With host_records and host_rects both NULL only info_out is filled (a caller sizes its buffers with it). Launches no
+ * kernel: copies on the lane's stream, then waits for them. BGS_EINVAL, with the reason in bgs_last_error, when no frame
+ * has been rendered (or a bgs_sort / bgs_radix_sort_pairs ran since), when frames are in flight or the pipeline depth is
+ * not 1, when the last frame was an async one, and when a capacity (bytes / words) is too small. Test hook. */
+typedef struct bgs_frame_records_info {
+    uint32_t draw_count, record_stride, has_rects, visible_count, color_max_bits;
+} bgs_frame_records_info;
+int bgs_debug_frame_records(bgs_ctx* ctx, void* host_records, uint64_t records_capacity_bytes, uint32_t* host_rects,
+                            uint32_t rects_capacity_words, bgs_frame_records_info* info_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -126,6 +126,11 @@ def shim() -> ctypes.CDLL:
     l.shim_sort_keys_two_step.restype = None
     l.shim_project.argtypes = [ctypes.POINTER(FrameParamsC), ctypes.c_uint32, fp, fp, fp, fp, fp, ctypes.POINTER(ShimOut)]
     l.shim_project.restype = None
+    l.shim_project_batch.argtypes = [ctypes.POINTER(FrameParamsC), ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, fp, fp, fp, fp, fp, fp,
+                                     ctypes.POINTER(ShimOut), fp]
+    l.shim_project_batch.restype = None
+    l.shim_surfel_probe.argtypes = [ctypes.POINTER(FrameParamsC), fp, fp, fp, fp]
+    l.shim_surfel_probe.restype = None
     l.shim_distance_to_camera.argtypes = [ctypes.POINTER(FrameParamsC), fp]
     l.shim_distance_to_camera.restype = ctypes.c_float
     l.shim_scratch_layout.argtypes = [ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(ScratchLayoutC)]
@@ -194,10 +199,11 @@ def device_sorted_entries(cloud, view, settings) -> np.ndarray:
     return out
 
 
-def emulate_render(cloud: PlanarGaussian3d, view: View, settings: CloudSettings, entries=None) -> np.ndarray:
+def emulate_render(cloud: PlanarGaussian3d, view: View, settings: CloudSettings, entries=None, cov3d: bool = False) -> np.ndarray:
     """numpy emulation of project_emit + raster: records from the HOST BUILD of splat_math.h,
     composited front-to-back per pixel exactly as raster_kernel does (same record fields, same
-    formulas), without tiling. Small scenes only."""
+    formulas), without tiling. Small scenes only. `cov3d`: the records of the cloud's precomputed-covariance form
+    (project_splat's cov3d_pre argument, through shim_project_batch)."""
     if entries is None:
         entries = device_sorted_entries(cloud, view, settings)
     depth = getattr(view, "depth_host", None)   # [H, W, samples] scene depth (random_case), or None
@@ -227,7 +233,13 @@ def emulate_render(cloud: PlanarGaussian3d, view: View, settings: CloudSettings,
         i_first, i_last = int(entries[min(1, n - 1)]["index"]), int(entries[n - 1]["index"])
         depth_range[0] = shim().shim_distance_to_camera(ctypes.byref(fpc), _fp(cloud.position_visibility[i_last]))
         depth_range[1] = shim().shim_distance_to_camera(ctypes.byref(fpc), _fp(cloud.position_visibility[i_first]))
+    outs = twin_project(cloud, view, settings, entries[:count], fmt="cov3d", full_entries=entries)["raw"] if cov3d else None
+
     def project(j):
+        nonlocal out
+        if outs is not None:
+            out = outs[count - 1 - j]
+            return bool(out.draw)
         e = entries[count - 1 - j]
         si = int(e["index"])
         shim().shim_project(ctypes.byref(fpc), int(e["key"]), _fp(cloud.position_visibility[si]),
@@ -305,6 +317,114 @@ def emulate_render(cloud: PlanarGaussian3d, view: View, settings: CloudSettings,
     img[..., :3] = C + T[..., None] * clear[:3]
     img[..., 3] = (np.float32(1) - T) + T * clear[3]
     return img
+
+
+# ---- the host twin of the device's vertex stage, for whole draw lists (tests/test_vertex_stage_*.py) -----------------
+RECT_EMPTY = 0x000000FF   # csrc/bgs_device.h; tests/test_vertex_stage_host.py holds it to the header
+# the float4 lanes of a record in project_rank's order (csrc/render_kernels.hip): Record 3 x float4, RecordSurfel 6 x float4
+RECORD_FIELDS = ("cx", "cy", "p0", "p1", "p2", "p3", "p4", "r", "g", "b", "a", "z")
+SURFEL_FIELDS = ("cx", "cy", "m00", "m11", "radius", "mean_x", "mean_y") + tuple(f"T{i}" for i in range(9)) + \
+                ("r", "g", "b", "a", "z", "pad0", "pad1", "pad2")
+COLOR_FIELDS = ("r", "g", "b")
+
+
+def twin_draw_list(cloud, view, settings, kept=None):
+    """(draw list, full list) of a frame as the device forms them, from the host build of the key arithmetic: the
+    drawable prefix of the sorted entries — SortMode::Radix leaves the culled keys behind it, the other modes keep every
+    splat — or, for a kept order (`kept`: the caller's chunk), the entries entry_kept (csrc/entries_math.h) lets through,
+    in chunk order; the full list is the draw list followed by the rest (RasterizeMode::Depth reads its ends)."""
+    n = len(cloud)
+    if kept is not None:
+        keep = (kept["key"] != 0xFFFFFFFF) & (kept["index"] < n)
+        tail = kept[~keep].copy()
+        tail["index"] = np.where(tail["index"] < n, tail["index"], n - 1)
+        return kept[keep].copy(), np.concatenate([kept[keep], tail])
+    full = device_sorted_entries(cloud, view, settings)
+    if settings.sort_mode == SortMode.Radix:
+        sentinel = np.uint32(0xFFFFFFFF >> frame_params(n, view, settings).key_shift)
+        return full[: int((full["key"] != sentinel).sum())].copy(), full
+    return full.copy(), full
+
+
+def twin_project(cloud: PlanarGaussian3d, view: View, settings: CloudSettings, entries, fmt: str = "f32", full_entries=None) -> dict:
+    """project_splat's host build over a whole draw list, as project_rank calls it for the cloud format `fmt`: "f32",
+    "f16" (the planes encoded and decoded: f16 -> f32 is exact, so the twin sees what the device's loads see) or "cov3d"
+    (the Covariance3dOpacity plane, project_splat's cov3d_pre). Arrays in ENTRY order (the device's rank j is entry
+    count - 1 - j); geometry and colour fields are meaningful where `draw` is set. `full_entries`: the frame's full list
+    (RasterizeMode::Depth normalises by its entries 1 and n - 1; default: `entries`)."""
+    n, count = len(cloud), len(entries)
+    fpc = frame_params(n, view, settings)
+    src = cloud.to_f16().to_f32() if fmt == "f16" else cloud
+    pv = np.ascontiguousarray(cloud.position_visibility, np.float32)
+    sh = np.ascontiguousarray(src.spherical_harmonic, np.float32)
+    rot = so = cov = None
+    if fmt == "cov3d":
+        from bevy_gaussian_splatting_amd.gaussian import covariance_3d_opacity
+        cov = np.ascontiguousarray(covariance_3d_opacity(cloud), np.float32)
+    else:
+        rot, so = np.ascontiguousarray(src.rotation, np.float32), np.ascontiguousarray(src.scale_opacity, np.float32)
+    depth_range = np.zeros(2, np.float32)
+    full = entries if full_entries is None else full_entries
+    if n > 0 and len(full) == n:
+        i_first, i_last = int(full[min(1, n - 1)]["index"]), int(full[n - 1]["index"])
+        depth_range[0] = shim().shim_distance_to_camera(ctypes.byref(fpc), _fp(pv[i_last]))
+        depth_range[1] = shim().shim_distance_to_camera(ctypes.byref(fpc), _fp(pv[i_first]))
+    e32 = np.ascontiguousarray(np.stack([entries["key"], entries["index"]], axis=1), np.uint32) if count else np.zeros((0, 2), np.uint32)
+    outs = (ShimOut * max(count, 1))()
+    cross = np.zeros((max(count, 1), 9), np.float32)
+    null = ctypes.POINTER(ctypes.c_float)()
+    shim().shim_project_batch(ctypes.byref(fpc), e32.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), count, _fp(pv),
+                              _fp(rot) if rot is not None else null, _fp(so) if so is not None else null, _fp(sh),
+                              _fp(cov) if cov is not None else null, _fp(depth_range), outs, _fp(cross))
+    a = np.frombuffer(outs, dtype=np.dtype(ShimOut))[:count]
+    rect = np.stack([a["tx0"], a["tx1"], a["ty0"], a["ty1"]], axis=1).astype(np.int64)
+    return {"raw": outs, "count": count, "visible": a["visible"] != 0, "draw": a["draw"] != 0, "color": a["color"].copy(),
+            "cx": a["cx"].copy(), "cy": a["cy"].copy(), "p": a["p"].copy(), "radius": a["radius"].copy(), "mean": a["mean"].copy(),
+            "T": a["T"].copy(), "cross": cross[:count], "bounds": a["bounds"].copy(), "z": a["ndc_z"].copy(), "rect": rect, "depth_range": depth_range,
+            "surfel": bool(fpc.gaussian_mode == 0 and fpc.aabb != 0)}
+
+
+def twin_rect_words(twin) -> np.ndarray:
+    """The packed tile rectangle x0 | x1 << 8 | y0 << 16 | y1 << 24 per RANK (project_rank), RECT_EMPTY where the twin does
+    not draw."""
+    r = twin["rect"][::-1]
+    words = (r[:, 0] | (r[:, 1] << 8) | (r[:, 2] << 16) | (r[:, 3] << 24)).astype(np.uint32)
+    return np.where(twin["draw"][::-1], words, np.uint32(RECT_EMPTY)).astype(np.uint32)
+
+
+def twin_instances(twin) -> int:
+    """Sum of the drawn ranks' tile-rectangle areas: what project_emit_kernel's scan totals."""
+    r = twin["rect"][twin["draw"]]
+    return int(((r[:, 1] - r[:, 0] + 1) * (r[:, 3] - r[:, 2] + 1)).sum())
+
+
+def twin_record_words(twin):
+    """(records, rects, drawn): the device's record array for the twin's draw list as uint32 [count, 12] (Record) or
+    [count, 24] (RecordSurfel) — the exact bytes project_rank writes, rank j = entry count - 1 - j —, the packed rect
+    word per rank, and which ranks the twin draws. A rank it does not draw is all zero here (the device leaves whatever
+    its buffer held) and RECT_EMPTY in rects."""
+    count = twin["count"]
+    f = lambda x: np.ascontiguousarray(x[::-1], np.float32)
+    col, p = f(twin["color"]), f(twin["p"])
+    if twin["surfel"]:
+        mean, cross = f(twin["mean"]), f(twin["cross"])
+        lanes = [f(twin["cx"]), f(twin["cy"]), p[:, 0], p[:, 1], f(twin["radius"]), mean[:, 0], mean[:, 1]] + \
+                [cross[:, i] for i in range(9)] + [col[:, 0], col[:, 1], col[:, 2], col[:, 3], f(twin["z"])] + \
+                [np.zeros(count, np.float32)] * 3
+    else:
+        lanes = [f(twin["cx"]), f(twin["cy"]), p[:, 0], p[:, 1], p[:, 2], p[:, 3], p[:, 4], col[:, 0], col[:, 1], col[:, 2], col[:, 3],
+                 f(twin["z"])]
+    rec = np.ascontiguousarray(np.stack(lanes, axis=1), np.float32).view(np.uint32) if count else np.zeros((0, len(lanes)), np.uint32)
+    drawn = twin["draw"][::-1].copy()
+    rec = np.where(drawn[:, None], rec, np.uint32(0)).astype(np.uint32)
+    return rec, twin_rect_words(twin), drawn
+
+
+def record_fields(records: np.ndarray) -> dict:
+    """The named lanes of a record array (uint32 [count, 12 or 24], the device's or the twin's) as float32 columns."""
+    names = {12: RECORD_FIELDS, 24: SURFEL_FIELDS}[records.shape[1]]
+    fl = np.ascontiguousarray(records, np.uint32).view(np.float32)
+    return {name: fl[:, i] for i, name in enumerate(names)}
 
 
 # ---- scenes of the reference's own tests / tools ------------------------------------------

@@ -145,17 +145,18 @@ void shim_sort_keys_two_step(const FrameParams* fp, const float* pos_vis, uint32
     *unsure_out = unsure_count;
 }
 
-// pos = position_visibility row (4 floats); depth_range = {min_distance, max_distance}
-void shim_project(const FrameParams* fp, uint32_t key, const float* pos, const float* rot,
-                  const float* so, const float* sh48, const float* depth_range, ShimOut* out) {
+// One draw-list entry through project_splat, the way project_rank (render_kernels.hip) calls it: the Color-only
+// instantiation unless another mode is asked for (the launchers' dispatch); cov6 != nullptr is the CLOUD_COV3D call
+// (rot and so[0..2] unused, the six covariance entries handed through).
+static void project_one(const FrameParams* fp, uint32_t key, const float* pos, const float* rot, const float* so,
+                        const float* sh48, const float* cov6, const float* depth_range, ShimOut* out) {
     Projected pr;
     memset(&pr, 0, sizeof pr);
     ColorInputs ci{pos[3], depth_range[0], depth_range[1]};
-    // the same dispatch as the launchers: the Color-only instantiation unless another mode is asked for
     if (fp->rasterize_mode == RASTERIZE_COLOR && fp->draw_mode == 0u)
-        project_splat<false>(*fp, key, V3{pos[0], pos[1], pos[2]}, rot, so, ShFloat{sh48}, ci, pr);
+        project_splat<false>(*fp, key, V3{pos[0], pos[1], pos[2]}, rot, so, ShFloat{sh48}, ci, pr, cov6);
     else
-        project_splat<true>(*fp, key, V3{pos[0], pos[1], pos[2]}, rot, so, ShFloat{sh48}, ci, pr);
+        project_splat<true>(*fp, key, V3{pos[0], pos[1], pos[2]}, rot, so, ShFloat{sh48}, ci, pr, cov6);
     memset(out, 0, sizeof *out);
     out->visible = pr.visible;
     out->draw = pr.draw;
@@ -174,6 +175,56 @@ void shim_project(const FrameParams* fp, uint32_t key, const float* pos, const f
     out->bounds[0] = pr.quad.minx; out->bounds[1] = pr.quad.maxx;
     out->bounds[2] = pr.quad.miny; out->bounds[3] = pr.quad.maxy;
     out->ndc_z = pr.ndc_z;
+}
+
+// pos = position_visibility row (4 floats); depth_range = {min_distance, max_distance}
+void shim_project(const FrameParams* fp, uint32_t key, const float* pos, const float* rot,
+                  const float* so, const float* sh48, const float* depth_range, ShimOut* out) {
+    project_one(fp, key, pos, rot, so, sh48, nullptr, depth_range, out);
+}
+
+// A whole entry list: out[e] is entry e = (key, index) of `entries` (list order; the device's rank j is entry
+// count - 1 - j). The planes are the cloud's, indexed by the entry's index: rot / scale_opacity [n][4], or — a
+// precomputed-covariance cloud — cov3d_opacity [n][8] (cov3d[6], opacity, pad) with rot = scale_opacity = NULL, which
+// takes project_rank's CLOUD_COV3D branch: rot = identity, so = (0, 0, 0, opacity), the six entries as cov3d_pre.
+// cross (may be NULL): [count][9], the surfel record's cross products A = T1 x T2, B = T2 x T0, C = T0 x T1 of
+// Surfel::T's columns, formed in double and rounded to float once each, the statements of project_rank.
+void shim_project_batch(const FrameParams* fp, const uint32_t* entries, uint32_t count, const float* pos_vis, const float* rot,
+                        const float* scale_opacity, const float* sh48, const float* cov3d_opacity, const float* depth_range,
+                        ShimOut* out, float* cross) {
+    for (uint32_t e = 0; e < count; ++e) {
+        const uint32_t key = entries[2 * e], si = entries[2 * e + 1];
+        if (cov3d_opacity) {
+            const float* c = cov3d_opacity + 8 * (size_t)si;
+            const float r1[4] = {1.0f, 0.0f, 0.0f, 0.0f}, so1[4] = {0.0f, 0.0f, 0.0f, c[6]};
+            project_one(fp, key, pos_vis + 4 * (size_t)si, r1, so1, sh48 + 48 * (size_t)si, c, depth_range, out + e);
+        } else {
+            project_one(fp, key, pos_vis + 4 * (size_t)si, rot + 4 * (size_t)si, scale_opacity + 4 * (size_t)si,
+                        sh48 + 48 * (size_t)si, nullptr, depth_range, out + e);
+        }
+        if (cross) {
+            const float* T = out[e].T;
+            float* x = cross + 9 * (size_t)e;
+            const double T0x = T[0], T0y = T[1], T0z = T[2];
+            const double T1x = T[3], T1y = T[4], T1z = T[5];
+            const double T2x = T[6], T2y = T[7], T2z = T[8];
+            x[0] = (float)(T1y * T2z - T1z * T2y); x[1] = (float)(T1z * T2x - T1x * T2z); x[2] = (float)(T1x * T2y - T1y * T2x);
+            x[3] = (float)(T2y * T0z - T2z * T0y); x[4] = (float)(T2z * T0x - T2x * T0z); x[5] = (float)(T2x * T0y - T2y * T0x);
+            x[6] = (float)(T0y * T1z - T0z * T1y); x[7] = (float)(T0z * T1x - T0x * T1z); x[8] = (float)(T0x * T1y - T0y * T1x);
+        }
+    }
+}
+
+// The two degeneracy decisions of the 2DGS path for one splat (cov2d_surfel, bounding_box_cov2d: `|d| < 1e-4` and
+// `extent < 1e-4`), so that a test can show its edge-on clouds hold both outcomes of each: out = extent[0], extent[1],
+// and 1 where cov2d_surfel returned at its d test (it then leaves T zero; otherwise T[8] is the centre's clip w, not 0 in the frustum).
+void shim_surfel_probe(const FrameParams* fp, const float* pos, const float* rot, const float* so, float out[3]) {
+    const V4 t4 = m4_mul_point(fp->transform, V3{pos[0], pos[1], pos[2]});
+    Surfel sf;
+    cov2d_surfel(*fp, V3{t4.x, t4.y, t4.z}, rot, so, cutoff_radius(*fp, so[3]), sf);
+    bool zero = true;
+    for (int i = 0; i < 9; ++i) zero = zero && sf.T[i] == 0.0f;
+    out[0] = sf.extent[0]; out[1] = sf.extent[1]; out[2] = zero ? 1.0f : 0.0f;
 }
 
 float shim_distance_to_camera(const FrameParams* fp, const float* pos) {
