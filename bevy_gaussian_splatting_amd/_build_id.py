@@ -1,47 +1,86 @@
-"""Identity of the kernel sources: SHA-256 over every HIP source and header of libbgs (csrc/*.hip, csrc/*.h) and the
-Makefile that holds the compiler flags they are built with.
+"""Build identity of the package's native libraries: what each one is, the SHA-256 of the sources it is built from, and
+the id a built library carries.
 
-The Makefile compiles it into libbgs.so (`bgs_build_id()`, and as the byte string `BGS_BUILD_ID=<hex>` so that it can
-be read without loading the library); `_native.load()` refuses a library built from other sources and rebuilds it
-instead, so a stale prebuilt binary can never be what the tests or `bench.py` ran. Counter files under `profiles/`
-are stamped with the same hash. Not the commit id: that also changes with every documentation commit.
+Each library's Makefile runs this file and compiles the hash into the library as the byte string `<MARKER><hex>`, where
+it can be read without loading the library (libbgs.so also returns it from `bgs_build_id()`). `_loader.ensure_current`
+rebuilds a library that carries another id and refuses one it cannot rebuild, so a stale prebuilt binary can never be
+what the tests or `bench.py` ran. Counter files under `profiles/` are stamped with libbgs's hash. Not the commit id:
+that also changes with every documentation commit.
 
-`python bevy_gaussian_splatting_amd/_build_id.py` prints the hash (used by csrc/Makefile)."""
+What a hash covers is data of the library's description, and part of the id: change a recipe and every library built
+before is stale.
+
+`python bevy_gaussian_splatting_amd/_build_id.py [libbgs | libbgs_query]` prints a library's hash (libbgs's by
+default). Standard library only and no relative import: the Makefiles run it as a plain script, and
+scripts/build_*_variant.sh copy this one file next to a bare csrc/."""
 from __future__ import annotations
 
 import hashlib
 import os
-from typing import Optional
+import sys
+from dataclasses import dataclass
+from typing import Optional, Tuple
 
-CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
-MARKER = b"BGS_BUILD_ID="
+_HERE = os.path.dirname(os.path.abspath(__file__))
 
 
-def kernel_source_sha256() -> str:
+@dataclass(frozen=True)
+class NativeLibrary:
+    name: str                                   # this file's argument; the library file is <name>.so
+    source_dir: str                             # holds the Makefile, the sources, the built library and the build lock
+    marker: bytes                               # the id stands behind it in the library's bytes
+    hashed_suffixes: Tuple[str, ...]            # the hash covers source_dir's files that end so, and its Makefile ...
+    hashed_elsewhere: Tuple[Tuple[str, str], ...] = ()   # ... then these (label, path from source_dir), as listed
+    make_args: Tuple[str, ...] = ()             # between `make -C source_dir` and ARCH=gfx950
+    dlopen_mode: int = os.RTLD_LOCAL
+
+    @property
+    def path(self) -> str:
+        return os.path.join(self.source_dir, self.name + ".so")
+
+
+# The compiler flags are in the Makefile and the Makefile is in the hash. build_id.inc is generated FROM the hash and
+# is no source. libbgs's recipe leaves out libbgs.map and include/bgs*.h, and stays so: adding them would move its id.
+LIBBGS = NativeLibrary("libbgs", os.path.join(_HERE, "csrc"), b"BGS_BUILD_ID=", (".hip", ".h"),
+                       make_args=("-j4",), dlopen_mode=os.RTLD_GLOBAL)
+LIBBGS_QUERY = NativeLibrary("libbgs_query", os.path.join(_HERE, "csrc_query"), b"BGSQ_BUILD_ID=", (".hip", ".h", ".map"),
+                             hashed_elsewhere=(("bgs_query.h", os.path.join("..", "..", "include", "bgs_query.h")),))
+LIBRARIES = {spec.name: spec for spec in (LIBBGS, LIBBGS_QUERY)}
+MARKER = LIBBGS.marker
+
+
+def source_sha256(spec: NativeLibrary) -> str:
+    """For every covered name in sorted order, the name then the file's bytes; then the same for the files elsewhere."""
+    covered = [(name, name) for name in sorted(os.listdir(spec.source_dir))
+               if name.endswith(spec.hashed_suffixes) or name == "Makefile"]
     h = hashlib.sha256()
-    for name in sorted(os.listdir(CSRC)):
-        if name.endswith((".hip", ".h")) or name == "Makefile":   # (build_id.inc is generated FROM this hash: not a source)
-            h.update(name.encode())
-            with open(os.path.join(CSRC, name), "rb") as f:
-                h.update(f.read())
+    for label, path in covered + list(spec.hashed_elsewhere):
+        h.update(label.encode())
+        with open(os.path.join(spec.source_dir, path), "rb") as f:
+            h.update(f.read())
     return h.hexdigest()
 
 
-def library_build_id(path: str) -> Optional[str]:
-    """The id compiled into a libbgs.so, read from the file's bytes (no dlopen); None if there is none."""
+def kernel_source_sha256() -> str:
+    return source_sha256(LIBBGS)
+
+
+def library_build_id(path: str, spec: NativeLibrary = LIBBGS) -> Optional[str]:
+    """The id compiled into a built library, read from the file's bytes (no dlopen); None if the file is missing or
+    carries none."""
     try:
         with open(path, "rb") as f:
             data = f.read()
     except OSError:
         return None
-    at = data.find(MARKER)
+    at = data.find(spec.marker)
     while at >= 0:
-        hexid = data[at + len(MARKER): at + len(MARKER) + 64]
+        hexid = data[at + len(spec.marker): at + len(spec.marker) + 64]
         if len(hexid) == 64 and all(c in b"0123456789abcdef" for c in hexid):
             return hexid.decode()
-        at = data.find(MARKER, at + 1)
+        at = data.find(spec.marker, at + 1)
     return None
 
 
 if __name__ == "__main__":
-    print(kernel_source_sha256())
+    print(source_sha256(LIBRARIES[sys.argv[1]] if len(sys.argv) > 1 else LIBBGS))

@@ -9,7 +9,7 @@
 #include "build_id.inc"
 #include "mesh_query_kernels.h"
 
-// The SHA-256 of the sources this library was compiled from (../_native_query.py source_sha256), readable from the
+// The SHA-256 of the sources this library was compiled from (../_build_id.py libbgs_query), readable from the
 // file's bytes: the loader rebuilds a library that carries another one.
 extern "C" __attribute__((used, visibility("hidden"))) const char bgsq_build_id_marker[] = "BGSQ_BUILD_ID=" BGSQ_BUILD_ID;
 

@@ -203,7 +203,7 @@ def test_the_library_exports_exactly_what_its_header_declares():
     assert defined == _declared() == set(_native_query.EXPORTED_SYMBOLS), sorted(defined ^ _declared())
     assert len(defined) == 8 and all(hasattr(lib, n) for n in defined)
     assert lib.bgsq_version() == (0 << 16) | 1 == _native_query.ABI_VERSION
-    assert _native_query.library_build_id(_native_query.LIB_PATH) == _native_query.source_sha256()
+    assert _build_id.library_build_id(_native_query.LIB_PATH, _build_id.LIBBGS_QUERY) == _build_id.source_sha256(_build_id.LIBBGS_QUERY)
     # it links the HIP runtime, not libbgs
     readelf = shutil.which("readelf") or "/opt/rocm/lib/llvm/bin/llvm-readelf"
     needed = subprocess.run([readelf, "-d", _native_query.LIB_PATH], check=True, capture_output=True, text=True).stdout
@@ -229,7 +229,7 @@ def test_libbgs_and_its_headers_did_not_move():
     for name in ("bgs.h", "bgs_diag.h", "bgs.hpp", "bgs_host.hpp"):
         assert "bgsq_" not in open(os.path.join(ROOT, "include", name)).read()
     assert not any(n.startswith("bgsq") for n in _native.EXPORTED_SYMBOLS)
-    assert _native_query.source_sha256() != _build_id.kernel_source_sha256()
+    assert _build_id.source_sha256(_build_id.LIBBGS_QUERY) != _build_id.kernel_source_sha256()
 
 
 def test_header_is_plain_c_and_the_cpp_layer_is_standard_cpp17(tmp_path):
