@@ -47,6 +47,12 @@ from .mesh_query import (
     icosphere_mesh,
     mesh_from_points,
 )
+from .sparse_select import (
+    SparseGrid,
+    SparseSelect,
+    neighbor_counts_reference,
+    select_reference,
+)
 from .plugin import (
     DeviceEntriesChunk,
     DeviceSortedEntries,
@@ -67,4 +73,5 @@ __all__ = [
     "DeviceEntriesChunk", "DeviceSortedEntries",
     "PARTICLE_BEHAVIOR_DTYPE", "ParticleBehaviors", "ParticleBehaviorsHandle", "random_particle_behaviors", "step_reference",
     "MeshQuery", "TriangleMesh", "crossings_reference", "cube_mesh", "icosphere_mesh", "mesh_from_points",
+    "SparseGrid", "SparseSelect", "neighbor_counts_reference", "select_reference",
 ]

@@ -10,7 +10,7 @@ that also changes with every documentation commit.
 What a hash covers is data of the library's description, and part of the id: change a recipe and every library built
 before is stale.
 
-`python bevy_gaussian_splatting_amd/_build_id.py [libbgs | libbgs_query]` prints a library's hash (libbgs's by
+`python bevy_gaussian_splatting_amd/_build_id.py [libbgs | libbgs_query | libbgs_sparse]` prints a library's hash (libbgs's by
 default). Standard library only and no relative import: the Makefiles run it as a plain script, and
 scripts/build_*_variant.sh copy this one file next to a bare csrc/."""
 from __future__ import annotations
@@ -45,7 +45,9 @@ LIBBGS = NativeLibrary("libbgs", os.path.join(_HERE, "csrc"), b"BGS_BUILD_ID=", 
                        make_args=("-j4",), dlopen_mode=os.RTLD_GLOBAL)
 LIBBGS_QUERY = NativeLibrary("libbgs_query", os.path.join(_HERE, "csrc_query"), b"BGSQ_BUILD_ID=", (".hip", ".h", ".map"),
                              hashed_elsewhere=(("bgs_query.h", os.path.join("..", "..", "include", "bgs_query.h")),))
-LIBRARIES = {spec.name: spec for spec in (LIBBGS, LIBBGS_QUERY)}
+LIBBGS_SPARSE = NativeLibrary("libbgs_sparse", os.path.join(_HERE, "csrc_sparse"), b"BGSS_BUILD_ID=", (".hip", ".h", ".map"),
+                              hashed_elsewhere=(("bgs_sparse.h", os.path.join("..", "..", "include", "bgs_sparse.h")),))
+LIBRARIES = {spec.name: spec for spec in (LIBBGS, LIBBGS_QUERY, LIBBGS_SPARSE)}
 MARKER = LIBBGS.marker
 
 

@@ -23,6 +23,7 @@ from .camera import View
 from .gaussian import PlanarGaussian3d, PlanarGaussian3dF16
 from .particles import PARTICLE_BEHAVIOR_DTYPE, ParticleBehaviors, ParticleBehaviorsHandle
 from .settings import CloudSettings
+from .sparse_select import SparseSelect, selected_indices
 
 SORT_ENTRY_DTYPE = np.dtype([("key", np.uint32), ("index", np.uint32)])
 
@@ -304,6 +305,45 @@ class GaussianSplattingPlugin:
             self.synchronize()
         finally:
             self.device_free(scratch)
+
+    # -- sparse-splat selection (src/query/sparse.rs; libbgs_sparse.so) ------------------
+    def keep_sparse(self, chunk: DeviceEntriesChunk, points_ptr: int, grid, select: SparseSelect = SparseSelect(),
+                    dense: bool = False, n: Optional[int] = None) -> None:
+        """Cull from a kept chunk every entry whose splat is not sparse under `select` (fewer than `neighbor_threshold`
+        splats within `radius`, itself included); with `dense`, every entry whose splat is: the floaters go. `grid` is a
+        `sparse_select.SparseGrid` of capacity >= n, `points_ptr` the device address of the cloud's `position_visibility`
+        plane in caller-owned memory (`n` points, default `chunk.count`). The counting stops at `neighbor_threshold`
+        neighbours a point, which the predicate cannot tell from more. Applies the ordering rule of include/bgs_sparse.h:
+        completes the frames in flight (they may read the chunk), enqueues the launches on `bgs_stream`, and completes
+        them before it returns."""
+        n = int(chunk.count if n is None else n)
+        self.synchronize()
+        if n == 0 or chunk.count == 0:
+            return
+        scratch = self.device_alloc(4 * n)
+        try:
+            stream = self.stream_handle()
+            grid.neighbor_counts(stream, points_ptr, n, select.radius, scratch, cap=select.neighbor_threshold)
+            grid.entries_keep(stream, chunk.ptr, chunk.count, scratch, n, select.neighbor_threshold, dense=dense)
+            self.synchronize()
+        finally:
+            self.device_free(scratch)
+
+    def sparse_select(self, points_ptr: int, n: int, grid, select: SparseSelect = SparseSelect()) -> np.ndarray:
+        """The ascending indices of the sparse splats among the `n` points at `points_ptr` (the reference's
+        `Select.indicies` after `SparseSelect::select`), from counts taken on the device and downloaded."""
+        n = int(n)
+        self.synchronize()
+        if n == 0:
+            return np.zeros(0, np.uint32)
+        scratch = self.device_alloc(4 * n)
+        try:
+            grid.neighbor_counts(self.stream_handle(), points_ptr, n, select.radius, scratch, cap=select.neighbor_threshold)
+            self.synchronize()
+            counts = self.download(scratch, np.empty(n, np.uint32))
+        finally:
+            self.device_free(scratch)
+        return selected_indices(counts, select.neighbor_threshold)
 
     # -- hot path --------------------------------------------------------------------
     def sort(self, handle: PlanarGaussian3dHandle, view: View, settings: CloudSettings,
