@@ -10,12 +10,14 @@ from .gaussian import (
     Gaussian3d,
     PlanarGaussian3d,
     PlanarGaussian3dF16,
+    PlanarGaussian4d,
     SphericalHarmonicCoefficients,
     SH_COEFF_COUNT,
     compute_covariance_3d,
     covariance_3d_opacity,
     random_gaussians_3d,
     random_gaussians_3d_seeded,
+    random_gaussians_4d_seeded,
     trained_like_gaussians_3d_seeded,
 )
 from .settings import (
@@ -53,6 +55,11 @@ from .sparse_select import (
     neighbor_counts_reference,
     select_reference,
 )
+from .time_slice import (
+    TimeSlicer,
+    slice_float64,
+    slice_reference,
+)
 from .plugin import (
     DeviceEntriesChunk,
     DeviceSortedEntries,
@@ -74,4 +81,5 @@ __all__ = [
     "PARTICLE_BEHAVIOR_DTYPE", "ParticleBehaviors", "ParticleBehaviorsHandle", "random_particle_behaviors", "step_reference",
     "MeshQuery", "TriangleMesh", "crossings_reference", "cube_mesh", "icosphere_mesh", "mesh_from_points",
     "SparseGrid", "SparseSelect", "neighbor_counts_reference", "select_reference",
+    "PlanarGaussian4d", "random_gaussians_4d_seeded", "TimeSlicer", "slice_float64", "slice_reference",
 ]

@@ -10,7 +10,7 @@ that also changes with every documentation commit.
 What a hash covers is data of the library's description, and part of the id: change a recipe and every library built
 before is stale.
 
-`python bevy_gaussian_splatting_amd/_build_id.py [libbgs | libbgs_query | libbgs_sparse]` prints a library's hash (libbgs's by
+`python bevy_gaussian_splatting_amd/_build_id.py [libbgs | libbgs_query | libbgs_sparse | libbgs_slice]` prints a library's hash (libbgs's by
 default). Standard library only and no relative import: the Makefiles run it as a plain script, and
 scripts/build_*_variant.sh copy this one file next to a bare csrc/."""
 from __future__ import annotations
@@ -48,6 +48,10 @@ LIBBGS_QUERY = NativeLibrary("libbgs_query", os.path.join(_HERE, "csrc_query"), 
 LIBBGS_SPARSE = NativeLibrary("libbgs_sparse", os.path.join(_HERE, "csrc_sparse"), b"BGSS_BUILD_ID=", (".hip", ".h", ".map"),
                               hashed_elsewhere=(("bgs_sparse.h", os.path.join("..", "..", "include", "bgs_sparse.h")),))
 LIBRARIES = {spec.name: spec for spec in (LIBBGS, LIBBGS_QUERY, LIBBGS_SPARSE)}
+# The time slice of a 4D cloud (include/bgs_slice.h). Kept beside the table of the three, not in it.
+LIBBGS_SLICE = NativeLibrary("libbgs_slice", os.path.join(_HERE, "csrc_slice"), b"BGST_BUILD_ID=", (".hip", ".h", ".map"),
+                             hashed_elsewhere=(("bgs_slice.h", os.path.join("..", "..", "include", "bgs_slice.h")),))
+BY_NAME = {**LIBRARIES, LIBBGS_SLICE.name: LIBBGS_SLICE}   # what this file's argument may name
 MARKER = LIBBGS.marker
 
 
@@ -85,4 +89,4 @@ def library_build_id(path: str, spec: NativeLibrary = LIBBGS) -> Optional[str]:
 
 
 if __name__ == "__main__":
-    print(source_sha256(LIBRARIES[sys.argv[1]] if len(sys.argv) > 1 else LIBBGS))
+    print(source_sha256(BY_NAME[sys.argv[1]] if len(sys.argv) > 1 else LIBBGS))

@@ -283,6 +283,60 @@ def trained_like_gaussians_3d_seeded(n: int, seed: int, patches: int = 96) -> Pl
     return PlanarGaussian3d(pv, sh, rot.astype(np.float32), so)
 
 
+SH_4D_COEFF_COUNT = 3 * SH_COEFF_COUNT  # 144: the static group, then the cos(2 pi theta) and the cos(4 pi theta) group
+
+
+class PlanarGaussian4d:
+    """Planar (SoA) time-conditioned cloud: five planes of `n` rows (the `Planar` derive of `Gaussian4d`,
+    src/gaussian/formats/planar_4d.rs:23-51): position_visibility [n, 4], spherindrical_harmonic [n, 144],
+    isotropic_rotations [n, 8] = (w, x, y, z, wr, xr, yr, zr), scale_opacity [n, 4] and timestamp_timescale [n, 4] =
+    (timestamp, time_scale, 0, 0). It is drawn through its time slice (time_slice.py, plugin.slice_4d)."""
+
+    def __init__(self, position_visibility, spherindrical_harmonic, isotropic_rotations, scale_opacity, timestamp_timescale):
+        n = len(position_visibility)
+        self.position_visibility = _f32(position_visibility, (n, 4))
+        self.spherindrical_harmonic = _f32(spherindrical_harmonic, (n, SH_4D_COEFF_COUNT))
+        self.isotropic_rotations = _f32(isotropic_rotations, (n, 8))
+        self.scale_opacity = _f32(scale_opacity, (n, 4))
+        self.timestamp_timescale = _f32(timestamp_timescale, (n, 4))
+
+    def __len__(self) -> int:
+        return self.position_visibility.shape[0]
+
+    def planes(self):
+        """The five planes in the order of `Gaussian4d`'s fields, which is the order `bgst_slice` takes them in."""
+        return (self.position_visibility, self.spherindrical_harmonic, self.isotropic_rotations, self.scale_opacity,
+                self.timestamp_timescale)
+
+    def nbytes(self) -> int:
+        return sum(p.nbytes for p in self.planes())
+
+    def slice(self, start: int, stop: int) -> "PlanarGaussian4d":
+        return PlanarGaussian4d(*(p[start:stop] for p in self.planes()))
+
+
+def random_gaussians_4d_seeded(n: int, seed: int) -> PlanarGaussian4d:
+    """Seeded synthetic 4D cloud with the reference's distributions (src/gaussian/formats/planar_4d.rs:245-288):
+    coefficients ~ U(-1, 1)^144, both rotations ~ U(-1, 1)^4 (NOT normalised), position ~ U(-20, 20)^3 with visibility 1,
+    scale ~ U(0, 1)^3, opacity ~ U(0, 0.8), timestamp ~ U(0, 1), time_scale ~ U(-1, 1).
+
+    As for `random_gaussians_3d_seeded`, the reference's `rand::StdRng` stream is not reproduced: numpy PCG64 with the
+    same per-field order gives clouds of the same statistics, not the same bits."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    sh = rng.uniform(-1.0, 1.0, size=(n, SH_4D_COEFF_COUNT)).astype(np.float32)
+    rot = rng.uniform(-1.0, 1.0, size=(n, 8)).astype(np.float32)
+    pv = np.empty((n, 4), np.float32)
+    pv[:, :3] = rng.uniform(-20.0, 20.0, size=(n, 3)).astype(np.float32)
+    pv[:, 3] = 1.0
+    so = np.empty((n, 4), np.float32)
+    so[:, :3] = rng.uniform(0.0, 1.0, size=(n, 3)).astype(np.float32)
+    so[:, 3] = rng.uniform(0.0, 0.8, size=n).astype(np.float32)
+    tt = np.zeros((n, 4), np.float32)
+    tt[:, 0] = rng.uniform(0.0, 1.0, size=n).astype(np.float32)
+    tt[:, 1] = rng.uniform(-1.0, 1.0, size=n).astype(np.float32)
+    return PlanarGaussian4d(pv, sh, rot, so, tt)
+
+
 def random_gaussians_3d(n: int) -> PlanarGaussian3d:
     """src/gaussian/formats/planar_3d.rs:171-180 (thread RNG -> OS entropy seed)."""
     return random_gaussians_3d_seeded(n, int(np.random.SeedSequence().entropy % (1 << 63)))

@@ -20,7 +20,7 @@ import numpy as np
 
 from . import _native
 from .camera import View
-from .gaussian import PlanarGaussian3d, PlanarGaussian3dF16
+from .gaussian import PlanarGaussian3d, PlanarGaussian3dF16, PlanarGaussian4d
 from .particles import PARTICLE_BEHAVIOR_DTYPE, ParticleBehaviors, ParticleBehaviorsHandle
 from .settings import CloudSettings
 from .sparse_select import SparseSelect, selected_indices
@@ -253,6 +253,53 @@ class GaussianSplattingPlugin:
         else:
             raise TypeError("cloud must be PlanarGaussian3d or PlanarGaussian3dF16")
         return PlanarGaussian3dHandle(self, out, n, fmt, cloud.nbytes())
+
+    def upload_covariance_planes(self, position_visibility, spherical_harmonic, covariance_3d_opacity) -> PlanarGaussian3dHandle:
+        """The sibling of `upload(..., precompute_covariance_3d=True)` for a covariance plane that is already made:
+        [n, 4], [n, 48] and [n, 8] float32 (`Covariance3dOpacity`: xx, xy, xz, yy, yz, zz, opacity, pad) go up as they
+        are (`bgs_cloud_upload_cov3d_f32`). Returns a handle of format "cov3d"."""
+        pv = np.ascontiguousarray(position_visibility, np.float32)
+        sh = np.ascontiguousarray(spherical_harmonic, np.float32)
+        cov = np.ascontiguousarray(covariance_3d_opacity, np.float32)
+        n = pv.shape[0]
+        if pv.shape != (n, 4) or sh.shape != (n, 48) or cov.shape != (n, 8):
+            raise ValueError("expected planes of shape [n, 4], [n, 48] and [n, 8]")
+        out = ctypes.c_void_p()
+        self._check(self._lib.bgs_cloud_upload_cov3d_f32(self._ctx, n, _fptr(pv), _fptr(sh), _fptr(cov), ctypes.byref(out)))
+        return PlanarGaussian3dHandle(self, out, n, "cov3d", n * (16 + 192 + 32))
+
+    # -- 4D clouds (src/render/gaussian_4d.wgsl; libbgs_slice.so) ----------------------
+    def slice_4d(self, cloud4d: PlanarGaussian4d, settings: CloudSettings, slicer=None, return_planes: bool = False):
+        """The 4D cloud at `settings.time` as a resident 3D cloud of format "cov3d": the five planes go into device
+        memory, `bgst_slice` runs on `bgs_stream` (`time_slice.TimeSlicer`; global_scale, time_start and time_stop are
+        read too), and the three planes of the slice come back to the host and go up again through
+        `bgs_cloud_upload_cov3d_f32`. The round trip is there because libbgs has no entry point that takes planes by
+        device address (include/bgs_slice.h "ORDERING"). Sort and render the handle with any
+        settings of the precomputed-covariance path, which reads neither `time` nor `global_scale`; free it before the
+        next time's slice replaces it. With `return_planes` also the three host planes."""
+        from .time_slice import TimeSlicer
+        if not isinstance(cloud4d, PlanarGaussian4d):
+            raise TypeError("cloud4d must be a PlanarGaussian4d")
+        slicer = slicer or TimeSlicer(self.device)
+        n = len(cloud4d)
+        outs = [np.zeros((n, w), np.float32) for w in (4, 48, 8)]
+        if n:
+            self.synchronize()
+            ptrs = []
+            try:
+                for plane in cloud4d.planes() + tuple(outs):
+                    ptrs.append(self.device_alloc(plane.nbytes))
+                for ptr, plane in zip(ptrs[:5], cloud4d.planes()):
+                    self.upload_bytes(ptr, plane)
+                slicer.slice(self.stream_handle(), n, ptrs[:5], ptrs[5:], settings)
+                self.synchronize()
+                for ptr, plane in zip(ptrs[5:], outs):
+                    self.download(ptr, plane)
+            finally:
+                for ptr in ptrs:
+                    self.device_free(ptr)
+        handle = self.upload_covariance_planes(*outs)
+        return (handle, tuple(outs)) if return_planes else handle
 
     # -- particle behaviours (src/morph/particle.rs) -----------------------------------
     def upload_particle_behaviors(self, behaviors) -> ParticleBehaviorsHandle:
