@@ -60,6 +60,11 @@ from .time_slice import (
     slice_float64,
     slice_reference,
 )
+from .interpolate import (
+    GaussianInterpolator,
+    interpolate_reference,
+    interpolation_factor,
+)
 from .plugin import (
     DeviceEntriesChunk,
     DeviceSortedEntries,
@@ -82,4 +87,5 @@ __all__ = [
     "MeshQuery", "TriangleMesh", "crossings_reference", "cube_mesh", "icosphere_mesh", "mesh_from_points",
     "SparseGrid", "SparseSelect", "neighbor_counts_reference", "select_reference",
     "PlanarGaussian4d", "random_gaussians_4d_seeded", "TimeSlicer", "slice_float64", "slice_reference",
+    "GaussianInterpolator", "interpolate_reference", "interpolation_factor",
 ]

@@ -10,7 +10,7 @@ that also changes with every documentation commit.
 What a hash covers is data of the library's description, and part of the id: change a recipe and every library built
 before is stale.
 
-`python bevy_gaussian_splatting_amd/_build_id.py [libbgs | libbgs_query | libbgs_sparse | libbgs_slice]` prints a library's hash (libbgs's by
+`python bevy_gaussian_splatting_amd/_build_id.py [libbgs | libbgs_query | libbgs_sparse | libbgs_slice | libbgs_morph]` prints a library's hash (libbgs's by
 default). Standard library only and no relative import: the Makefiles run it as a plain script, and
 scripts/build_*_variant.sh copy this one file next to a bare csrc/."""
 from __future__ import annotations
@@ -51,7 +51,10 @@ LIBRARIES = {spec.name: spec for spec in (LIBBGS, LIBBGS_QUERY, LIBBGS_SPARSE)}
 # The time slice of a 4D cloud (include/bgs_slice.h). Kept beside the table of the three, not in it.
 LIBBGS_SLICE = NativeLibrary("libbgs_slice", os.path.join(_HERE, "csrc_slice"), b"BGST_BUILD_ID=", (".hip", ".h", ".map"),
                              hashed_elsewhere=(("bgs_slice.h", os.path.join("..", "..", "include", "bgs_slice.h")),))
-BY_NAME = {**LIBRARIES, LIBBGS_SLICE.name: LIBBGS_SLICE}   # what this file's argument may name
+# The morph between two clouds (include/bgs_morph.h). Beside the table as well.
+LIBBGS_MORPH = NativeLibrary("libbgs_morph", os.path.join(_HERE, "csrc_morph"), b"BGSM_BUILD_ID=", (".hip", ".h", ".map"),
+                             hashed_elsewhere=(("bgs_morph.h", os.path.join("..", "..", "include", "bgs_morph.h")),))
+BY_NAME = {**LIBRARIES, LIBBGS_SLICE.name: LIBBGS_SLICE, LIBBGS_MORPH.name: LIBBGS_MORPH}   # what this file's argument may name
 MARKER = LIBBGS.marker
 
 

@@ -1,4 +1,4 @@
-"""What the bindings of the native libraries (`_native`, `_native_query`, `_native_sparse`, `_native_slice`) share: a library on disk is the one built
+"""What the bindings of the native libraries (`_native`, `_native_query`, `_native_sparse`, `_native_slice`, `_native_morph`) share: a library on disk is the one built
 from this tree's sources (`_build_id`) or it is rebuilt, one builder at a time; failing that it is refused. And the
 prototypes of a loaded library come from one table. There is no CPU fallback."""
 from __future__ import annotations

@@ -175,6 +175,68 @@ class PlanarGaussian3dHandle:
         self._ptr = None
 
 
+class MorphPair:
+    """The two sides of a morph (`GaussianInterpolate { lhs, rhs }`) and the output's planes, kept in device memory
+    across calls; made by `GaussianSplattingPlugin.morph_pair`. `at(settings)` runs the blend on `bgs_stream`
+    (libbgs_morph.so), downloads the output and returns it as a resident cloud."""
+
+    def __init__(self, plugin: "GaussianSplattingPlugin", lhs: PlanarGaussian3d, rhs: PlanarGaussian3d,
+                 precompute_covariance_3d: bool = False, interpolator=None):
+        from .interpolate import COV3D_WIDTHS, F32_WIDTHS, GaussianInterpolator, covariance_planes, planes_of
+        if not isinstance(lhs, PlanarGaussian3d) or not isinstance(rhs, PlanarGaussian3d):
+            raise TypeError("lhs and rhs must be f32 PlanarGaussian3d")
+        if len(lhs) != len(rhs):
+            raise ValueError(f"lhs has {len(lhs)} splats, rhs {len(rhs)}: a morph needs two clouds of equal length")
+        self._plugin = plugin
+        self._interpolator = interpolator or GaussianInterpolator(plugin.device)
+        self.n = len(lhs)
+        self.precompute_covariance_3d = bool(precompute_covariance_3d)
+        self._widths = COV3D_WIDTHS if precompute_covariance_3d else F32_WIDTHS
+        sides = [planes_of(covariance_planes(c) if precompute_covariance_3d else c) for c in (lhs, rhs)]
+        self._ptrs = []                      # the lhs's planes, the rhs's, the output's
+        if self.n:
+            try:
+                for plane in sides[0] + sides[1]:
+                    self._ptrs.append(plugin.device_alloc(plane.nbytes))
+                    plugin.upload_bytes(self._ptrs[-1], plane)
+                for w in self._widths:
+                    self._ptrs.append(plugin.device_alloc(self.n * w * 4))
+            except BaseException:
+                self.free()
+                raise
+
+    def __len__(self) -> int:
+        return self.n
+
+    def at(self, settings: CloudSettings, return_planes: bool = False):
+        """The output cloud at `settings.time` (time_start and time_stop are read as well) as a resident handle, of
+        format "cov3d" for a pair made with `precompute_covariance_3d`. With `return_planes` also its host planes."""
+        plugin, k = self._plugin, len(self._widths)
+        outs = [np.zeros((self.n, w), np.float32) for w in self._widths]
+        if self.n:
+            if not self._ptrs:
+                raise RuntimeError("this MorphPair was freed")
+            plugin.synchronize()
+            self._interpolator.interpolate(plugin.stream_handle(), self.n, self._ptrs[:k], self._ptrs[k:2 * k], self._ptrs[2 * k:], settings)
+            plugin.synchronize()
+            for ptr, plane in zip(self._ptrs[2 * k:], outs):
+                plugin.download(ptr, plane)
+        handle = plugin.upload_covariance_planes(*outs) if self.precompute_covariance_3d else plugin.upload(PlanarGaussian3d(*outs))
+        return (handle, tuple(outs)) if return_planes else handle
+
+    def free(self) -> None:
+        ptrs, self._ptrs = self._ptrs, []
+        if self._plugin._ctx is not None:
+            for ptr in ptrs:
+                self._plugin.device_free(ptr)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+
 def _fptr(a: np.ndarray):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
 
@@ -300,6 +362,27 @@ class GaussianSplattingPlugin:
                     self.device_free(ptr)
         handle = self.upload_covariance_planes(*outs)
         return (handle, tuple(outs)) if return_planes else handle
+
+    # -- morph between two clouds (src/morph/interpolate.wgsl; libbgs_morph.so) ---------
+    def morph_pair(self, lhs: PlanarGaussian3d, rhs: PlanarGaussian3d, precompute_covariance_3d: bool = False,
+                   interpolator=None) -> "MorphPair":
+        """Both sides of a `GaussianInterpolate` made resident once: a `MorphPair` whose `.at(settings)` does only the
+        kernel, the download and the upload. A host that scrubs `time` uploads each side once. Free it (`.free()`, or
+        use it as a context manager) when the morph ends."""
+        return MorphPair(self, lhs, rhs, precompute_covariance_3d, interpolator)
+
+    def interpolate(self, lhs: PlanarGaussian3d, rhs: PlanarGaussian3d, settings: CloudSettings,
+                    precompute_covariance_3d: bool = False, interpolator=None, return_planes: bool = False):
+        """The blend of two clouds of equal length at `settings.time` between `time_start` and `time_stop` as a resident
+        cloud (the reference's `GaussianInterpolate { lhs, rhs }`): both sides' planes go into device memory,
+        `bgsm_interpolate_f32` runs on `bgs_stream` (`interpolate.GaussianInterpolator`), and the output's planes come
+        back to the host and go up again through `bgs_cloud_upload_f32`. With `precompute_covariance_3d` the two clouds'
+        `Covariance3dOpacity` planes are blended instead of rotation and scale (`bgsm_interpolate_cov3d_f32`) and the
+        handle is of format "cov3d". The round trip is there because libbgs has no entry point that takes planes by
+        device address (include/bgs_morph.h "ORDERING"). Free the handle before the next
+        time's morph replaces it. With `return_planes` also the output's host planes."""
+        with self.morph_pair(lhs, rhs, precompute_covariance_3d, interpolator) as pair:
+            return pair.at(settings, return_planes=return_planes)
 
     # -- particle behaviours (src/morph/particle.rs) -----------------------------------
     def upload_particle_behaviors(self, behaviors) -> ParticleBehaviorsHandle:
