@@ -10,8 +10,11 @@ that also changes with every documentation commit.
 What a hash covers is data of the library's description, and part of the id: change a recipe and every library built
 before is stale.
 
-`python bevy_gaussian_splatting_amd/_build_id.py [libbgs | libbgs_query | libbgs_sparse | libbgs_slice | libbgs_morph]` prints a library's hash (libbgs's by
-default). Standard library only and no relative import: the Makefiles run it as a plain script, and
+`LIBRARIES` is the one table of them, in build order: libbgs, then the four small libraries, whose specs come from one
+constructor and whose hashes also cover what they share (small_lib/). A further library is one more line there.
+
+`python bevy_gaussian_splatting_amd/_build_id.py [NAME]` prints the hash of the library of `LIBRARIES` so named (libbgs's
+by default). Standard library only and no relative import: the Makefiles run it as a plain script, and
 scripts/build_*_variant.sh copy this one file next to a bare csrc/."""
 from __future__ import annotations
 
@@ -43,18 +46,22 @@ class NativeLibrary:
 # is no source. libbgs's recipe leaves out libbgs.map and include/bgs*.h, and stays so: adding them would move its id.
 LIBBGS = NativeLibrary("libbgs", os.path.join(_HERE, "csrc"), b"BGS_BUILD_ID=", (".hip", ".h"),
                        make_args=("-j4",), dlopen_mode=os.RTLD_GLOBAL)
-LIBBGS_QUERY = NativeLibrary("libbgs_query", os.path.join(_HERE, "csrc_query"), b"BGSQ_BUILD_ID=", (".hip", ".h", ".map"),
-                             hashed_elsewhere=(("bgs_query.h", os.path.join("..", "..", "include", "bgs_query.h")),))
-LIBBGS_SPARSE = NativeLibrary("libbgs_sparse", os.path.join(_HERE, "csrc_sparse"), b"BGSS_BUILD_ID=", (".hip", ".h", ".map"),
-                              hashed_elsewhere=(("bgs_sparse.h", os.path.join("..", "..", "include", "bgs_sparse.h")),))
-LIBRARIES = {spec.name: spec for spec in (LIBBGS, LIBBGS_QUERY, LIBBGS_SPARSE)}
-# The time slice of a 4D cloud (include/bgs_slice.h). Kept beside the table of the three, not in it.
-LIBBGS_SLICE = NativeLibrary("libbgs_slice", os.path.join(_HERE, "csrc_slice"), b"BGST_BUILD_ID=", (".hip", ".h", ".map"),
-                             hashed_elsewhere=(("bgs_slice.h", os.path.join("..", "..", "include", "bgs_slice.h")),))
-# The morph between two clouds (include/bgs_morph.h). Beside the table as well.
-LIBBGS_MORPH = NativeLibrary("libbgs_morph", os.path.join(_HERE, "csrc_morph"), b"BGSM_BUILD_ID=", (".hip", ".h", ".map"),
-                             hashed_elsewhere=(("bgs_morph.h", os.path.join("..", "..", "include", "bgs_morph.h")),))
-BY_NAME = {**LIBRARIES, LIBBGS_SLICE.name: LIBBGS_SLICE, LIBBGS_MORPH.name: LIBBGS_MORPH}   # what this file's argument may name
+
+
+def _small_library(name: str, directory: str, marker: bytes, header: str) -> NativeLibrary:
+    """A small device library: its own directory with its map file, its public header under include/, then what all of
+    them are built with (small_lib/: the API support headers and the Makefile recipe, where the compiler flags are)."""
+    elsewhere = [(header, os.path.join("..", "..", "include", header))]
+    elsewhere += [(shared, os.path.join("..", "small_lib", shared)) for shared in ("api_support.h", "api_support_hip.h", "library.mk")]
+    return NativeLibrary(name, os.path.join(_HERE, directory), marker, (".hip", ".h", ".map"), hashed_elsewhere=tuple(elsewhere))
+
+
+LIBBGS_QUERY = _small_library("libbgs_query", "csrc_query", b"BGSQ_BUILD_ID=", "bgs_query.h")     # point-in-mesh selection
+LIBBGS_SPARSE = _small_library("libbgs_sparse", "csrc_sparse", b"BGSS_BUILD_ID=", "bgs_sparse.h")  # sparse-splat selection
+LIBBGS_SLICE = _small_library("libbgs_slice", "csrc_slice", b"BGST_BUILD_ID=", "bgs_slice.h")      # the time slice of a 4D cloud
+LIBBGS_MORPH = _small_library("libbgs_morph", "csrc_morph", b"BGSM_BUILD_ID=", "bgs_morph.h")      # the morph between two clouds
+# Every native library, in build order; this file's argument names one of them.
+LIBRARIES = {spec.name: spec for spec in (LIBBGS, LIBBGS_QUERY, LIBBGS_SPARSE, LIBBGS_SLICE, LIBBGS_MORPH)}
 MARKER = LIBBGS.marker
 
 
@@ -92,4 +99,4 @@ def library_build_id(path: str, spec: NativeLibrary = LIBBGS) -> Optional[str]:
 
 
 if __name__ == "__main__":
-    print(source_sha256(BY_NAME[sys.argv[1]] if len(sys.argv) > 1 else LIBBGS))
+    print(source_sha256(LIBRARIES[sys.argv[1]] if len(sys.argv) > 1 else LIBBGS))

@@ -1,13 +1,15 @@
-"""What the bindings of the native libraries (`_native`, `_native_query`, `_native_sparse`, `_native_slice`, `_native_morph`) share: a library on disk is the one built
-from this tree's sources (`_build_id`) or it is rebuilt, one builder at a time; failing that it is refused. And the
-prototypes of a loaded library come from one table. There is no CPU fallback."""
+"""What the bindings of the native libraries (`_native` and the `_native_*` of the small libraries) share: a library on
+disk is the one built from this tree's sources (`_build_id`) or it is rebuilt, one builder at a time; failing that it is
+refused. The prototypes of a loaded library come from one table. And a small library's binding opens its library with
+`open_library` and turns a status into its exception with `check_status`: what is left in the binding is the table, the
+constants and the error class. There is no CPU fallback."""
 from __future__ import annotations
 
 import ctypes
 import fcntl
 import os
 import subprocess
-from typing import Iterable, Optional, Sequence, Tuple
+from typing import Callable, Iterable, Optional, Sequence, Tuple
 
 from . import _build_id
 from ._build_id import NativeLibrary
@@ -59,3 +61,22 @@ def declare(lib: ctypes.CDLL, prototypes: Iterable[Prototype]) -> None:
         fn = getattr(lib, name)
         fn.restype = restype
         fn.argtypes = list(argtypes)
+
+
+def open_library(spec: NativeLibrary, path: str, prototypes: Sequence[Prototype], version_function: str, abi_version: int) -> ctypes.CDLL:
+    """A small library's `load()`: the library at `path` is made current, opened, given its prototypes, and asked for the
+    version of its ABI, which must be the one the binding was written against."""
+    ensure_current(spec, path)
+    lib = ctypes.CDLL(path, mode=spec.dlopen_mode)
+    declare(lib, prototypes)
+    version = getattr(lib, version_function)()
+    if version != abi_version:
+        raise ImportError(f"{spec.name}.so is version {version:#x}, this binding was written against {abi_version:#x}")
+    return lib
+
+
+def check_status(status: int, last_error: Callable[[], Optional[bytes]], error_class: type) -> None:
+    """A small library's `check()`: a status other than 0 is raised as `error_class(status, the library's last error)`."""
+    if status != 0:
+        msg = last_error()
+        raise error_class(status, msg.decode("utf-8", "replace") if msg else "")

@@ -1,7 +1,7 @@
 """ctypes binding of libbgs.so (the C ABI in include/bgs.h and include/bgs_diag.h).
 
 What is specific to this library: its status codes, structs, prototype table and ABI handshake. How the library on
-disk is kept the one built from this tree's sources is `_loader` + `_build_id`, shared with `_native_query`.
+disk is kept the one built from this tree's sources is `_loader` + `_build_id`, shared with the bindings of the small libraries.
 `__graft_entry__.build()` (or `make -C bevy_gaussian_splatting_amd/csrc`) builds it in-tree. There is no CPU fallback:
 if the library is missing, or no HIP device is usable, every entry point of the package raises.
 """

@@ -53,18 +53,10 @@ def load() -> ctypes.CDLL:
     """Load libbgs_query.so once and declare prototypes. Raises if it is not built from this tree's sources and cannot
     be rebuilt."""
     global _lib
-    if _lib is not None:
-        return _lib
-    _loader.ensure_current(SPEC, LIB_PATH)
-    lib = ctypes.CDLL(LIB_PATH, mode=SPEC.dlopen_mode)
-    _loader.declare(lib, PROTOTYPES)
-    if lib.bgsq_version() != ABI_VERSION:
-        raise ImportError(f"libbgs_query.so is version {lib.bgsq_version():#x}, this binding was written against {ABI_VERSION:#x}")
-    _lib = lib
-    return lib
+    if _lib is None:
+        _lib = _loader.open_library(SPEC, LIB_PATH, PROTOTYPES, "bgsq_version", ABI_VERSION)
+    return _lib
 
 
 def check(lib: ctypes.CDLL, status: int) -> None:
-    if status != BGSQ_OK:
-        msg = lib.bgsq_last_error()
-        raise BgsQueryError(status, msg.decode("utf-8", "replace") if msg else "")
+    _loader.check_status(status, lib.bgsq_last_error, BgsQueryError)

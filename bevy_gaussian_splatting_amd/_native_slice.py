@@ -24,7 +24,7 @@ ABI_VERSION = (0 << 16) | 1
 vp, u32 = ctypes.c_void_p, ctypes.c_uint32
 
 # Every function include/bgs_slice.h declares, in its order: (name, restype, argtypes). Held against the header by
-# tests/test_time_slice_host.py (names, order, parameter counts, return types).
+# tests/test_native_binding.py (names, order, parameter counts, return types).
 PROTOTYPES = (
     ("bgst_version", u32, ()),
     ("bgst_last_error", c_char_p, ()),
@@ -46,18 +46,10 @@ def load() -> ctypes.CDLL:
     """Load libbgs_slice.so once and declare prototypes. Raises if it is not built from this tree's sources and cannot
     be rebuilt."""
     global _lib
-    if _lib is not None:
-        return _lib
-    _loader.ensure_current(SPEC, LIB_PATH)
-    lib = ctypes.CDLL(LIB_PATH, mode=SPEC.dlopen_mode)
-    _loader.declare(lib, PROTOTYPES)
-    if lib.bgst_version() != ABI_VERSION:
-        raise ImportError(f"libbgs_slice.so is version {lib.bgst_version():#x}, this binding was written against {ABI_VERSION:#x}")
-    _lib = lib
-    return lib
+    if _lib is None:
+        _lib = _loader.open_library(SPEC, LIB_PATH, PROTOTYPES, "bgst_version", ABI_VERSION)
+    return _lib
 
 
 def check(lib: ctypes.CDLL, status: int) -> None:
-    if status != BGST_OK:
-        msg = lib.bgst_last_error()
-        raise BgsSliceError(status, msg.decode("utf-8", "replace") if msg else "")
+    _loader.check_status(status, lib.bgst_last_error, BgsSliceError)

@@ -1,51 +1,18 @@
 // bgs_morph_api.hip — the C ABI of libbgs_morph.so (include/bgs_morph.h) over the launcher of morph_kernels.hip.
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 #include "../../include/bgs_morph.h"
 #include "build_id.inc"
 #include "morph_kernels.h"
+#include "../small_lib/api_support_hip.h"
 
 // The SHA-256 of the sources this library was compiled from (../_build_id.py libbgs_morph), readable from the
 // file's bytes: the loader rebuilds a library that carries another one.
 extern "C" __attribute__((used, visibility("hidden"))) const char bgsm_build_id_marker[] = "BGSM_BUILD_ID=" BGSM_BUILD_ID;
 
+static_assert(BGSM_EINVAL == API_EINVAL && BGSM_ENOMEM == API_ENOMEM && BGSM_EHIP == API_EHIP, "the shared support's status codes");
+
 namespace {
-
-thread_local char g_error[512] = "";
-
-int fail(int status, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_error, sizeof g_error, fmt, ap);
-    va_end(ap);
-    return status;
-}
-
-int fail_hip(const char* what, hipError_t e) { return fail(BGSM_EHIP, "%s: %s", what, hipGetErrorString(e)); }
-
-// Makes `device` current for the calling thread and puts the previous one back: the host's own choice is not disturbed.
-class DeviceScope {
-  public:
-    explicit DeviceScope(int device) {
-        if (hipGetDevice(&previous_) != hipSuccess) previous_ = -1;
-        status_ = hipSetDevice(device);
-    }
-    ~DeviceScope() {
-        if (status_ == hipSuccess && previous_ >= 0) (void)hipSetDevice(previous_);
-    }
-    hipError_t status() const { return status_; }
-
-  private:
-    int previous_ = -1;
-    hipError_t status_ = hipSuccess;
-};
-
-struct Named {
-    const char* name;
-    const void* ptr;
-};
 
 // Both entry points: `planes` holds the lhs's planes, then the rhs's, then the output's, `per_side` each. Everything is
 // validated before a device is touched.
@@ -58,17 +25,8 @@ int interpolate(const char* fn, bool covariance, int hip_device, void* hip_strea
         if (!isfinite(values[k])) return fail(BGSM_EINVAL, "%s: %s %g must be finite", fn, names[k], (double)values[k]);
     if (n == 0u) return BGSM_OK;
     const int inputs = 2 * per_side, count = 3 * per_side;
-    for (int k = 0; k < count; ++k) {
-        if (!planes[k].ptr) return fail(BGSM_EINVAL, "%s: %s is NULL", fn, planes[k].name);
-        if ((uintptr_t)planes[k].ptr & 15u) return fail(BGSM_EINVAL, "%s: %s must be a 16-byte aligned device address", fn, planes[k].name);
-    }
-    for (int o = inputs; o < count; ++o)
-        for (int k = 0; k < o; ++k)
-            if (planes[o].ptr == planes[k].ptr) return fail(BGSM_EINVAL, "%s: %s is %s as well", fn, planes[o].name, planes[k].name);
-    if (hip_device < 0) return fail(BGSM_EINVAL, "%s: hip_device %d", fn, hip_device);
-    int devices = 0;
-    if (hipGetDeviceCount(&devices) != hipSuccess || hip_device >= devices)
-        return fail(BGSM_EHIP, "%s: no usable HIP device %d (%d visible)", fn, hip_device, devices);
+    if (const int refused = check_planes(fn, planes, inputs, count)) return refused;
+    if (const int refused = check_device(fn, hip_device)) return refused;
     DeviceScope scope(hip_device);
     if (scope.status() != hipSuccess) return fail_hip("hipSetDevice", scope.status());
     bgsm::MorphSide side[2];

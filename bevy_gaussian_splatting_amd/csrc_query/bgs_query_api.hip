@@ -1,17 +1,18 @@
 // bgs_query_api.hip — the C ABI of libbgs_query.so (include/bgs_query.h) over the launchers of mesh_query_kernels.hip.
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 #include <new>
 
 #include "../../include/bgs_query.h"
 #include "build_id.inc"
 #include "mesh_query_kernels.h"
+#include "../small_lib/api_support_hip.h"
 
 // The SHA-256 of the sources this library was compiled from (../_build_id.py libbgs_query), readable from the
 // file's bytes: the loader rebuilds a library that carries another one.
 extern "C" __attribute__((used, visibility("hidden"))) const char bgsq_build_id_marker[] = "BGSQ_BUILD_ID=" BGSQ_BUILD_ID;
+
+static_assert(BGSQ_EINVAL == API_EINVAL && BGSQ_ENOMEM == API_ENOMEM && BGSQ_EHIP == API_EHIP, "the shared support's status codes");
 
 struct bgsq_mesh {
     int device = 0;
@@ -22,35 +23,6 @@ struct bgsq_mesh {
 };
 
 namespace {
-
-thread_local char g_error[512] = "";
-
-int fail(int status, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_error, sizeof g_error, fmt, ap);
-    va_end(ap);
-    return status;
-}
-
-int fail_hip(const char* what, hipError_t e) { return fail(BGSQ_EHIP, "%s: %s", what, hipGetErrorString(e)); }
-
-// Makes `device` current for the calling thread and puts the previous one back: the host's own choice is not disturbed.
-class DeviceScope {
-  public:
-    explicit DeviceScope(int device) {
-        if (hipGetDevice(&previous_) != hipSuccess) previous_ = -1;
-        status_ = hipSetDevice(device);
-    }
-    ~DeviceScope() {
-        if (status_ == hipSuccess && previous_ >= 0) (void)hipSetDevice(previous_);
-    }
-    hipError_t status() const { return status_; }
-
-  private:
-    int previous_ = -1;
-    hipError_t status_ = hipSuccess;
-};
 
 // Enough workgroups to give every compute unit two: below that, the triangle list is cut into slices.
 uint32_t automatic_slices(const bgsq_mesh& m, uint32_t n) {
@@ -86,10 +58,7 @@ int bgsq_mesh_create(int hip_device, const float* vertices_xyz, uint32_t vertex_
         if (indices[k] >= vertex_count)
             return fail(BGSQ_EINVAL, "bgsq_mesh_create: triangle %llu names vertex %u, the mesh has %u", (unsigned long long)(k / 3u),
                         indices[k], vertex_count);
-    if (hip_device < 0) return fail(BGSQ_EINVAL, "bgsq_mesh_create: hip_device %d", hip_device);
-    int devices = 0;
-    if (hipGetDeviceCount(&devices) != hipSuccess || hip_device >= devices)
-        return fail(BGSQ_EHIP, "bgsq_mesh_create: no usable HIP device %d (%d visible)", hip_device, devices);
+    if (const int refused = check_device("bgsq_mesh_create", hip_device)) return refused;
     DeviceScope scope(hip_device);
     if (scope.status() != hipSuccess) return fail_hip("hipSetDevice", scope.status());
 

@@ -1,53 +1,16 @@
 // bgs_slice_api.hip — the C ABI of libbgs_slice.so (include/bgs_slice.h) over the launcher of slice_kernels.hip.
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 #include "../../include/bgs_slice.h"
 #include "build_id.inc"
 #include "slice_kernels.h"
+#include "../small_lib/api_support_hip.h"
 
 // The SHA-256 of the sources this library was compiled from (../_build_id.py libbgs_slice), readable from the
 // file's bytes: the loader rebuilds a library that carries another one.
 extern "C" __attribute__((used, visibility("hidden"))) const char bgst_build_id_marker[] = "BGST_BUILD_ID=" BGST_BUILD_ID;
 
-namespace {
-
-thread_local char g_error[512] = "";
-
-int fail(int status, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_error, sizeof g_error, fmt, ap);
-    va_end(ap);
-    return status;
-}
-
-int fail_hip(const char* what, hipError_t e) { return fail(BGST_EHIP, "%s: %s", what, hipGetErrorString(e)); }
-
-// Makes `device` current for the calling thread and puts the previous one back: the host's own choice is not disturbed.
-class DeviceScope {
-  public:
-    explicit DeviceScope(int device) {
-        if (hipGetDevice(&previous_) != hipSuccess) previous_ = -1;
-        status_ = hipSetDevice(device);
-    }
-    ~DeviceScope() {
-        if (status_ == hipSuccess && previous_ >= 0) (void)hipSetDevice(previous_);
-    }
-    hipError_t status() const { return status_; }
-
-  private:
-    int previous_ = -1;
-    hipError_t status_ = hipSuccess;
-};
-
-struct Named {
-    const char* name;
-    const void* ptr;
-};
-
-}  // namespace
+static_assert(BGST_EINVAL == API_EINVAL && BGST_ENOMEM == API_ENOMEM && BGST_EHIP == API_EHIP, "the shared support's status codes");
 
 extern "C" {
 
@@ -61,10 +24,10 @@ int bgst_slice(int hip_device, void* hip_stream, uint32_t n, const void* positio
                void* out_position_visibility_device_ptr, void* out_spherical_harmonic_device_ptr,
                void* out_covariance_3d_opacity_device_ptr, float global_scale, float time, float time_start, float time_stop) {
     g_error[0] = 0;
-    const Named settings[4] = {{"global_scale", nullptr}, {"time", nullptr}, {"time_start", nullptr}, {"time_stop", nullptr}};
+    const char* const names[4] = {"global_scale", "time", "time_start", "time_stop"};
     const float values[4] = {global_scale, time, time_start, time_stop};
     for (int k = 0; k < 4; ++k)
-        if (!isfinite(values[k])) return fail(BGST_EINVAL, "bgst_slice: %s %g must be finite", settings[k].name, (double)values[k]);
+        if (!isfinite(values[k])) return fail(BGST_EINVAL, "bgst_slice: %s %g must be finite", names[k], (double)values[k]);
     if (time_stop == time_start) return fail(BGST_EINVAL, "bgst_slice: time_stop == time_start (%g): the duration is 0", (double)time_start);
     if (n == 0u) return BGST_OK;
     const Named planes[8] = {{"position_visibility_device_ptr", position_visibility_device_ptr},
@@ -75,17 +38,8 @@ int bgst_slice(int hip_device, void* hip_stream, uint32_t n, const void* positio
                              {"out_position_visibility_device_ptr", out_position_visibility_device_ptr},
                              {"out_spherical_harmonic_device_ptr", out_spherical_harmonic_device_ptr},
                              {"out_covariance_3d_opacity_device_ptr", out_covariance_3d_opacity_device_ptr}};
-    for (int k = 0; k < 8; ++k) {
-        if (!planes[k].ptr) return fail(BGST_EINVAL, "bgst_slice: %s is NULL", planes[k].name);
-        if ((uintptr_t)planes[k].ptr & 15u) return fail(BGST_EINVAL, "bgst_slice: %s must be a 16-byte aligned device address", planes[k].name);
-    }
-    for (int o = 5; o < 8; ++o)
-        for (int k = 0; k < o; ++k)
-            if (planes[o].ptr == planes[k].ptr) return fail(BGST_EINVAL, "bgst_slice: %s is %s as well", planes[o].name, planes[k].name);
-    if (hip_device < 0) return fail(BGST_EINVAL, "bgst_slice: hip_device %d", hip_device);
-    int devices = 0;
-    if (hipGetDeviceCount(&devices) != hipSuccess || hip_device >= devices)
-        return fail(BGST_EHIP, "bgst_slice: no usable HIP device %d (%d visible)", hip_device, devices);
+    if (const int refused = check_planes("bgst_slice", planes, 5, 8)) return refused;
+    if (const int refused = check_device("bgst_slice", hip_device)) return refused;
     DeviceScope scope(hip_device);
     if (scope.status() != hipSuccess) return fail_hip("hipSetDevice", scope.status());
     const bgst::SlicePlanes p = {(const float4*)position_visibility_device_ptr, (const float4*)spherindrical_harmonic_device_ptr,

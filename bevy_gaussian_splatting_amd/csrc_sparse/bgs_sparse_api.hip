@@ -1,17 +1,18 @@
 // bgs_sparse_api.hip — the C ABI of libbgs_sparse.so (include/bgs_sparse.h) over the launchers of sparse_kernels.hip.
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 #include <new>
 
 #include "../../include/bgs_sparse.h"
 #include "build_id.inc"
 #include "sparse_kernels.h"
+#include "../small_lib/api_support_hip.h"
 
 // The SHA-256 of the sources this library was compiled from (../_build_id.py libbgs_sparse), readable from the
 // file's bytes: the loader rebuilds a library that carries another one.
 extern "C" __attribute__((used, visibility("hidden"))) const char bgss_build_id_marker[] = "BGSS_BUILD_ID=" BGSS_BUILD_ID;
+
+static_assert(BGSS_EINVAL == API_EINVAL && BGSS_ENOMEM == API_ENOMEM && BGSS_EHIP == API_EHIP, "the shared support's status codes");
 
 struct bgss_grid {
     int device = 0;
@@ -24,35 +25,6 @@ struct bgss_grid {
 namespace {
 
 constexpr uint32_t MIN_TABLE_BITS = 6, MAX_TABLE_BITS = 26;
-
-thread_local char g_error[512] = "";
-
-int fail(int status, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_error, sizeof g_error, fmt, ap);
-    va_end(ap);
-    return status;
-}
-
-int fail_hip(const char* what, hipError_t e) { return fail(BGSS_EHIP, "%s: %s", what, hipGetErrorString(e)); }
-
-// Makes `device` current for the calling thread and puts the previous one back: the host's own choice is not disturbed.
-class DeviceScope {
-  public:
-    explicit DeviceScope(int device) {
-        if (hipGetDevice(&previous_) != hipSuccess) previous_ = -1;
-        status_ = hipSetDevice(device);
-    }
-    ~DeviceScope() {
-        if (status_ == hipSuccess && previous_ >= 0) (void)hipSetDevice(previous_);
-    }
-    hipError_t status() const { return status_; }
-
-  private:
-    int previous_ = -1;
-    hipError_t status_ = hipSuccess;
-};
 
 // The smallest table with at least two slots a point: half of them stay empty, so a cell seldom shares its slot.
 uint32_t automatic_bits(uint32_t n) {
@@ -81,10 +53,7 @@ int bgss_grid_create(int hip_device, uint32_t max_points, bgss_grid** out) {
     g_error[0] = 0;
     if (!out) return fail(BGSS_EINVAL, "bgss_grid_create: out is NULL");
     *out = nullptr;
-    if (hip_device < 0) return fail(BGSS_EINVAL, "bgss_grid_create: hip_device %d", hip_device);
-    int devices = 0;
-    if (hipGetDeviceCount(&devices) != hipSuccess || hip_device >= devices)
-        return fail(BGSS_EHIP, "bgss_grid_create: no usable HIP device %d (%d visible)", hip_device, devices);
+    if (const int refused = check_device("bgss_grid_create", hip_device)) return refused;
     DeviceScope scope(hip_device);
     if (scope.status() != hipSuccess) return fail_hip("hipSetDevice", scope.status());
 
