@@ -25,11 +25,13 @@ from .settings import (
     DrawMode,
     GaussianColorSpace,
     GaussianMode,
+    PlaybackMode,
     RadixSortDepthBits,
     RasterizeMode,
     ShaderDefines,
     SortMode,
     compute_aabb,
+    playback_update,
 )
 from .io_ply import parse_ply_3d, write_ply_3d
 from .io_gcloud import decode_gcloud, encode_gcloud, read_gcloud, write_gcloud
@@ -69,7 +71,9 @@ from .plugin import (
     DeviceEntriesChunk,
     DeviceSortedEntries,
     GaussianSplattingPlugin,
+    MorphPair,
     PlanarGaussian3dHandle,
+    ResidentCloud4d,
     SortedEntries,
     SORT_ENTRY_DTYPE,
 )
@@ -88,4 +92,5 @@ __all__ = [
     "SparseGrid", "SparseSelect", "neighbor_counts_reference", "select_reference",
     "PlanarGaussian4d", "random_gaussians_4d_seeded", "TimeSlicer", "slice_float64", "slice_reference",
     "GaussianInterpolator", "interpolate_reference", "interpolation_factor",
+    "PlaybackMode", "playback_update", "MorphPair", "ResidentCloud4d",
 ]

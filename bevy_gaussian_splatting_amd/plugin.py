@@ -178,7 +178,8 @@ class PlanarGaussian3dHandle:
 class MorphPair:
     """The two sides of a morph (`GaussianInterpolate { lhs, rhs }`) and the output's planes, kept in device memory
     across calls; made by `GaussianSplattingPlugin.morph_pair`. `at(settings)` runs the blend on `bgs_stream`
-    (libbgs_morph.so), downloads the output and returns it as a resident cloud."""
+    (libbgs_morph.so) and hands the output's device planes to the cloud upload, which packs them where they lie
+    (include/bgs.h "DEVICE PLANES"): nothing crosses the host."""
 
     def __init__(self, plugin: "GaussianSplattingPlugin", lhs: PlanarGaussian3d, rhs: PlanarGaussian3d,
                  precompute_covariance_3d: bool = False, interpolator=None):
@@ -210,18 +211,21 @@ class MorphPair:
 
     def at(self, settings: CloudSettings, return_planes: bool = False):
         """The output cloud at `settings.time` (time_start and time_stop are read as well) as a resident handle, of
-        format "cov3d" for a pair made with `precompute_covariance_3d`. With `return_planes` also its host planes."""
+        format "cov3d" for a pair made with `precompute_covariance_3d`. The blend is enqueued on `bgs_stream` and the
+        upload follows it with no synchronisation in between: the upload orders itself behind that stream and returns
+        once the cloud is complete, so the next `at` may overwrite the output planes. Free the handle before the next
+        time's replaces it. With `return_planes` also the output's planes, downloaded."""
         plugin, k = self._plugin, len(self._widths)
-        outs = [np.zeros((self.n, w), np.float32) for w in self._widths]
+        outs = [np.zeros((self.n, w), np.float32) for w in self._widths] if return_planes else None
+        if self.n and not self._ptrs:
+            raise RuntimeError("this MorphPair was freed")
+        out_ptrs = self._ptrs[2 * k:] if self.n else [0] * k
         if self.n:
-            if not self._ptrs:
-                raise RuntimeError("this MorphPair was freed")
-            plugin.synchronize()
-            self._interpolator.interpolate(plugin.stream_handle(), self.n, self._ptrs[:k], self._ptrs[k:2 * k], self._ptrs[2 * k:], settings)
-            plugin.synchronize()
-            for ptr, plane in zip(self._ptrs[2 * k:], outs):
+            self._interpolator.interpolate(plugin.stream_handle(), self.n, self._ptrs[:k], self._ptrs[k:2 * k], out_ptrs, settings)
+        handle = plugin.upload_device_planes("cov3d" if self.precompute_covariance_3d else "f32", self.n, out_ptrs)
+        if return_planes and self.n:
+            for ptr, plane in zip(out_ptrs, outs):     # (the upload has synchronised: the planes are complete)
                 plugin.download(ptr, plane)
-        handle = plugin.upload_covariance_planes(*outs) if self.precompute_covariance_3d else plugin.upload(PlanarGaussian3d(*outs))
         return (handle, tuple(outs)) if return_planes else handle
 
     def free(self) -> None:
@@ -235,6 +239,77 @@ class MorphPair:
 
     def __exit__(self, *exc):
         self.free()
+
+
+class ResidentCloud4d:
+    """A 4D cloud's five planes and the three planes of its slice, kept in device memory across calls; made by
+    `GaussianSplattingPlugin.resident_4d`. The analogue of `MorphPair` for a playing 4D asset: the planes go up once,
+    and `at(settings)` does only the slice (`bgst_slice` on `bgs_stream`, libbgs_slice.so) and the cloud upload from
+    the slice's device planes (include/bgs.h "DEVICE PLANES"): nothing crosses the host."""
+
+    WIDTHS = (4, 48, 8)
+
+    def __init__(self, plugin: "GaussianSplattingPlugin", cloud4d: PlanarGaussian4d, slicer=None):
+        from .time_slice import TimeSlicer
+        if not isinstance(cloud4d, PlanarGaussian4d):
+            raise TypeError("cloud4d must be a PlanarGaussian4d")
+        self._plugin = plugin
+        self._slicer = slicer or TimeSlicer(plugin.device)
+        self.n = len(cloud4d)
+        self._ptrs = []                      # the five planes of the 4D cloud, then the slice's three
+        if self.n:
+            try:
+                for plane in cloud4d.planes():
+                    self._ptrs.append(plugin.device_alloc(plane.nbytes))
+                    plugin.upload_bytes(self._ptrs[-1], plane)
+                for w in self.WIDTHS:
+                    self._ptrs.append(plugin.device_alloc(self.n * w * 4))
+            except BaseException:
+                self.free()
+                raise
+
+    def __len__(self) -> int:
+        return self.n
+
+    def at(self, settings: CloudSettings, return_planes: bool = False):
+        """The cloud at `settings.time` (global_scale, time_start and time_stop are read too) as a resident handle of
+        format "cov3d". The slice is enqueued on `bgs_stream` and the upload follows it with no synchronisation in
+        between: the upload orders itself behind that stream and returns once the cloud is complete, so the next `at`
+        may overwrite the slice's planes. Sort and render the handle with any settings of the precomputed-covariance
+        path, which reads neither `time` nor `global_scale`; free it before the next time's replaces it. With
+        `return_planes` also the slice's three planes, downloaded."""
+        plugin = self._plugin
+        outs = [np.zeros((self.n, w), np.float32) for w in self.WIDTHS] if return_planes else None
+        if self.n and not self._ptrs:
+            raise RuntimeError("this ResidentCloud4d was freed")
+        out_ptrs = self._ptrs[5:] if self.n else [0] * 3
+        if self.n:
+            self._slicer.slice(plugin.stream_handle(), self.n, self._ptrs[:5], out_ptrs, settings)
+        handle = plugin.upload_device_planes("cov3d", self.n, out_ptrs)
+        if return_planes and self.n:
+            for ptr, plane in zip(out_ptrs, outs):     # (the upload has synchronised: the planes are complete)
+                plugin.download(ptr, plane)
+        return (handle, tuple(outs)) if return_planes else handle
+
+    def free(self) -> None:
+        ptrs, self._ptrs = self._ptrs, []
+        if self._plugin._ctx is not None:
+            for ptr in ptrs:
+                self._plugin.device_free(ptr)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+
+# The three cloud uploads by format: the C entry point, its planes in the order of its arguments, and the bytes of a splat.
+DEVICE_PLANE_FORMATS = {
+    "f32": ("bgs_cloud_upload_f32", ("position_visibility", "spherical_harmonic", "rotation", "scale_opacity"), 16 + 192 + 16 + 16),
+    "f16": ("bgs_cloud_upload_f16", ("position_visibility", "spherical_harmonic_h2", "rotation_scale_opacity"), 16 + 96 + 16),
+    "cov3d": ("bgs_cloud_upload_cov3d_f32", ("position_visibility", "spherical_harmonic", "covariance_3d_opacity"), 16 + 192 + 32),
+}
 
 
 def _fptr(a: np.ndarray):
@@ -330,57 +405,66 @@ class GaussianSplattingPlugin:
         self._check(self._lib.bgs_cloud_upload_cov3d_f32(self._ctx, n, _fptr(pv), _fptr(sh), _fptr(cov), ctypes.byref(out)))
         return PlanarGaussian3dHandle(self, out, n, "cov3d", n * (16 + 192 + 32))
 
+    def upload_device_planes(self, fmt: str, n: int, pointers) -> PlanarGaussian3dHandle:
+        """A resident cloud of `n` splats from planes that are in device memory already (include/bgs.h "DEVICE PLANES"):
+        `fmt` is "f32", "f16" or "cov3d", `pointers` the planes' addresses as integers in the order of that format's C
+        entry point (`DEVICE_PLANE_FORMATS`). Each is device memory of this plugin's device, 16-byte aligned; the work
+        that writes it is complete or was enqueued on `stream_handle()` before this call, and no `synchronize()` is
+        needed in between. Returns once the cloud is complete: the planes are the caller's again, and unchanged. The
+        entry points take host addresses as well, plane by plane, so the planes may be mixed."""
+        if fmt not in DEVICE_PLANE_FORMATS:
+            raise ValueError(f"fmt must be one of {sorted(DEVICE_PLANE_FORMATS)}, not {fmt!r}")
+        entry, names, splat_bytes = DEVICE_PLANE_FORMATS[fmt]
+        pointers = [int(p or 0) for p in pointers]
+        if len(pointers) != len(names):
+            raise ValueError(f"{entry} takes {len(names)} planes ({', '.join(names)}), got {len(pointers)} pointers")
+        n = int(n)
+        if n < 0:
+            raise ValueError("n must be >= 0")
+        ptype = {"f32": ctypes.POINTER(ctypes.c_float), "u32": ctypes.POINTER(ctypes.c_uint32)}
+        kinds = ("f32", "u32", "u32") if fmt == "f16" else ("f32",) * len(names)
+        args = [ctypes.cast(ctypes.c_void_p(p), ptype[k]) for p, k in zip(pointers, kinds)]
+        out = ctypes.c_void_p()
+        self._check(getattr(self._lib, entry)(self._ctx, n, *args, ctypes.byref(out)))
+        return PlanarGaussian3dHandle(self, out, n, fmt, n * splat_bytes)
+
     # -- 4D clouds (src/render/gaussian_4d.wgsl; libbgs_slice.so) ----------------------
+    def resident_4d(self, cloud4d: PlanarGaussian4d, slicer=None) -> "ResidentCloud4d":
+        """The five planes of a 4D cloud made resident once, with room for its slice: a `ResidentCloud4d` whose
+        `.at(settings)` does only the slice and the upload from the slice's device planes. A host that plays the cloud
+        uploads it once and calls `playback_update` then `.at` per frame. Free it (`.free()`, or use it as a context
+        manager) when the playback ends."""
+        return ResidentCloud4d(self, cloud4d, slicer)
+
     def slice_4d(self, cloud4d: PlanarGaussian4d, settings: CloudSettings, slicer=None, return_planes: bool = False):
-        """The 4D cloud at `settings.time` as a resident 3D cloud of format "cov3d": the five planes go into device
-        memory, `bgst_slice` runs on `bgs_stream` (`time_slice.TimeSlicer`; global_scale, time_start and time_stop are
-        read too), and the three planes of the slice come back to the host and go up again through
-        `bgs_cloud_upload_cov3d_f32`. The round trip is there because libbgs has no entry point that takes planes by
-        device address (include/bgs_slice.h "ORDERING"). Sort and render the handle with any
-        settings of the precomputed-covariance path, which reads neither `time` nor `global_scale`; free it before the
-        next time's slice replaces it. With `return_planes` also the three host planes."""
-        from .time_slice import TimeSlicer
-        if not isinstance(cloud4d, PlanarGaussian4d):
-            raise TypeError("cloud4d must be a PlanarGaussian4d")
-        slicer = slicer or TimeSlicer(self.device)
-        n = len(cloud4d)
-        outs = [np.zeros((n, w), np.float32) for w in (4, 48, 8)]
-        if n:
-            self.synchronize()
-            ptrs = []
-            try:
-                for plane in cloud4d.planes() + tuple(outs):
-                    ptrs.append(self.device_alloc(plane.nbytes))
-                for ptr, plane in zip(ptrs[:5], cloud4d.planes()):
-                    self.upload_bytes(ptr, plane)
-                slicer.slice(self.stream_handle(), n, ptrs[:5], ptrs[5:], settings)
-                self.synchronize()
-                for ptr, plane in zip(ptrs[5:], outs):
-                    self.download(ptr, plane)
-            finally:
-                for ptr in ptrs:
-                    self.device_free(ptr)
-        handle = self.upload_covariance_planes(*outs)
-        return (handle, tuple(outs)) if return_planes else handle
+        """The 4D cloud at `settings.time` as a resident 3D cloud of format "cov3d", in one shot: the five planes go
+        into device memory, `bgst_slice` runs on `bgs_stream` (`time_slice.TimeSlicer`; global_scale, time_start and
+        time_stop are read too), and `bgs_cloud_upload_cov3d_f32` packs the cloud from the three device planes of the
+        slice (include/bgs_slice.h "ORDERING"). For more than one `time` keep the cloud
+        resident (`resident_4d`). Sort and render the handle with any settings of the precomputed-covariance path, which
+        reads neither `time` nor `global_scale`; free it before the next time's slice replaces it. With `return_planes`
+        also the three planes on the host."""
+        with self.resident_4d(cloud4d, slicer) as resident:
+            return resident.at(settings, return_planes=return_planes)
 
     # -- morph between two clouds (src/morph/interpolate.wgsl; libbgs_morph.so) ---------
     def morph_pair(self, lhs: PlanarGaussian3d, rhs: PlanarGaussian3d, precompute_covariance_3d: bool = False,
                    interpolator=None) -> "MorphPair":
         """Both sides of a `GaussianInterpolate` made resident once: a `MorphPair` whose `.at(settings)` does only the
-        kernel, the download and the upload. A host that scrubs `time` uploads each side once. Free it (`.free()`, or
+        kernel and the upload from the output's device planes. A host that scrubs `time` uploads each side once. Free it (`.free()`, or
         use it as a context manager) when the morph ends."""
         return MorphPair(self, lhs, rhs, precompute_covariance_3d, interpolator)
 
     def interpolate(self, lhs: PlanarGaussian3d, rhs: PlanarGaussian3d, settings: CloudSettings,
                     precompute_covariance_3d: bool = False, interpolator=None, return_planes: bool = False):
         """The blend of two clouds of equal length at `settings.time` between `time_start` and `time_stop` as a resident
-        cloud (the reference's `GaussianInterpolate { lhs, rhs }`): both sides' planes go into device memory,
-        `bgsm_interpolate_f32` runs on `bgs_stream` (`interpolate.GaussianInterpolator`), and the output's planes come
-        back to the host and go up again through `bgs_cloud_upload_f32`. With `precompute_covariance_3d` the two clouds'
-        `Covariance3dOpacity` planes are blended instead of rotation and scale (`bgsm_interpolate_cov3d_f32`) and the
-        handle is of format "cov3d". The round trip is there because libbgs has no entry point that takes planes by
-        device address (include/bgs_morph.h "ORDERING"). Free the handle before the next
-        time's morph replaces it. With `return_planes` also the output's host planes."""
+        cloud (the reference's `GaussianInterpolate { lhs, rhs }`), in one shot: both sides' planes go into device memory,
+        `bgsm_interpolate_f32` runs on `bgs_stream` (`interpolate.GaussianInterpolator`), and `bgs_cloud_upload_f32` packs
+        the cloud from the output's device planes. With `precompute_covariance_3d` the two clouds' `Covariance3dOpacity`
+        planes are blended instead of rotation and scale (`bgsm_interpolate_cov3d_f32`) and the handle is of format
+        "cov3d" (include/bgs_morph.h "ORDERING"). For more than one `time` keep the pair
+        resident (`morph_pair`). Free the handle before the next time's morph replaces it. With `return_planes` also the
+        output's planes on the host."""
         with self.morph_pair(lhs, rhs, precompute_covariance_3d, interpolator) as pair:
             return pair.at(settings, return_planes=return_planes)
 

@@ -30,6 +30,16 @@ class SortMode(enum.IntEnum):
     Std = 3
 
 
+class PlaybackMode(enum.IntEnum):
+    """src/gaussian/settings.rs:27-33 (same discriminants; the default is Still): how `playback_update` advances
+    `CloudSettings.time`."""
+
+    Loop = 0
+    Once = 1
+    Sin = 2
+    Still = 3
+
+
 class RadixSortDepthBits(enum.IntEnum):
     """src/gaussian/settings.rs:52-77."""
 
@@ -164,6 +174,7 @@ class CloudSettings:
     radix_sort_depth_bits: RadixSortDepthBits = RadixSortDepthBits.Bits32
     draw_mode: DrawMode = DrawMode.All
     gaussian_mode: GaussianMode = GaussianMode.Gaussian3d
+    playback_mode: PlaybackMode = PlaybackMode.Still
     rasterize_mode: RasterizeMode = RasterizeMode.Color
     color_space: GaussianColorSpace = GaussianColorSpace.SrgbRec709Display
     num_classes: int = 1
@@ -201,6 +212,38 @@ class CloudSettings:
         s.position_min[:] = [float(v) for v in self.position_min] + [1.0]
         s.position_max[:] = [float(v) for v in self.position_max] + [1.0]
         return s
+
+
+def playback_update(settings: CloudSettings, delta_secs: float, elapsed_secs: float) -> None:
+    """One run of the reference's `playback_update` system (src/gaussian/settings.rs:145-191) on one cloud's settings:
+    `settings.time` advances by the rule of `settings.playback_mode`, in f32, every operation rounded once, in the order
+    the reference writes them. `delta_secs` and `elapsed_secs` stand for `Time::delta_secs()` and `Time::elapsed_secs()`.
+
+      time_scale == 0, or Still      nothing
+      Once with time >= time_stop    nothing (it stays where it stopped, which may be past time_stop)
+      Loop, Once                     time += delta_secs * time_scale; Loop then resets to time_start when time > time_stop
+      Sin                            time = time_start + ((time_stop - time_start) * (sin((time_scale * elapsed_secs * 2) * pi) + 1)) / 2
+
+    The sine is numpy's float32 sine; include/bgs_host.hpp's twin uses the C library's. The slice and the morph read
+    `time` from the settings they are given: call this before `ResidentCloud4d.at` / `MorphPair.at`."""
+    f = np.float32
+    scale = f(settings.time_scale)
+    mode = PlaybackMode(settings.playback_mode)
+    if scale == f(0.0) or mode == PlaybackMode.Still:
+        return
+    time, start, stop = f(settings.time), f(settings.time_start), f(settings.time_stop)
+    if mode == PlaybackMode.Once and time >= stop:
+        return
+    with np.errstate(all="ignore"):
+        if mode == PlaybackMode.Sin:
+            theta = scale * f(elapsed_secs)
+            y = np.sin(theta * f(2.0) * f(np.pi), dtype=np.float32)
+            time = start + (stop - start) * (y + f(1.0)) / f(2.0)
+        else:
+            time = time + f(delta_secs) * scale
+            if mode == PlaybackMode.Loop and time > stop:
+                time = start
+    settings.time = float(time)
 
 
 def compute_aabb(cloud):

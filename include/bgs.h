@@ -261,6 +261,22 @@ void bgs_view_perspective(const float world_from_view[16], float fov_y_radians,
                           bgs_view* out);
 
 /* ---- cloud upload (planar SoA, src/gaussian/formats/planar_3d.rs:45-54) ---------- */
+/* DEVICE PLANES. Each plane pointer of the three uploads below is, plane by plane, either host memory or device memory
+ * of the context's device; the planes of one call may be mixed. The library asks the runtime where each pointer lies:
+ *   - host plane: pageable, pinned or managed memory, and any pointer the runtime does not know. It is copied to the
+ *     device (blocking) and has no alignment rule.
+ *   - device plane: device memory of the context's device (bgs_device_alloc, or the caller's own). It must be 16-byte
+ *     aligned. No copy of it is made: the library packs the cloud's records straight from where the plane lies; only
+ *     position_visibility, which the cloud keeps as a plane of its own, is copied device to device. The upload never
+ *     writes a plane of the caller's.
+ *   - BGS_EINVAL, naming the plane, before anything is allocated: device memory of another device, and a device plane
+ *     that is not 16-byte aligned.
+ * Ordering of a device plane: the work that writes it is either complete, or was enqueued on the stream bgs_stream(ctx)
+ * names BEFORE the call: the upload orders itself behind what that stream holds at the call, on the device, with no
+ * synchronisation by the caller in between. The upload returns once the cloud is complete (it synchronises its own
+ * stream), so the caller may overwrite or free its planes as soon as it returns, e.g. with the next time's output of a
+ * kernel that produces a cloud per frame; bgs_cloud_free the previous cloud once its frames are done.
+ * n == 0 is BGS_OK and looks at no pointer. */
 /* f32 planes: position_visibility[n][4], spherical_harmonic[n][48] (index 3*k+c),
  * rotation[n][4] as [w,x,y,z], scale_opacity[n][4] (sx,sy,sz,opacity). */
 int bgs_cloud_upload_f32(bgs_ctx* ctx, uint32_t n, const float* position_visibility,

@@ -346,6 +346,39 @@ class GaussianSplattingPlugin {
         return PlanarGaussian3dHandle(ctx_, cloud);
     }
 
+    // The uploads by raw plane pointers, n rows each, as the C ABI takes them (include/bgs.h "DEVICE PLANES"): each plane
+    // is host memory or 16-byte aligned device memory of this context's device, plane by plane. A device plane is packed
+    // from where it lies; the work that writes it is complete or was enqueued on stream() before the call. This is how
+    // the output of a device-side producer (include/bgs_slice.hpp, include/bgs_morph.hpp) becomes a cloud without
+    // crossing the host.
+    PlanarGaussian3dHandle upload(uint32_t n, const float* position_visibility, const float* spherical_harmonic,
+                                  const float* rotation, const float* scale_opacity) {
+        bgs_cloud* cloud = nullptr;
+        check(bgs_cloud_upload_f32(ctx_, n, position_visibility, spherical_harmonic, rotation, scale_opacity, &cloud),
+              "bgs_cloud_upload_f32");
+        return PlanarGaussian3dHandle(ctx_, cloud);
+    }
+    PlanarGaussian3dHandle upload_f16(uint32_t n, const float* position_visibility, const uint32_t* spherical_harmonic_h2,
+                                      const uint32_t* rotation_scale_opacity) {
+        bgs_cloud* cloud = nullptr;
+        check(bgs_cloud_upload_f16(ctx_, n, position_visibility, spherical_harmonic_h2, rotation_scale_opacity, &cloud),
+              "bgs_cloud_upload_f16");
+        return PlanarGaussian3dHandle(ctx_, cloud);
+    }
+    PlanarGaussian3dHandle upload_cov3d(uint32_t n, const float* position_visibility, const float* spherical_harmonic,
+                                        const float* covariance_3d_opacity) {
+        bgs_cloud* cloud = nullptr;
+        check(bgs_cloud_upload_cov3d_f32(ctx_, n, position_visibility, spherical_harmonic, covariance_3d_opacity, &cloud),
+              "bgs_cloud_upload_cov3d_f32");
+        return PlanarGaussian3dHandle(ctx_, cloud);
+    }
+    // the stream a device-side producer of planes enqueues on (bgs_stream): a hipStream_t
+    void* stream() {
+        void* st = nullptr;
+        check(bgs_stream(ctx_, &st), "bgs_stream");
+        return st;
+    }
+
     // run_radix_sort / rayon_sort for one view: the full sorted entry list (culled entries last)
     std::vector<bgs_sort_entry> sort(const PlanarGaussian3dHandle& h, const View& v, const CloudSettings& s) {
         std::vector<bgs_sort_entry> out(h.size());

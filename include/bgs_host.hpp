@@ -4,7 +4,8 @@
 // (src/sort/mod.rs:331-393), compute_aabb (src/gaussian/interface.rs:22-63) and the INRIA `.ply` loader
 // (src/io/ply.rs:23-132, with the reference's quirks), the `.gcloud` container reader and the loader's dispatch on
 // the file extension (src/io/gcloud/flexbuffers.rs:9-22, src/io/loader.rs:22-61), the precomputed-covariance
-// plane (src/gaussian/covariance.rs:4-41, src/gaussian/f32.rs:218-251). Header-only; tests/test_cpp_host.py checks each
+// plane (src/gaussian/covariance.rs:4-41, src/gaussian/f32.rs:218-251), the rule by which a playing cloud's time
+// advances (src/gaussian/settings.rs:27-33,145-191). Header-only; tests/test_cpp_host.py checks each
 // against the Python mirror, which is pinned by known answers.
 #ifndef BGS_HOST_HPP
 #define BGS_HOST_HPP
@@ -112,6 +113,39 @@ inline void update_sort_trigger(SortTrigger& t, const std::array<float, 3>& came
 // src/sort/rayon.rs:124-129: the CPU sorts stretch the period to at least 4x the measured sort time
 inline void after_cpu_sort(SortConfig& config, double sort_duration_s) {
     config.period_ms = std::max({config.period_ms, config.period_ms * 4 / 5, (int64_t)4 * (int64_t)(sort_duration_s * 1000.0)});
+}
+
+// ---- how a playing cloud's time advances --------------------------------------------------------------
+enum class PlaybackMode : uint32_t { Loop = 0, Once = 1, Sin = 2, Still = 3 };  // src/gaussian/settings.rs:27-33 (default Still)
+// The time fields of the reference's CloudSettings (src/gaussian/settings.rs:100-107, defaults :125-129). The slice of a
+// 4D cloud and the morph between two clouds read time, time_start and time_stop (include/bgs_slice.hpp, bgs_morph.hpp).
+struct Playback {
+    PlaybackMode playback_mode = PlaybackMode::Still;
+    float time = 0.0f;
+    float time_scale = 1.0f;
+    float time_start = 0.0f;
+    float time_stop = 1.0f;
+};
+// One run of the reference's playback_update system (src/gaussian/settings.rs:145-191) on one cloud's settings, in f32,
+// every operation rounded once, in the order the reference writes them; delta_secs and elapsed_secs stand for
+// Time::delta_secs() and Time::elapsed_secs(). time_scale == 0 and Still do nothing; Once does nothing once time >=
+// time_stop; Loop and Once add delta_secs * time_scale; Loop resets to time_start when time is strictly past time_stop;
+// Sin sets time_start + ((time_stop - time_start) * (sin((time_scale * elapsed_secs * 2) * pi) + 1)) / 2. The Python
+// mirror is settings.playback_update: the linear modes agree to the bit where the compiler does not contract the
+// multiplication and the addition into one operation (-ffp-contract=off where the target has one), Sin within the two
+// sine functions' errors.
+inline void playback_update(Playback& s, float delta_secs, float elapsed_secs) {
+    if (s.time_scale == 0.0f) return;
+    if (s.playback_mode == PlaybackMode::Still) return;
+    if (s.playback_mode == PlaybackMode::Once && s.time >= s.time_stop) return;
+    if (s.playback_mode == PlaybackMode::Sin) {
+        const float theta = s.time_scale * elapsed_secs;
+        const float y = std::sin(theta * 2.0f * 3.14159265358979323846f);
+        s.time = s.time_start + (s.time_stop - s.time_start) * (y + 1.0f) / 2.0f;
+        return;
+    }
+    s.time += delta_secs * s.time_scale;
+    if (s.playback_mode == PlaybackMode::Loop && s.time > s.time_stop) s.time = s.time_start;
 }
 
 // ---- multi-camera sorted-entry asset ---------------------------------------------------------------

@@ -25,13 +25,17 @@
  * ORDERING. Both entry points only ENQUEUE on the stream they are given (two launches): they never block and touch no
  * other stream. What they read must be complete on that stream (or earlier); what they write is complete once the
  * stream reaches that point. They keep no state and need no scratch: there is nothing to create or free, and any
- * number of threads may call them. libbgs has no entry point that takes planes by device address, so a morphed cloud
- * reaches a resident cloud through the host:
- *   1. bgsm_interpolate_f32(.., bgs_stream(ctx), ..) or bgsm_interpolate_cov3d_f32, then bgs_synchronize(ctx)
- *   2. bgs_download of the output planes
- *   3. bgs_cloud_upload_f32(ctx, n, position_visibility, spherical_harmonic, rotation, scale_opacity, &cloud), or
- *      bgs_cloud_upload_cov3d_f32(ctx, n, position_visibility, spherical_harmonic, covariance_3d_opacity, &cloud)
- *   4. bgs_sort / bgs_render of that cloud; bgs_cloud_free before the next time's morph replaces it.
+ * number of threads may call them. libbgs's uploads take a plane by device address (include/bgs.h, DEVICE PLANES), so
+ * a morphed cloud reaches a resident cloud without leaving the device:
+ *   1. bgsm_interpolate_f32(.., bgs_stream(ctx), ..) or bgsm_interpolate_cov3d_f32: no synchronisation after it
+ *   2. bgs_cloud_upload_f32(ctx, n, position_visibility, spherical_harmonic, rotation, scale_opacity, &cloud), or
+ *      bgs_cloud_upload_cov3d_f32(ctx, n, position_visibility, spherical_harmonic, covariance_3d_opacity, &cloud), with
+ *      the OUTPUT's device addresses: it orders itself behind what bgs_stream(ctx) holds, packs the cloud from the
+ *      output planes, and returns once the cloud is complete; the output planes are free for the next time's morph from
+ *      then on
+ *   3. bgs_sort / bgs_render of that cloud; bgs_cloud_free before the next time's morph replaces it.
+ * A host that wants the planes on the host anyway takes the other order: bgs_synchronize(ctx) after step 1, bgs_download
+ * of the output planes, and the same upload from the host copies.
  * The lhs and rhs planes stay where they are: a host that scrubs `time` uploads each side once.
  * Status codes mirror bgs_status. */
 #ifndef BGS_MORPH_H

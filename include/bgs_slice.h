@@ -24,12 +24,16 @@
  * ORDERING. bgst_slice only ENQUEUES on the stream it is given (two launches): it never blocks and touches no other
  * stream. What it reads must be complete on that stream (or earlier); what it writes is complete once the stream
  * reaches that point. It keeps no state and needs no scratch: there is nothing to create or free, and any number of
- * threads may call it. libbgs has no entry point that takes planes by device address, so a slice reaches a resident
- * cloud through the host:
- *   1. bgst_slice(.., bgs_stream(ctx), ..), then bgs_synchronize(ctx)
- *   2. bgs_download of the three output planes
- *   3. bgs_cloud_upload_cov3d_f32(ctx, n, position_visibility, spherical_harmonic, covariance_3d_opacity, &cloud)
- *   4. bgs_sort / bgs_render of that cloud; bgs_cloud_free before the next time's slice replaces it.
+ * threads may call it. libbgs's uploads take a plane by device address (include/bgs.h, DEVICE PLANES), so a slice
+ * reaches a resident cloud without leaving the device:
+ *   1. bgst_slice(.., bgs_stream(ctx), ..): no synchronisation after it
+ *   2. bgs_cloud_upload_cov3d_f32(ctx, n, out_position_visibility_device_ptr, out_spherical_harmonic_device_ptr,
+ *      out_covariance_3d_opacity_device_ptr, &cloud): it orders itself behind what bgs_stream(ctx) holds, packs the
+ *      cloud from the three output planes, and returns once the cloud is complete; the output planes are free for the
+ *      next time's slice from then on
+ *   3. bgs_sort / bgs_render of that cloud; bgs_cloud_free before the next time's slice replaces it.
+ * A host that wants the planes on the host anyway takes the other order: bgs_synchronize(ctx) after step 1, bgs_download
+ * of the three output planes, and the same upload from the host copies.
  * Status codes mirror bgs_status. */
 #ifndef BGS_SLICE_H
 #define BGS_SLICE_H
