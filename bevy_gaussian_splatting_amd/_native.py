@@ -31,7 +31,7 @@ STAGE_NAMES = ("keygen", "depth_sort", "project", "tile_sort", "ranges", "raster
 COMM_ID_BYTES = 128
 # what this binding was written against (include/bgs.h BGS_VERSION_*): load() hands it to bgs_abi_check together with
 # the sizes of its ctypes structs
-ABI_VERSION = (0 << 16) | 4
+ABI_VERSION = (0 << 16) | 5
 
 
 class BgsSortEntry(ctypes.Structure):
@@ -68,6 +68,18 @@ class BgsFrameRecordsInfo(ctypes.Structure):
 
     _fields_ = [("draw_count", ctypes.c_uint32), ("record_stride", ctypes.c_uint32), ("has_rects", ctypes.c_uint32),
                 ("visible_count", ctypes.c_uint32), ("color_max_bits", ctypes.c_uint32)]
+
+
+class BgsFrameListsInfo(ctypes.Structure):
+    """bgs_frame_lists_info (include/bgs_diag.h)."""
+
+    _fields_ = [("entry_count", ctypes.c_uint64), ("binning", ctypes.c_uint32), ("draw_count", ctypes.c_uint32),
+                ("sup_edge", ctypes.c_uint32), ("sup_x", ctypes.c_uint32), ("sup_y", ctypes.c_uint32), ("level", ctypes.c_uint32),
+                ("coarse_cap", ctypes.c_uint32), ("wide_bin", ctypes.c_uint32), ("instance_count", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+SELFTEST_BIN_GUARD = 64   # BGS_SELFTEST_BIN_GUARD (include/bgs_diag.h)
 
 
 vp, u32, u64 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64
@@ -141,6 +153,8 @@ PROTOTYPES = (
     ("bgs_selftest_tile_order", c_int, (vp, vp, u32, u32, vp, vp)),
     ("bgs_selftest_pack", c_int, (vp, u32, vp, u32, vp)),
     ("bgs_debug_frame_records", c_int, (vp, vp, u64, up, u32, POINTER(BgsFrameRecordsInfo))),
+    ("bgs_selftest_bin", c_int, (vp, up, u32, u32, u32, u32, u32, u32, u32, up, u64, up, up)),
+    ("bgs_debug_frame_lists", c_int, (vp, up, u32, up, u64, up, u32, POINTER(BgsFrameListsInfo))),
 )
 EXPORTED_SYMBOLS = tuple(name for name, _, _ in PROTOTYPES)
 

@@ -172,6 +172,60 @@ int bgs_selftest_tile_order(bgs_ctx* ctx, const uint16_t* host_cost, uint32_t nt
     return BGS_OK;
 }
 
+// bin_kernel alone, on the caller's rectangles: a zeroed Control of its own (draw_count = n), zeroed chain words, and the
+// lists plus BGS_SELFTEST_BIN_GUARD entries filled with 0xFF bytes, all of which go back to the caller. What is refused is
+// what the kernel's own indexing rests on (render_kernels.hip: 32-entry mask rows, 256 chain threads, 8-bit tile
+// coordinates); the rectangles themselves may hold anything: a coordinate past the grid matches no column / row mask.
+int bgs_selftest_bin(bgs_ctx* ctx, const uint32_t* host_rects, uint32_t n, uint32_t tiles_x, uint32_t tiles_y, uint32_t sup_edge,
+                     uint32_t coarse_cap, uint32_t wide, uint32_t blocks, uint32_t* host_lists, uint64_t lists_capacity_words,
+                     uint32_t* host_totals, uint32_t* error_out) {
+    if (!ctx) return fail(nullptr, BGS_EINVAL, "ctx is NULL");
+    if (!host_rects || !host_lists || !host_totals || !error_out)
+        return fail(ctx, BGS_EINVAL, "bin self-test: host_rects, host_lists, host_totals and error_out must be non-NULL");
+    if (n < 1u || n > (1u << 24)) return fail(ctx, BGS_EINVAL, "bin self-test: n must be 1 .. 2^24, got " + std::to_string(n));
+    if (tiles_x < 1u || tiles_x > 256u) return fail(ctx, BGS_EINVAL, "bin self-test: tiles_x must be 1 .. 256, got " + std::to_string(tiles_x));
+    if (tiles_y < 1u || tiles_y > 256u) return fail(ctx, BGS_EINVAL, "bin self-test: tiles_y must be 1 .. 256, got " + std::to_string(tiles_y));
+    if (sup_edge < 1u || sup_edge > 32u) return fail(ctx, BGS_EINVAL, "bin self-test: sup_edge must be 1 .. 32, got " + std::to_string(sup_edge));
+    if (!supertile_bins_fit(tiles_x, tiles_y, sup_edge))
+        return fail(ctx, BGS_EINVAL, "bin self-test: sup_edge " + std::to_string(sup_edge) + " gives more than " + std::to_string(MAX_SUPERTILES) +
+                                         " supertiles, or more than " + std::to_string(MAX_SUPERTILES_PER_AXIS) + " on an axis");
+    if (wide > 1u) return fail(ctx, BGS_EINVAL, "bin self-test: wide must be 0 or 1, got " + std::to_string(wide));
+    if (blocks < 1u || blocks > 4096u) return fail(ctx, BGS_EINVAL, "bin self-test: blocks must be 1 .. 4096, got " + std::to_string(blocks));
+    const uint32_t sup_x = (tiles_x + sup_edge - 1u) / sup_edge, sup_y = (tiles_y + sup_edge - 1u) / sup_edge, num_st = sup_x * sup_y;
+    if (coarse_cap < 1u || (uint64_t)num_st * coarse_cap > (1ull << 25))
+        return fail(ctx, BGS_EINVAL, "bin self-test: coarse_cap must be >= 1 and supertiles x coarse_cap <= 2^25, got " + std::to_string(coarse_cap));
+    const uint64_t list_words = ((uint64_t)num_st * coarse_cap + BGS_SELFTEST_BIN_GUARD) * 2u;
+    if (lists_capacity_words < list_words)
+        return fail(ctx, BGS_EINVAL, "bin self-test: host_lists holds " + std::to_string(lists_capacity_words) + " words, the lists and their guard are " +
+                                         std::to_string(list_words));
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, BGS_EHIP, "hipSetDevice failed");
+    int rc = finish_all(ctx);
+    if (rc != BGS_OK) return rc;
+    const size_t status_words = ((size_t)(n + 255u) / 256u + 1u) * MAX_SUPERTILES;   // (as scratch_layout sizes the frames')
+    DeviceBuffer<uint32_t> rects_buf, status_buf, lists_buf;
+    DeviceBuffer<Control> ctl_buf;
+    if (!rects_buf.reserve(n) || !status_buf.reserve(status_words) || !lists_buf.reserve((size_t)list_words) || !ctl_buf.reserve(1))
+        return fail(ctx, BGS_ENOMEM, "hipMalloc(bin self-test) failed");
+    Control* const ctl = ctl_buf.ptr;
+    hipStream_t st = ctx->lanes[0].stream;
+    bool ok = hipMemsetAsync(ctl, 0, sizeof(Control), st) == hipSuccess &&
+              hipMemsetAsync(status_buf.ptr, 0, status_words * sizeof(uint32_t), st) == hipSuccess &&
+              hipMemsetAsync(lists_buf.ptr, 0xFF, (size_t)list_words * sizeof(uint32_t), st) == hipSuccess &&
+              hipMemcpyAsync(rects_buf.ptr, host_rects, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, st) == hipSuccess &&
+              hipMemsetD32Async((hipDeviceptr_t)&ctl->draw_count, (int)n, 1, st) == hipSuccess;
+    if (ok) {
+        launch_bin(st, rects_buf.ptr, ctl, status_buf.ptr, lists_buf.ptr, coarse_cap, supertile_mul(sup_edge), sup_x, sup_y,
+                   /*ticket_slot=*/4, blocks, wide != 0u);
+        ok = hipGetLastError() == hipSuccess &&
+             hipMemcpyAsync(host_lists, lists_buf.ptr, (size_t)list_words * sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
+             hipMemcpyAsync(host_totals, ctl->coarse_total, sizeof ctl->coarse_total, hipMemcpyDeviceToHost, st) == hipSuccess &&
+             hipMemcpyAsync(error_out, &ctl->error, sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
+             hipStreamSynchronize(st) == hipSuccess;
+    }
+    if (!ok) { (void)hipGetLastError(); return fail(ctx, BGS_EHIP, "bin self-test failed on the device"); }
+    return BGS_OK;
+}
+
 // The Control block of the lane's last frame (Lane::last_ctl) is one of the two in the lane's scratch region. Where each
 // value the hook reads is final, from bgs_frame.hip (enqueue_frame, finish_lane) and render_kernels.hip:
 //   records      written by project_rank only (project_kernel / project_emit_kernel); bin_kernel and the rasterisers read them.
@@ -228,6 +282,87 @@ int bgs_debug_frame_records(bgs_ctx* ctx, void* host_records, uint64_t records_c
     if (rec_bytes) HIP_TRY(ctx, hipMemcpyAsync(host_records, L.records.ptr, rec_bytes, hipMemcpyDeviceToHost, st));
     if (info.has_rects && info.draw_count)
         HIP_TRY(ctx, hipMemcpyAsync(host_rects, L.rects.ptr, (size_t)info.draw_count * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    return BGS_OK;
+}
+
+// What the binning stage of the last frame left, from the lane the frame ran on (ctx->recent: lane 0 for every synchronous
+// frame, at any pipeline depth). Where each value is final (bgs_frame.hip, render_kernels.hip):
+//   BINNING_SCAN  coarse_total   written by bin_kernel into the frame's Control block; the frame's rasteriser (or, under
+//                                BGS_DEBUG_NO_RASTER_CLEANUP, the copy behind it) copies all 256 words to the lane's pinned
+//                                Control, which finish_lane reads and nothing writes until the lane's next frame: read there.
+//                 lists          L.coarse, num_st lists coarse_cap (Lane::pending_coarse_cap) entries apart, written by
+//                                bin_kernel only. A re-run writes them again with the re-run's capacity.
+//   BINNING_SORT  instances      L.inst[0] after the two tile-id passes (inst[0] -> inst[1] -> inst[0]); instance_count in
+//                                the pinned Control (the whole block is copied behind the frame).
+//                 ranges         in the lane's scratch region, which a BINNING_SORT frame leaves as it is: whatever
+//                                rewrites the region (the next frame's memset, bgs_radix_sort_pairs, a re-allocation)
+//                                clears Lane::last_ctl with it.
+int bgs_debug_frame_lists(bgs_ctx* ctx, uint32_t* host_totals, uint32_t totals_capacity_words, uint32_t* host_entries,
+                          uint64_t entries_capacity_words, uint32_t* host_ranges, uint32_t ranges_capacity_words,
+                          bgs_frame_lists_info* info_out) {
+    if (!ctx) return fail(nullptr, BGS_EINVAL, "ctx is NULL");
+    if (!info_out) return fail(ctx, BGS_EINVAL, "frame lists: info_out is NULL");
+    for (const Lane& lane : ctx->lanes)
+        if (lane.pending) return fail(ctx, BGS_EINVAL, "frame lists: frames are in flight");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, BGS_EHIP, "hipSetDevice failed");
+    int rc = finish_all(ctx);
+    if (rc != BGS_OK) return rc;
+    Lane& L = ctx->lanes[ctx->recent];
+    if (!L.has_result || !L.plan.render || !L.last_ctl || !L.stream)
+        return fail(ctx, BGS_EINVAL, "frame lists: no frame has been rendered (or a bgs_sort / bgs_radix_sort_pairs ran since)");
+    if (L.in.allow_graph) return fail(ctx, BGS_EINVAL, "frame lists: the last frame was an async frame");
+    const FramePlan& p = L.plan;
+    const Control& h = *L.h_ctl.ptr;
+    hipStream_t st = L.stream;
+    bgs_frame_lists_info info{};
+    info.binning = p.scan ? BINNING_SCAN : BINNING_SORT;
+    info.draw_count = h.sort_overflow ? 0u : h.draw_count;
+    if (p.scan) {
+        const uint32_t cap = L.pending_coarse_cap;
+        info.sup_edge = p.sup_edge;
+        info.sup_x = ((uint32_t)p.fp.tiles_x + p.sup_edge - 1u) / p.sup_edge;
+        info.sup_y = ((uint32_t)p.fp.tiles_y + p.sup_edge - 1u) / p.sup_edge;
+        info.level = p.level;
+        info.coarse_cap = cap;
+        info.wide_bin = p.wide_bin ? 1u : 0u;
+        const uint32_t num_st = info.draw_count ? p.num_st : 0u;   // (an empty draw list launches no bin_kernel: no lists)
+        if (num_st > MAX_SUPERTILES || info.sup_x * info.sup_y != p.num_st || (size_t)p.num_st * cap * 2u > L.coarse.capacity)
+            return fail(ctx, BGS_EINTERNAL, "frame lists: the frame's supertile lists exceed the lane's buffer");
+        for (uint32_t s = 0; s < num_st; ++s) info.entry_count += std::min(h.coarse_total[s], cap);
+        *info_out = info;
+        if (!host_totals && !host_entries && !host_ranges) return BGS_OK;   // the sizes only
+        if (!host_totals || totals_capacity_words < p.num_st)
+            return fail(ctx, BGS_EINVAL, "frame lists: host_totals holds " + std::to_string(totals_capacity_words) + " words, the frame has " +
+                                             std::to_string(p.num_st) + " supertiles");
+        if (info.entry_count && (!host_entries || entries_capacity_words < info.entry_count * 2u))
+            return fail(ctx, BGS_EINVAL, "frame lists: host_entries holds " + std::to_string(entries_capacity_words) + " words, the frame's lists are " +
+                                             std::to_string(info.entry_count * 2u));
+        uint64_t at = 0;
+        for (uint32_t s = 0; s < p.num_st; ++s) {
+            host_totals[s] = num_st ? h.coarse_total[s] : 0u;
+            const uint32_t len = num_st ? std::min(h.coarse_total[s], cap) : 0u;
+            if (len) HIP_TRY(ctx, hipMemcpyAsync(host_entries + at, L.coarse.ptr + (size_t)s * cap * 2u, (size_t)len * 8u, hipMemcpyDeviceToHost, st));
+            at += (uint64_t)len * 2u;
+        }
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        return BGS_OK;
+    }
+    constexpr uint32_t RANGE_WORDS = RADIX_BASE * RADIX_BASE * 2u;
+    info.entry_count = info.instance_count = h.instance_count;
+    *info_out = info;
+    if (!host_totals && !host_entries && !host_ranges) return BGS_OK;   // the sizes only
+    if (info.instance_count > L.inst[0].capacity || L.layout.off_ranges + RANGE_WORDS * 4ull > L.layout.bytes)
+        return fail(ctx, BGS_EINTERNAL, "frame lists: the frame's instances exceed the lane's buffers");
+    if (info.instance_count && (!host_entries || entries_capacity_words < (uint64_t)info.instance_count * 2u))
+        return fail(ctx, BGS_EINVAL, "frame lists: host_entries holds " + std::to_string(entries_capacity_words) + " words, the frame's instances are " +
+                                         std::to_string((uint64_t)info.instance_count * 2u));
+    if (!host_ranges || ranges_capacity_words < RANGE_WORDS)
+        return fail(ctx, BGS_EINVAL, "frame lists: host_ranges holds " + std::to_string(ranges_capacity_words) + " words, the table is " +
+                                         std::to_string(RANGE_WORDS));
+    if (info.instance_count)
+        HIP_TRY(ctx, hipMemcpyAsync(host_entries, L.inst[0].ptr, (size_t)info.instance_count * sizeof(uint2), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(host_ranges, L.scratch.ptr + L.layout.off_ranges, (size_t)RANGE_WORDS * 4u, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     return BGS_OK;
 }

@@ -162,6 +162,11 @@ void launch_project_bin(hipStream_t stream, const FrameParams& fp, const FramePa
                         const uint2* draw_list, const uint2* culled, Control* ctl, uint32_t* bin_status, void* records,
                         uint32_t* rects, uint32_t* coarse, uint32_t coarse_cap, uint32_t sup_edge,
                         uint32_t ticket_slot, int project_blocks, int bin_blocks, bool wide_bin);
+// bin_kernel alone, as launch_project_bin launches it behind project_kernel (and bgs_selftest_bin on rectangles of its
+// own): `blocks` workgroups of 1024 (wide_bin) or 256 threads; sup_mul = supertile_mul(edge), sup_x x sup_y supertiles.
+void launch_bin(hipStream_t stream, const uint32_t* rects, Control* ctl, uint32_t* bin_status, uint32_t* coarse,
+                uint32_t coarse_cap, uint32_t sup_mul, uint32_t sup_x, uint32_t sup_y, uint32_t ticket_slot,
+                uint32_t blocks, bool wide_bin);
 
 // Tile rasteriser for BINNING_SCAN: walks the supertile's ordered list, keeps the ranks whose
 // rectangle contains this tile (order-preserving ballot compaction), stages their records in LDS

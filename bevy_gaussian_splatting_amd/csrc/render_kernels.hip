@@ -595,11 +595,17 @@ void launch_project_bin(hipStream_t stream, const FrameParams& fp, const FramePa
 #undef BGS_LAUNCH_PB
     uint32_t bblocks = (fp.n + BIN_RANKS - 1u) / BIN_RANKS;
     if (bblocks > (uint32_t)bin_blocks) bblocks = (uint32_t)bin_blocks;
+    launch_bin(stream, rects, ctl, bin_status, coarse, coarse_cap, sup_mul, sup_x, sup_y, ticket_slot, bblocks, wide_bin);
+}
+
+void launch_bin(hipStream_t stream, const uint32_t* rects, Control* ctl, uint32_t* bin_status, uint32_t* coarse,
+                uint32_t coarse_cap, uint32_t sup_mul, uint32_t sup_x, uint32_t sup_y, uint32_t ticket_slot,
+                uint32_t blocks, bool wide_bin) {
     if (wide_bin)
-        hipLaunchKernelGGL(bin_kernel<16u>, dim3(bblocks), dim3(1024), 0, stream, rects, ctl, bin_status, coarse, coarse_cap,
+        hipLaunchKernelGGL(bin_kernel<16u>, dim3(blocks), dim3(1024), 0, stream, rects, ctl, bin_status, coarse, coarse_cap,
                            sup_mul, sup_x, sup_y, ticket_slot);
     else
-        hipLaunchKernelGGL(bin_kernel<4u>, dim3(bblocks), dim3(256), 0, stream, rects, ctl, bin_status, coarse, coarse_cap,
+        hipLaunchKernelGGL(bin_kernel<4u>, dim3(blocks), dim3(256), 0, stream, rects, ctl, bin_status, coarse, coarse_cap,
                            sup_mul, sup_x, sup_y, ticket_slot);
 }
 

@@ -695,6 +695,50 @@ class GaussianSplattingPlugin:
                 "rects": rects if info.has_rects else None, "visible_count": int(info.visible_count),
                 "color_max_bits": int(info.color_max_bits)}
 
+    def selftest_bin(self, rects: np.ndarray, tiles_x: int, tiles_y: int, sup_edge: int, coarse_cap: int, wide: int, blocks: int) -> dict:
+        """`bgs_selftest_bin`: bin_kernel alone on packed tile rectangles (uint32[n]). `lists` uint32[supertiles, coarse_cap,
+        2] (rank, rectangle; what the kernel did not write holds 0xFFFFFFFF), `guard` uint32[64, 2] (the entries behind the
+        last list), `totals` uint32[256] and `error` (Control::error). Test hook (see include/bgs_diag.h)."""
+        r = np.ascontiguousarray(rects, dtype=np.uint32)
+        num_st = max(-(-int(tiles_x) // max(int(sup_edge), 1)) * -(-int(tiles_y) // max(int(sup_edge), 1)), 0)
+        entries = num_st * max(int(coarse_cap), 0) + _native.SELFTEST_BIN_GUARD
+        lists = np.zeros((entries, 2), np.uint32)
+        totals = np.zeros(256, np.uint32)
+        err = ctypes.c_uint32()
+        self._check(self._lib.bgs_selftest_bin(self._ctx, _uptr(r), r.size, int(tiles_x), int(tiles_y), int(sup_edge), int(coarse_cap),
+                                               int(wide), int(blocks), _uptr(lists), lists.size, _uptr(totals), ctypes.byref(err)))
+        body = entries - _native.SELFTEST_BIN_GUARD
+        return {"lists": lists[:body].reshape(num_st, int(coarse_cap), 2), "guard": lists[body:], "totals": totals, "error": int(err.value)}
+
+    def debug_frame_lists(self) -> dict:
+        """`bgs_debug_frame_lists`: what the binning stage of the last synchronous `render` left on the device, at any
+        pipeline depth. Scan binning: `sup_edge`, `sup_x`, `sup_y`, `level`, `coarse_cap`, `wide_bin`, `totals`
+        uint32[supertiles] and `lists`, one uint32[min(total, coarse_cap), 2] (rank, rectangle) per supertile. Sort
+        binning: `instance_count`, `instances` uint32[instance_count, 2] (tile id, rank) and `ranges` uint32[65536, 2].
+        Both: `binning` ("scan" / "sort") and `draw_count`. Test hook; raises when there is no such frame."""
+        info = _native.BgsFrameListsInfo()
+        self._check(self._lib.bgs_debug_frame_lists(self._ctx, None, 0, None, 0, None, 0, ctypes.byref(info)))
+        count, scan = int(info.entry_count), int(info.binning) == 0
+        num_st = int(info.sup_x) * int(info.sup_y)
+        totals = np.zeros(max(num_st, 1), np.uint32)
+        entries = np.zeros((max(count, 1), 2), np.uint32)
+        ranges = np.zeros((65536, 2), np.uint32)
+        self._check(self._lib.bgs_debug_frame_lists(self._ctx, _uptr(totals), num_st if scan else 0, _uptr(entries), 2 * count,
+                                                    _uptr(ranges), ranges.size, ctypes.byref(info)))
+        if int(info.entry_count) != count:
+            raise RuntimeError("the frame changed between the two calls of bgs_debug_frame_lists")
+        out = {"binning": "scan" if scan else "sort", "draw_count": int(info.draw_count)}
+        if scan:
+            cap = int(info.coarse_cap)
+            totals = totals[:num_st]
+            ends = np.cumsum(np.minimum(totals, cap).astype(np.int64))
+            out.update(sup_edge=int(info.sup_edge), sup_x=int(info.sup_x), sup_y=int(info.sup_y), level=int(info.level), coarse_cap=cap,
+                       wide_bin=int(info.wide_bin), totals=totals,
+                       lists=[entries[int(e) - int(min(t, cap)):int(e)] for e, t in zip(ends, totals)])
+        else:
+            out.update(instance_count=int(info.instance_count), instances=entries[:count], ranges=ranges)
+        return out
+
     def set_pipeline_streams(self, streams: int) -> None:
         """HIP streams the lanes are multiplexed onto (0 = one per lane); see bgs_set_pipeline_streams."""
         self._check(self._lib.bgs_set_pipeline_streams(self._ctx, int(streams)))

@@ -149,6 +149,49 @@ typedef struct bgs_frame_records_info {
 int bgs_debug_frame_records(bgs_ctx* ctx, void* host_records, uint64_t records_capacity_bytes, uint32_t* host_rects,
                             uint32_t rects_capacity_words, bgs_frame_records_info* info_out);
 
+/* bin_kernel (the ordered coarse binning of BGS_BINNING_SCAN frames) alone, launched once on caller-supplied packed tile
+ * rectangles host_rects[n] (x0 | x1 << 8 | y0 << 16 | y1 << 24, 0x000000FF = touches no tile) for a grid of tiles_x x
+ * tiles_y tiles in supertiles of sup_edge x sup_edge: `wide` 0 is the 256-thread instantiation (pipelined frames), 1 the
+ * 1024-thread one (pipeline depth 1); `blocks` workgroups (fewer than ceil(n / 1024): each takes several 1024-rank tiles
+ * by ticket); lists of coarse_cap entries. Everything the kernel reads or writes is allocated for the call and zeroed —
+ * a Control block with draw_count = n, the chain words — except the lists, which are filled with 0xFF bytes together with
+ * BGS_SELFTEST_BIN_GUARD entries behind the last list. Returned as they are:
+ *   host_lists     (supertiles * coarse_cap + BGS_SELFTEST_BIN_GUARD) entries of two words (rank, packed rectangle), list s
+ *                  (supertile sy * sup_x + sx) at entry s * coarse_cap; lists_capacity_words: the words host_lists holds;
+ *   host_totals    256 words: Control::coarse_total (entries per list, counted past coarse_cap);
+ *   error_out      Control::error (the look-back watchdog; 0).
+ * BGS_EINVAL, naming the argument, for what the kernel's own indexing does not allow: 1 <= n <= 2^24, 1 <= tiles_x,
+ * tiles_y <= 256, 1 <= sup_edge <= 32 with at most 256 supertiles and 32 per axis, wide 0 / 1, 1 <= blocks <= 4096,
+ * coarse_cap >= 1 with supertiles * coarse_cap <= 2^25, and a host_lists that is too small (nothing is written then).
+ * Completes the frames in flight. Test hook (tests/test_bin_stage_gpu.py). */
+#define BGS_SELFTEST_BIN_GUARD 64u
+int bgs_selftest_bin(bgs_ctx* ctx, const uint32_t* host_rects, uint32_t n, uint32_t tiles_x, uint32_t tiles_y, uint32_t sup_edge,
+                     uint32_t coarse_cap, uint32_t wide, uint32_t blocks, uint32_t* host_lists, uint64_t lists_capacity_words,
+                     uint32_t* host_totals, uint32_t* error_out);
+
+/* What the binning stage of the last completed, synchronous bgs_render left on the device, copied to host memory as it is
+ * — at ANY pipeline depth: a synchronous frame runs on lane 0, with the 1024-thread bin_kernel at depth 1 and the
+ * 256-thread one at any other. By the frame's binning mode (info_out->binning):
+ *   BGS_BINNING_SCAN (0)  sup_edge, sup_x, sup_y, level (the supertile level the frame ran at), coarse_cap (entries per list
+ *                  the frame's last run was given), wide_bin; host_totals[sup_x * sup_y]: entries bin_kernel counted per
+ *                  supertile list (past coarse_cap where a list overflowed); host_entries: the first min(total, coarse_cap)
+ *                  entries (rank, packed tile rectangle: two words) of list 0, then of list 1, ...: entry_count in all;
+ *   BGS_BINNING_SORT (1)  instance_count; host_entries: the instance_count tile-sorted instances (tile id ty << 8 | tx, rank);
+ *                  host_ranges: the 65 536 [start, end) pairs of the tile ranges, indexed by tile id (131 072 words).
+ * draw_count: the ranks the frame projected. With the three host pointers NULL only info_out is filled (a caller sizes its
+ * buffers with entry_count). Launches no kernel. BGS_EINVAL, with the reason in bgs_last_error, when no frame has been
+ * rendered (or a bgs_sort / bgs_radix_sort_pairs ran since), when frames are in flight, when the last frame was an async
+ * one, and when a capacity (words) is too small — nothing is written then. Test hook. */
+typedef struct bgs_frame_lists_info {
+    uint64_t entry_count;
+    uint32_t binning, draw_count;
+    uint32_t sup_edge, sup_x, sup_y, level, coarse_cap, wide_bin;
+    uint32_t instance_count, reserved;
+} bgs_frame_lists_info;
+int bgs_debug_frame_lists(bgs_ctx* ctx, uint32_t* host_totals, uint32_t totals_capacity_words, uint32_t* host_entries,
+                          uint64_t entries_capacity_words, uint32_t* host_ranges, uint32_t ranges_capacity_words,
+                          bgs_frame_lists_info* info_out);
+
 #ifdef __cplusplus
 }
 #endif
