@@ -31,7 +31,7 @@ STAGE_NAMES = ("keygen", "depth_sort", "project", "tile_sort", "ranges", "raster
 COMM_ID_BYTES = 128
 # what this binding was written against (include/bgs.h BGS_VERSION_*): load() hands it to bgs_abi_check together with
 # the sizes of its ctypes structs
-ABI_VERSION = (0 << 16) | 5
+ABI_VERSION = (0 << 16) | 6
 
 
 class BgsSortEntry(ctypes.Structure):
@@ -80,6 +80,7 @@ class BgsFrameListsInfo(ctypes.Structure):
 
 
 SELFTEST_BIN_GUARD = 64   # BGS_SELFTEST_BIN_GUARD (include/bgs_diag.h)
+SELFTEST_BUCKET_GUARD = 64   # BGS_SELFTEST_BUCKET_GUARD (include/bgs_diag.h)
 
 
 vp, u32, u64 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64
@@ -155,6 +156,8 @@ PROTOTYPES = (
     ("bgs_debug_frame_records", c_int, (vp, vp, u64, up, u32, POINTER(BgsFrameRecordsInfo))),
     ("bgs_selftest_bin", c_int, (vp, up, u32, u32, u32, u32, u32, u32, u32, up, u64, up, up)),
     ("bgs_debug_frame_lists", c_int, (vp, up, u32, up, u64, up, u32, POINTER(BgsFrameListsInfo))),
+    ("bgs_selftest_bucket_sort", c_int, (vp, u32, u32, u32, up, up, u32, up, u64, up)),
+    ("bgs_selftest_keygen_buckets", c_int, (vp, vp, view_p, settings_p, up, u32, u32, u32, u32, up, up, u64, up, u64, up)),
 )
 EXPORTED_SYMBOLS = tuple(name for name, _, _ in PROTOTYPES)
 

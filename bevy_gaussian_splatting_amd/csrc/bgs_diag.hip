@@ -367,4 +367,140 @@ int bgs_debug_frame_lists(bgs_ctx* ctx, uint32_t* host_totals, uint32_t totals_c
     return BGS_OK;
 }
 
+// bucket_sort_kernel alone, on the caller's bucket contents: a zeroed Control with the caller's counts, slot regions that
+// hold each bucket's pairs at their start and 0xFF bytes behind them, an output list of n + BGS_SELFTEST_BUCKET_GUARD entries
+// of 0xFF bytes. What the kernel indexes (sort_kernels.hip): bucket_count[i < nb], a region's first min(count, cap) slots
+// (a launch with some count over cap reads no slot at all), out[offset of the bucket + rank < n]: any counts are in bounds
+// once pair_count is their clamped sum, so only the geometry is refused.
+int bgs_selftest_bucket_sort(bgs_ctx* ctx, uint32_t sub, uint32_t wide, uint32_t key_xor, const uint32_t* host_counts,
+                             const uint32_t* host_pairs, uint32_t pair_count, uint32_t* host_out, uint64_t out_capacity_words,
+                             uint32_t* info_out) {
+    if (!ctx) return fail(nullptr, BGS_EINVAL, "ctx is NULL");
+    if (!host_counts || !host_out || !info_out || (!host_pairs && pair_count))
+        return fail(ctx, BGS_EINVAL, "bucket self-test: host_counts, host_pairs, host_out and info_out must be non-NULL");
+    if (sub < 1u || sub > BUCKET_SUB_MAX) return fail(ctx, BGS_EINVAL, "bucket self-test: sub must be 1 .. 16, got " + std::to_string(sub));
+    if (wide > 1u) return fail(ctx, BGS_EINVAL, "bucket self-test: wide must be 0 or 1, got " + std::to_string(wide));
+    const uint32_t nb = BUCKET_COUNT * sub, cap = wide ? BUCKET_CAP_WIDE : BUCKET_CAP;
+    uint64_t n = 0;
+    for (uint32_t b = 0; b < nb; ++b) n += std::min(host_counts[b], cap);
+    if (n != pair_count)
+        return fail(ctx, BGS_EINVAL, "bucket self-test: pair_count is " + std::to_string(pair_count) + ", host_counts asks for " + std::to_string(n) +
+                                         " pairs (the sum of min(count, capacity))");
+    const uint64_t out_words = (n + BGS_SELFTEST_BUCKET_GUARD) * 2u;
+    if (out_capacity_words < out_words)
+        return fail(ctx, BGS_EINVAL, "bucket self-test: host_out holds " + std::to_string(out_capacity_words) + " words, the list and its guard are " +
+                                         std::to_string(out_words));
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, BGS_EHIP, "hipSetDevice failed");
+    int rc = finish_all(ctx);
+    if (rc != BGS_OK) return rc;
+    DeviceBuffer<uint2> slots_buf, out_buf;
+    DeviceBuffer<Control> ctl_buf;
+    if (!slots_buf.reserve((size_t)nb * cap) || !out_buf.reserve((size_t)(n + BGS_SELFTEST_BUCKET_GUARD)) || !ctl_buf.reserve(1))
+        return fail(ctx, BGS_ENOMEM, "hipMalloc(bucket self-test) failed");
+    Control* const ctl = ctl_buf.ptr;
+    hipStream_t st = ctx->lanes[0].stream;
+    bool ok = hipMemsetAsync(ctl, 0, sizeof(Control), st) == hipSuccess &&
+              hipMemsetAsync(slots_buf.ptr, 0xFF, (size_t)nb * cap * sizeof(uint2), st) == hipSuccess &&
+              hipMemsetAsync(out_buf.ptr, 0xFF, (size_t)out_words * sizeof(uint32_t), st) == hipSuccess &&
+              hipMemcpyAsync(ctl->bucket_count, host_counts, (size_t)nb * sizeof(uint32_t), hipMemcpyHostToDevice, st) == hipSuccess;
+    uint64_t at = 0;
+    for (uint32_t b = 0; ok && b < nb; ++b) {
+        const uint32_t len = std::min(host_counts[b], cap);
+        if (len) ok = hipMemcpyAsync(slots_buf.ptr + (size_t)b * cap, host_pairs + at * 2u, (size_t)len * sizeof(uint2), hipMemcpyHostToDevice, st) == hipSuccess;
+        at += len;
+    }
+    if (ok) {
+        ok = launch_bucket_sort(st, slots_buf.ptr, out_buf.ptr, ctl, key_xor, nb, wide != 0u) == hipSuccess && hipGetLastError() == hipSuccess &&
+             hipMemcpyAsync(host_out, out_buf.ptr, (size_t)out_words * sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
+             hipMemcpyAsync(&info_out[0], &ctl->draw_count, sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
+             hipMemcpyAsync(&info_out[1], &ctl->sort_overflow, sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
+             hipMemcpyAsync(&info_out[2], &ctl->bucket_max, sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
+             hipStreamSynchronize(st) == hipSuccess;
+    }
+    if (!ok) { (void)hipGetLastError(); return fail(ctx, BGS_EHIP, "bucket self-test failed on the device"); }
+    return BGS_OK;
+}
+
+// keygen's bucket placement alone: the KeygenLaunch of a bucket frame (bgs_frame.hip, enqueue_frame) with buffers of the
+// call's own. What keygen_kernel<.., BUCKET = true, ..> indexes (sort_kernels.hip): pos[i < n]; bucket_count[bucket < nb];
+// bucket_slots[bucket * cap + slot < cap]; the table's first nb - 1 keys (kernel arguments or device_keys); with ORDERED
+// the tile's chain word part_status[tile < ceil(n / 2048)], ticket[ticket_slot][0] and culled[i - drawable before i < n].
+// entries, fp_out, zero_word and bucket_status stay null: a bucket keygen writes no index-ordered list, and the other three
+// are optional (bucket_status is unused).
+int bgs_selftest_keygen_buckets(bgs_ctx* ctx, const bgs_cloud* cloud, const bgs_view* view, const bgs_settings* settings,
+                                const uint32_t* host_splitters, uint32_t sub, uint32_t wide_buckets, uint32_t ordered,
+                                uint32_t alone, uint32_t* host_counts, uint32_t* host_slots, uint64_t slots_capacity_words,
+                                uint32_t* host_culled, uint64_t culled_capacity_words, uint32_t* info_out) {
+    if (!ctx) return fail(nullptr, BGS_EINVAL, "ctx is NULL");
+    if (!cloud || !view || !settings || !host_splitters || !host_counts || !host_slots || !info_out)
+        return fail(ctx, BGS_EINVAL, "keygen self-test: cloud, view, settings, host_splitters, host_counts, host_slots and info_out must be non-NULL");
+    const uint32_t n = cloud->ptrs.n;
+    if (n < 1u || n > MAX_SPLATS) return fail(ctx, BGS_EINVAL, "keygen self-test: the cloud must hold 1 .. 2^30 - 1 splats, got " + std::to_string(n));
+    if (sub < 1u || sub > BUCKET_SUB_MAX) return fail(ctx, BGS_EINVAL, "keygen self-test: sub must be 1 .. 16, got " + std::to_string(sub));
+    if (wide_buckets > 1u) return fail(ctx, BGS_EINVAL, "keygen self-test: wide_buckets must be 0 or 1, got " + std::to_string(wide_buckets));
+    if (ordered > 1u) return fail(ctx, BGS_EINVAL, "keygen self-test: ordered must be 0 or 1, got " + std::to_string(ordered));
+    if (alone > 1u) return fail(ctx, BGS_EINVAL, "keygen self-test: alone must be 0 or 1, got " + std::to_string(alone));
+    if (settings->sort_mode > BGS_SORT_STD) return fail(ctx, BGS_EINVAL, "keygen self-test: unknown sort_mode");
+    if (settings->radix_depth_bits != 16 && settings->radix_depth_bits != 24 && settings->radix_depth_bits != 32)
+        return fail(ctx, BGS_EINVAL, "keygen self-test: radix_depth_bits must be 16, 24 or 32");
+    const uint32_t nb = BUCKET_COUNT * sub, cap = wide_buckets ? BUCKET_CAP_WIDE : BUCKET_CAP, nkeys = nb - 1u;
+    for (uint32_t t = 1; t < nkeys; ++t)
+        if (host_splitters[t] < host_splitters[t - 1u])
+            return fail(ctx, BGS_EINVAL, "keygen self-test: host_splitters must ascend, entry " + std::to_string(t) + " is below entry " + std::to_string(t - 1u));
+    const uint64_t slot_words = (uint64_t)nb * cap * 2u;
+    if (slots_capacity_words < slot_words)
+        return fail(ctx, BGS_EINVAL, "keygen self-test: host_slots holds " + std::to_string(slots_capacity_words) + " words, the slot regions are " +
+                                         std::to_string(slot_words));
+    if (ordered && (!host_culled || culled_capacity_words < (uint64_t)n * 2u))
+        return fail(ctx, BGS_EINVAL, "keygen self-test: host_culled must hold " + std::to_string((uint64_t)n * 2u) + " words with ordered = 1");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, BGS_EHIP, "hipSetDevice failed");
+    int rc = finish_all(ctx);
+    if (rc != BGS_OK) return rc;
+    const size_t status_words = (size_t)(n + KEYGEN_TILE - 1u) / KEYGEN_TILE + 1u;
+    DeviceBuffer<uint2> slots_buf, culled_buf;
+    DeviceBuffer<uint32_t> status_buf, keys_buf;
+    DeviceBuffer<Control> ctl_buf;
+    if (!slots_buf.reserve((size_t)nb * cap) || !status_buf.reserve(status_words) || !ctl_buf.reserve(1) ||
+        (ordered && !culled_buf.reserve(n)) || (sub > BUCKET_SUB_KERNARG && !keys_buf.reserve(nkeys)))
+        return fail(ctx, BGS_ENOMEM, "hipMalloc(keygen self-test) failed");
+    Control* const ctl = ctl_buf.ptr;
+    hipStream_t st = ctx->lanes[0].stream;
+    KeygenLaunch kg{};
+    fill_frame_params(n, view, settings, kg.fp);
+    kg.fp.sort_path = 1u;
+    kg.pos = cloud->ptrs.position_visibility;
+    kg.culled = ordered ? culled_buf.ptr : nullptr;   // (null: the chainless instantiation, as in every rendered frame)
+    kg.ctl = ctl;
+    kg.part_status = status_buf.ptr;
+    kg.places = 4u;
+    kg.ticket_slot = 7u;
+    kg.bucket_slots = slots_buf.ptr;
+    if (sub <= BUCKET_SUB_KERNARG) std::memcpy(kg.split.key, host_splitters, (size_t)nkeys * sizeof(uint32_t));
+    kg.split.device_keys = keys_buf.ptr;
+    kg.split.sub = sub;
+    kg.split.wide = wide_buckets;
+    kg.wide = alone != 0u;
+    if (!kg.prepare(ctx->num_cus * 4)) return fail(ctx, BGS_EINTERNAL, "keygen self-test: nothing to launch");
+    bool ok = hipMemsetAsync(ctl, 0, sizeof(Control), st) == hipSuccess &&
+              hipMemsetAsync(status_buf.ptr, 0, status_words * sizeof(uint32_t), st) == hipSuccess &&
+              hipMemsetAsync(slots_buf.ptr, 0xFF, (size_t)slot_words * sizeof(uint32_t), st) == hipSuccess &&
+              (!ordered || hipMemsetAsync(culled_buf.ptr, 0xFF, (size_t)n * sizeof(uint2), st) == hipSuccess) &&
+              (sub <= BUCKET_SUB_KERNARG ||
+               hipMemcpyAsync(keys_buf.ptr, host_splitters, (size_t)nkeys * sizeof(uint32_t), hipMemcpyHostToDevice, st) == hipSuccess);
+    if (ok) {
+        ok = kg.launch(st) == hipSuccess && hipGetLastError() == hipSuccess &&
+             hipMemcpyAsync(host_counts, ctl->bucket_count, (size_t)nb * sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
+             hipMemcpyAsync(host_slots, slots_buf.ptr, (size_t)slot_words * sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
+             (!ordered || hipMemcpyAsync(host_culled, culled_buf.ptr, (size_t)n * sizeof(uint2), hipMemcpyDeviceToHost, st) == hipSuccess) &&
+             hipMemcpyAsync(&info_out[0], &ctl->draw_count, sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
+             hipMemcpyAsync(&info_out[1], &ctl->splat_count, sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
+             hipMemcpyAsync(&info_out[2], &ctl->error, sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
+             hipStreamSynchronize(st) == hipSuccess;
+    }
+    if (!ok) { (void)hipGetLastError(); return fail(ctx, BGS_EHIP, "keygen self-test failed on the device"); }
+    info_out[3] = kg.threads;
+    info_out[4] = kg.blocks;
+    return BGS_OK;
+}
+
 }  // extern "C"

@@ -739,6 +739,45 @@ class GaussianSplattingPlugin:
             out.update(instance_count=int(info.instance_count), instances=entries[:count], ranges=ranges)
         return out
 
+    def selftest_bucket_sort(self, sub: int, wide: int, key_xor: int, counts: np.ndarray, pairs: np.ndarray) -> dict:
+        """`bgs_selftest_bucket_sort`: bucket_sort_kernel alone on `counts` uint32[256 * sub] (Control::bucket_count) and
+        `pairs` uint32[n, 2] (key, index; bucket after bucket, min(count, capacity) of each, in arrival order). `out`
+        uint32[n, 2] (key ^ key_xor, index; what the kernel did not write holds 0xFFFFFFFF), `guard` uint32[64, 2] (the
+        entries behind the list), `draw_count`, `sort_overflow`, `bucket_max`. Test hook (see include/bgs_diag.h)."""
+        c = np.ascontiguousarray(counts, dtype=np.uint32)
+        p = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+        n = p.shape[0]
+        out = np.zeros((n + _native.SELFTEST_BUCKET_GUARD, 2), np.uint32)
+        info = np.zeros(3, np.uint32)
+        if 1 <= int(sub) <= 16 and c.size != 256 * int(sub):   # (any other sub is the library's to refuse)
+            raise ValueError("counts holds one word per bucket: 256 * sub")
+        self._check(self._lib.bgs_selftest_bucket_sort(self._ctx, int(sub), int(wide), int(key_xor) & 0xFFFFFFFF, _uptr(c), _uptr(p), n,
+                                                       _uptr(out), out.size, _uptr(info)))
+        return {"out": out[:n], "guard": out[n:], "draw_count": int(info[0]), "sort_overflow": int(info[1]), "bucket_max": int(info[2])}
+
+    def selftest_keygen_buckets(self, handle: PlanarGaussian3dHandle, view: View, settings: CloudSettings, splitters: np.ndarray,
+                                sub: int, wide_buckets: int = 0, ordered: int = 0, alone: int = 0) -> dict:
+        """`bgs_selftest_keygen_buckets`: keygen's bucket placement alone with the table `splitters` uint32[256 * sub - 1]
+        (keygen's key space, ascending). `counts` uint32[256 * sub], `slots` uint32[256 * sub, capacity, 2] (key, index;
+        unwritten slots hold 0xFFFFFFFF), `culled` uint32[n, 2] (ordered only, else None), `draw_count`, `splat_count`,
+        `error`, `threads`, `blocks`. Test hook (see include/bgs_diag.h)."""
+        t = np.ascontiguousarray(splitters, dtype=np.uint32)
+        nb = 256 * min(max(int(sub), 1), 16)   # (a sub outside 1 .. 16 is the library's to refuse)
+        if 1 <= int(sub) <= 16 and t.size != nb - 1:
+            raise ValueError("splitters holds 256 * sub - 1 keys")
+        cap = 16384 if int(wide_buckets) == 1 else 4096
+        counts = np.zeros(nb, np.uint32)
+        slots = np.zeros((nb, cap, 2), np.uint32)
+        culled = np.zeros((handle.n, 2), np.uint32) if int(ordered) == 1 else None
+        info = np.zeros(5, np.uint32)
+        v, s = view.to_native(), settings.to_native()
+        self._check(self._lib.bgs_selftest_keygen_buckets(self._ctx, handle._ptr, ctypes.byref(v), ctypes.byref(s), _uptr(t), int(sub),
+                                                          int(wide_buckets), int(ordered), int(alone), _uptr(counts), _uptr(slots), slots.size,
+                                                          _uptr(culled) if culled is not None else None,
+                                                          culled.size if culled is not None else 0, _uptr(info)))
+        return {"counts": counts, "slots": slots, "culled": culled, "draw_count": int(info[0]), "splat_count": int(info[1]),
+                "error": int(info[2]), "threads": int(info[3]), "blocks": int(info[4])}
+
     def set_pipeline_streams(self, streams: int) -> None:
         """HIP streams the lanes are multiplexed onto (0 = one per lane); see bgs_set_pipeline_streams."""
         self._check(self._lib.bgs_set_pipeline_streams(self._ctx, int(streams)))

@@ -43,7 +43,9 @@ extern "C" {
 #endif
 
 #define BGS_VERSION_MAJOR 0
-#define BGS_VERSION_MINOR 5 /* 0.5: the binning stage's test hooks (bgs_diag.h: bgs_selftest_bin, bgs_debug_frame_lists); the seam of
+#define BGS_VERSION_MINOR 6 /* 0.6: the bucket sort path's test hooks (bgs_diag.h: bgs_selftest_bucket_sort, bgs_selftest_keygen_buckets); the
+                               seam of this header, bgs_view, bgs_settings and bgs_stats as in 0.4.
+                               0.5: the binning stage's test hooks (bgs_diag.h: bgs_selftest_bin, bgs_debug_frame_lists); the seam of
                                this header, bgs_view, bgs_settings and bgs_stats as in 0.4.
                                0.4: bgs_abi_check, bgs_comm_* (the multi-GPU frame gather), sample_count 0 = default; struct layouts as 0.3
                                (0.3: bgs_view gained sample_count + depth_device_ptr, 16 bytes longer; bgs_stats 16 bytes longer than 0.2's).

@@ -192,6 +192,52 @@ int bgs_debug_frame_lists(bgs_ctx* ctx, uint32_t* host_totals, uint32_t totals_c
                           uint64_t entries_capacity_words, uint32_t* host_ranges, uint32_t ranges_capacity_words,
                           bgs_frame_lists_info* info_out);
 
+/* bucket_sort_kernel (the default depth sort behind keygen's bucket placement) alone, launched once through the frames' own
+ * launcher on caller-supplied bucket contents: nb = 256 * sub buckets; `wide` 0 is the 256-thread instantiation on slot
+ * regions of 4096 pairs, 1 the 1024-thread one on regions of 16 384; key_xor is XOR-ed into every key on output.
+ *   host_counts    nb words: what Control::bucket_count holds. A count may exceed the region's capacity `cap`;
+ *   host_pairs     the pairs (key, index: two words), bucket after bucket, min(count, cap) of each, in the arrival order the
+ *                  caller wants; pair_count = their number n. The hook puts each bucket's pairs at the start of its slot
+ *                  region and fills the rest of every region with 0xFF bytes.
+ * Everything the kernel reads or writes is allocated for the call: a zeroed Control block with the counts, the regions,
+ * and an output list of n + BGS_SELFTEST_BUCKET_GUARD entries filled with 0xFF bytes. Returned as they are:
+ *   host_out       (n + BGS_SELFTEST_BUCKET_GUARD) entries of two words (key ^ key_xor, index); out_capacity_words: the
+ *                  words host_out holds;
+ *   info_out       3 words: Control::draw_count, Control::sort_overflow (bit 0: a count over the capacity, bit 1: more than
+ *                  BUCKET_FINE_MAX = 1024 pairs in one fine range of a bucket), Control::bucket_max.
+ * BGS_EINVAL, naming the argument, for what the kernel's own indexing does not allow: 1 <= sub <= 16, wide 0 / 1, the
+ * pointers non-NULL, pair_count = the sum of min(count, cap), and a host_out that is too small (nothing is launched then).
+ * Completes the frames in flight. Test hook (tests/test_bucket_stage_gpu.py). */
+#define BGS_SELFTEST_BUCKET_GUARD 64u
+int bgs_selftest_bucket_sort(bgs_ctx* ctx, uint32_t sub, uint32_t wide, uint32_t key_xor, const uint32_t* host_counts,
+                             const uint32_t* host_pairs, uint32_t pair_count, uint32_t* host_out, uint64_t out_capacity_words,
+                             uint32_t* info_out);
+
+/* keygen's bucket placement alone: keygen_kernel, launched once through the frames' own KeygenLaunch on a resident cloud
+ * with a caller-supplied splitter table host_splitters[256 * sub - 1] — keygen's key space, the one a completed frame's
+ * quantile keys are in (sorted key ^ 0xFFFFFFFF for BGS_SORT_RAYON / BGS_SORT_STD), non-strictly ascending. As in a frame,
+ * a table of sub <= 3 travels in the kernel arguments and a longer one is copied to a device table first.
+ *   wide_buckets   slot regions of 16 384 pairs instead of 4096 (cap);
+ *   ordered        0: the chainless instantiation of rendered frames; 1: bgs_sort's, with the tile chain and the culled tail;
+ *   alone          KeygenLaunch::wide, what a frame at pipeline depth 1 sets: 4096-splat tiles (clouds of 2^19 splats or
+ *                  more) run as 1024 threads x 4 instead of 256 x 16.
+ * Everything the kernel writes is allocated for the call: a zeroed Control block, zeroed chain words, and the slot regions
+ * and the culled list filled with 0xFF bytes. Returned as they are:
+ *   host_counts    256 * sub words: Control::bucket_count (counted past cap where a bucket overflows);
+ *   host_slots     256 * sub regions of cap entries of two words (key, index); slots_capacity_words: the words it holds;
+ *   host_culled    ordered = 1 only (else it may be NULL): bgs_cloud_len entries of two words, the culled splats (key = the
+ *                  culled sentinel) in index order, then the fill; culled_capacity_words: the words it holds;
+ *   info_out       5 words: Control::draw_count, Control::splat_count and Control::error (the look-back watchdog) — the
+ *                  words keygen publishes; the chainless instantiation leaves draw_count to bucket_sort_kernel and
+ *                  publishes splat_count only —, then the launch's threads per workgroup and its workgroups.
+ * BGS_EINVAL, naming the argument: NULL pointers, an empty cloud, sub outside 1 .. 16, a flag that is not 0 / 1, settings
+ * bgs_sort would refuse (sort_mode, radix_depth_bits), a table that descends somewhere, a capacity that is too small
+ * (nothing is launched then). Completes the frames in flight. Test hook (tests/test_bucket_stage_gpu.py). */
+int bgs_selftest_keygen_buckets(bgs_ctx* ctx, const bgs_cloud* cloud, const bgs_view* view, const bgs_settings* settings,
+                                const uint32_t* host_splitters, uint32_t sub, uint32_t wide_buckets, uint32_t ordered,
+                                uint32_t alone, uint32_t* host_counts, uint32_t* host_slots, uint64_t slots_capacity_words,
+                                uint32_t* host_culled, uint64_t culled_capacity_words, uint32_t* info_out);
+
 #ifdef __cplusplus
 }
 #endif
