@@ -71,23 +71,25 @@ constexpr int EV_COUNT = BGS_STAGE_COUNT + 1;
 constexpr int EV_RING = 64;   // per-stage timings are averaged over up to this many frames per lane
 constexpr int MAX_LANES = 8;
 
-// What the launches of a captured frame depend on besides FrameParams (which one node carries, see
-// KeygenLaunch): compared bytewise, any difference rebuilds the graph.
+// What the launches of a captured frame depend on besides what its first node carries (FrameParams; a kept-order
+// frame's chunk address too: KeygenLaunch, EntriesLaunch): compared bytewise, any difference rebuilds the graph.
 struct GraphKey {
     const void* cloud[6];
     const void* bufs[11];
     uint32_t n, format, places, sort_mode, gaussian_mode, aabb, any_mode, srgb8, debug_flags;
     int32_t width, height;
-    int32_t sort_blocks, bin_blocks, keygen_blocks;
+    int32_t sort_blocks, bin_blocks, front_blocks;
     uint32_t sup_edge;
     // the offsets baked into the nodes depend on the scratch layout and the list capacity, not only on
     // the base pointers (a re-allocation may return the same address)
     ScratchLayout scratch;
     uint32_t coarse_cap, sort_path;
-    // keygen has several instantiations per size (with / without chains, 256- or 1024-thread tiles: KeygenLaunch): a
-    // captured node is only ever UPDATED to the kernel and block size it was captured with
-    const void* keygen_func;
-    uint32_t keygen_threads;
+    // The front node (FrameGraph::front_node): keygen, or a kept-order frame's compaction (EntriesLaunch). keygen has
+    // several instantiations per size (with / without chains, 256- or 1024-thread tiles: KeygenLaunch), the compaction
+    // two (with / without the skipped tail): a captured node is only ever UPDATED to the kernel, grid (front_blocks) and
+    // block size it was captured with
+    const void* front_func;
+    uint32_t front_threads;
     uint32_t wide_bin;         // bin_kernel<16> (1024 threads) or <4>: follows the pipeline depth, not the grid sizes
     uint32_t raster_variant;   // the launched rasteriser instantiation: samples | depth << 8 | overlay << 9 | mode (graph_key)
     uint32_t split_sub;        // FrameCleanup::split_sub, a rasteriser argument: how many quantile keys the captured clean-up leaves
@@ -95,7 +97,7 @@ struct GraphKey {
 struct FrameGraph {
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
-    hipGraphNode_t keygen_node = nullptr;
+    hipGraphNode_t front_node = nullptr;   // the graph's root, the one node a replay updates: keygen, or the kept-order compaction
     GraphKey key{};
 };
 
@@ -147,7 +149,9 @@ struct Lane {
     hipStream_t stream = nullptr;  // owned by the context; lanes may share one (bgs_set_pipeline_streams)
     hipEvent_t done = nullptr;     // recorded behind the lane's frame: what completing the lane waits for
     DeviceBuffer<FrameParams> d_fp;  // the frame's FrameParams as the kernels behind keygen read them
-    FrameGraph graph[2];          // the captured BINNING_SCAN frame, one per Control parity
+    // the captured BINNING_SCAN frames, one per kind (0 sorting, 1 kept order) and Control parity: a lane that alternates
+    // between the kinds replays both
+    FrameGraph graph[2][2];
 
     // zeroed-every-frame scratch and where its parts lie (scratch_layout, frame_params.h; grown monotonically in the
     // splat and the instance capacity it is laid out for)

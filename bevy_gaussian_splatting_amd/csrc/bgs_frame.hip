@@ -88,7 +88,8 @@ void graph_destroy(FrameGraph& g) {
 
 void lane_destroy(Lane& L) {
     if (L.stream) (void)hipStreamSynchronize(L.stream);
-    for (auto& g : L.graph) graph_destroy(g);
+    for (auto& kind : L.graph)
+        for (auto& g : kind) graph_destroy(g);
     for (auto& slot : L.ev_ring)
         for (auto ev : slot) if (ev) (void)hipEventDestroy(ev);
     if (L.done) (void)hipEventDestroy(L.done);
@@ -819,15 +820,18 @@ FramePlan plan_frame(const bgs_ctx& ctx, const Lane& L, const FrameInputs& in) {
     // Measured: 7 launches cost 19 us of host time (30 us with stage events), a replay 10 us; on the
     // GPU a replayed frame is ~5 % SLOWER than the same launches issued directly (178 vs 171 us per
     // frame back to back on one stream), so it is for hosts that cannot spare the CPU time.
-    // A kept-order frame is launched directly, as timed frames are: the captured graph's one updatable node is keygen's.
+    // A kept-order frame is a graph of its own kind (Lane::graph): the compaction stands in keygen's place as the updated
+    // node, and its arguments carry the caller's chunk as well. (It is never a bucket frame: p.bucket_sub stays 1.)
     p.graph_ok = in.allow_graph && ctx.use_graphs && p.raster_cleans && p.bucket_sub <= BUCKET_SUB_KERNARG &&
-                 !(flags & BGS_DEBUG_NO_GRAPHS) && !ctx.tile_trace && !p.kept;
+                 !(flags & BGS_DEBUG_NO_GRAPHS) && !ctx.tile_trace;
     return p;
 }
 
 // What the launches of a captured frame depend on besides FrameParams: the plan's choices and the buffers they were
-// bound to. Nothing that changes from frame to frame (the splitter slot, its epoch: keygen's node update carries them).
-GraphKey graph_key(const FramePlan& p, const FrameInputs& in, const Lane& L, const KeygenLaunch& kg, uint32_t coarse_cap) {
+// bound to. Nothing that changes from frame to frame (the splitter slot, its epoch, a kept order's chunk: the front node's
+// update carries them). `front`: the prepared KeygenLaunch or EntriesLaunch, whose kernel and grid the node keeps.
+template <class Front>
+GraphKey graph_key(const FramePlan& p, const FrameInputs& in, const Lane& L, const Front& front, uint32_t coarse_cap) {
     GraphKey key;
     std::memset(&key, 0, sizeof key);
     const FrameParams& fp = p.fp;
@@ -843,8 +847,8 @@ GraphKey graph_key(const FramePlan& p, const FrameInputs& in, const Lane& L, con
     key.debug_flags = in.debug_flags;
     key.width = fp.width; key.height = fp.height;
     key.sort_blocks = p.bucket ? 0 : p.sort_blocks;  // the bucket sort's grid is fixed
-    key.bin_blocks = p.bin_blocks * 4096 + p.binning_blocks;   // (the bin kernel's shape follows the pipeline depth, as keygen's does: key.keygen_threads)
-    key.keygen_blocks = (int32_t)kg.blocks; key.keygen_func = kg.func; key.keygen_threads = kg.threads;
+    key.bin_blocks = p.bin_blocks * 4096 + p.binning_blocks;   // (the bin kernel's shape follows the pipeline depth, as keygen's does: key.front_threads)
+    key.front_blocks = (int32_t)front.blocks; key.front_func = front.func; key.front_threads = front.threads;   // (kept: entries_blocks(n) of the compaction)
     key.wide_bin = p.wide_bin ? 1u : 0u;
     const RasterInst& r = p.raster;
     key.raster_variant = r.samples | (r.depth ? 0x100u : 0u) | (r.overlay ? 0x200u : 0u) | (r.mode == 1 ? 0x400u : r.mode == 2 ? 0x800u : 0u);
@@ -856,12 +860,11 @@ GraphKey graph_key(const FramePlan& p, const FrameInputs& in, const Lane& L, con
     return key;
 }
 
-// Replay the lane's graph of this key (keygen's node updated to this frame), or capture `issue` into a new one.
-template <class Issue>
-int launch_graph(bgs_ctx* ctx, Lane& L, const GraphKey& key, KeygenLaunch& kg, Issue&& issue) {
-    FrameGraph& G = L.graph[L.ctl_parity];
+// Replay the graph G of this key (its front node updated to this frame), or capture `issue` into a new one.
+template <class Front, class Issue>
+int launch_graph(bgs_ctx* ctx, Lane& L, FrameGraph& G, const GraphKey& key, Front& front, Issue&& issue) {
     if (G.exec && std::memcmp(&G.key, &key, sizeof key) == 0) {
-        HIP_TRY(ctx, kg.update_node(G.exec, G.keygen_node));
+        HIP_TRY(ctx, front.update_node(G.exec, G.front_node));
         ctx->graph_replays += 1;
     } else {
         graph_destroy(G);
@@ -871,7 +874,7 @@ int launch_graph(bgs_ctx* ctx, Lane& L, const GraphKey& key, KeygenLaunch& kg, I
         size_t roots = 1;
         if (ie != hipSuccess || ce != hipSuccess || !G.graph ||
             hipGraphInstantiate(&G.exec, G.graph, nullptr, nullptr, 0) != hipSuccess ||
-            hipGraphGetRootNodes(G.graph, &G.keygen_node, &roots) != hipSuccess || roots != 1) {
+            hipGraphGetRootNodes(G.graph, &G.front_node, &roots) != hipSuccess || roots != 1) {
             graph_destroy(G);
             (void)hipGetLastError();
             return fail(ctx, BGS_EHIP, "capturing the frame into a hipGraph failed");
@@ -971,7 +974,21 @@ int enqueue_frame(bgs_ctx* ctx, Lane& L, const FrameInputs& in) {
     }
     kg.wide = p.wide_bin;
     const bool have_keygen = !p.kept && kg.prepare(ctx->num_cus * 4);
-    const uint2* const kept_entries = reinterpret_cast<const uint2*>((uintptr_t)in.view.entries_device_ptr);
+    // a kept order: the compaction in keygen's place, leaving what keygen leaves (entries_kernels.hip)
+    EntriesLaunch ek;   // (filled for a kept order only: a sorting frame's enqueue does not touch it)
+    bool have_compact = false;
+    if (p.kept) {
+        ek.fp = fp;
+        ek.entries = reinterpret_cast<const uint2*>((uintptr_t)in.view.entries_device_ptr);
+        ek.draw_list = draw_list;
+        ek.tail = kg.culled;
+        ek.ctl = ctl;
+        ek.part_status = part_status;
+        ek.ticket_slot = kg.ticket_slot;
+        ek.fp_out = L.d_fp.ptr;
+        ek.zero_word = kg.zero_word;
+        have_compact = ek.prepare();
+    }
     FrameCleanup cl{};
     if (p.raster_cleans) {
         cl.part_status = part_status;
@@ -1023,9 +1040,8 @@ int enqueue_frame(bgs_ctx* ctx, Lane& L, const FrameInputs& in) {
             hipError_t e = kg.launch(st);
             if (e != hipSuccess) return e;
         }
-        if (p.kept) {   // in keygen's place, and leaving what keygen leaves (entries_kernels.hip)
-            const hipError_t e = launch_entries_compact(st, fp, kept_entries, draw_list, kg.culled, ctl, part_status, kg.ticket_slot,
-                                                        L.d_fp.ptr, kg.zero_word);
+        if (have_compact) {
+            const hipError_t e = ek.launch(st);
             if (e != hipSuccess) return e;
         }
         mark(1);
@@ -1072,7 +1088,9 @@ int enqueue_frame(bgs_ctx* ctx, Lane& L, const FrameInputs& in) {
         return hipGetLastError();
     };
     if (p.graph_ok && !need_memset && prof == 0 && have_keygen) {
-        if ((rc = launch_graph(ctx, L, graph_key(p, in, L, kg, coarse_cap), kg, issue)) != BGS_OK) return rc;
+        if ((rc = launch_graph(ctx, L, L.graph[0][L.ctl_parity], graph_key(p, in, L, kg, coarse_cap), kg, issue)) != BGS_OK) return rc;
+    } else if (p.graph_ok && !need_memset && prof == 0 && have_compact) {
+        if ((rc = launch_graph(ctx, L, L.graph[1][L.ctl_parity], graph_key(p, in, L, ek, coarse_cap), ek, issue)) != BGS_OK) return rc;
     } else {
         if (need_memset) HIP_TRY(ctx, hipMemsetAsync(scratch, 0, lay.bytes, st));
         // no keygen (empty cloud): the kernels behind it still read the frame's parameters

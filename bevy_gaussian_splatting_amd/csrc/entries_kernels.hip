@@ -13,6 +13,12 @@
 //   *zero_word = 0                          the heavy-tile list's count, if the frame has one
 //   part_status[0 .. ceil(n / 2048))        the chain's words, which the rasteriser's clean-up zeroes for ceil(n / KEYGEN_TILE)
 //   ctl->ticket[ticket_slot][0]             the tile counter (the Control block is zeroed as a whole)
+// Both are zero when the kernel starts, launched directly or replayed from a captured frame graph (EntriesLaunch,
+// kernels.h), because a BINNING_SCAN frame's LAST kernel re-zeroes them and that kernel is a node of the same graph: the
+// frame's own rasteriser zeroes part_status[0 .. ceil(fp.n / KEYGEN_TILE)) — KEYGEN_TILE == ENTRIES_TILE, fp.n read from
+// the parameters this kernel left —, and the rasteriser of the lane's PREVIOUS frame zeroed this frame's Control block
+// (FrameCleanup::other_ctl; the lane's frames alternate between two blocks and run in stream order). A lane whose
+// scratch is not known to be clean (Lane::scratch_clean) gets a memset and a direct launch, never a replay.
 //
 // GEOMETRY (entries_math.h). A tile is ENTRIES_TILE = 2048 slots = 256 threads x 8 items; a wave's 64 lanes hold 64
 // consecutive slots per item (a row), loaded and stored as 8-byte words: coalesced 512-byte rows. Inside a row the rank
@@ -35,6 +41,8 @@
 #include "lookback.h"
 
 namespace bgs {
+
+static_assert(ENTRIES_TILE == KEYGEN_TILE, "the rasteriser's clean-up zeroes one chain word per KEYGEN_TILE splats");
 
 namespace {
 
@@ -128,17 +136,29 @@ __global__ __launch_bounds__(ENTRIES_THREADS) void entries_compact_kernel(FrameP
     }
 }
 
-hipError_t launch_entries_compact(hipStream_t stream, const FrameParams& fp, const uint2* entries, uint2* draw_list, uint2* tail,
-                                  Control* ctl, uint32_t* part_status, uint32_t ticket_slot, FrameParams* fp_out, uint32_t* zero_word) {
-    if (fp.n == 0) return hipSuccess;
-    const dim3 grid(entries_blocks(fp.n)), block(ENTRIES_THREADS);
-    if (tail)
-        hipLaunchKernelGGL(entries_compact_kernel<true>, grid, block, 0, stream, fp, entries, draw_list, tail, ctl, part_status,
-                           ticket_slot, fp_out, zero_word);
-    else
-        hipLaunchKernelGGL(entries_compact_kernel<false>, grid, block, 0, stream, fp, entries, draw_list, tail, ctl, part_status,
-                           ticket_slot, fp_out, zero_word);
-    return hipGetLastError();
+bool EntriesLaunch::prepare() {
+    if (fp.n == 0) return false;
+    func = tail ? reinterpret_cast<const void*>(&entries_compact_kernel<true>) : reinterpret_cast<const void*>(&entries_compact_kernel<false>);
+    blocks = entries_blocks(fp.n);
+    threads = ENTRIES_THREADS;
+    argv[0] = &fp; argv[1] = &entries; argv[2] = &draw_list; argv[3] = &tail; argv[4] = &ctl;
+    argv[5] = &part_status; argv[6] = &ticket_slot; argv[7] = &fp_out; argv[8] = &zero_word;
+    return true;
+}
+
+hipError_t EntriesLaunch::launch(hipStream_t stream) {
+    return hipLaunchKernel(func, dim3(blocks), dim3(threads), argv, 0, stream);
+}
+
+hipError_t EntriesLaunch::update_node(hipGraphExec_t exec, hipGraphNode_t node) {
+    hipKernelNodeParams np{};
+    np.func = const_cast<void*>(func);
+    np.gridDim = dim3(blocks);
+    np.blockDim = dim3(threads);
+    np.sharedMemBytes = 0;
+    np.kernelParams = argv;
+    np.extra = nullptr;
+    return hipGraphExecKernelNodeSetParams(exec, node, &np);
 }
 
 }  // namespace bgs

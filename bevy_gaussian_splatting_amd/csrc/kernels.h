@@ -115,9 +115,27 @@ inline uint32_t keygen_tile_splats(uint32_t n) { return n >= (1u << BGS_KEYGEN_H
 // The front end of a kept-order frame (bgs_view.entries_device_ptr; entries_kernels.hip) in keygen's place: the caller's
 // fp.n sorted entries -> draw_list, order kept, without the entries that cannot be drawn (key all-ones, index >= n);
 // ctl->draw_count = how many stayed. tail (or null): the skipped entries, in order (RasterizeMode::Depth reads them).
-// part_status, ticket_slot, fp_out, zero_word: as for keygen. Nothing is launched for fp.n == 0.
-hipError_t launch_entries_compact(hipStream_t stream, const FrameParams& fp, const uint2* entries, uint2* draw_list, uint2* tail,
-                                  Control* ctl, uint32_t* part_status, uint32_t ticket_slot, FrameParams* fp_out, uint32_t* zero_word);
+// part_status, ticket_slot, fp_out, zero_word: as for keygen. Like keygen it is the first node of a captured frame and
+// the one whose arguments a replay sets: fp AND entries change from frame to frame (a host with several cameras hands a
+// different chunk on the same lane), everything else is what the graph was captured with (GraphKey, bgs_context.h).
+struct EntriesLaunch {
+    FrameParams fp;
+    const uint2* entries;
+    uint2* draw_list;
+    uint2* tail;
+    Control* ctl;
+    uint32_t* part_status;
+    uint32_t ticket_slot;
+    FrameParams* fp_out;
+    uint32_t* zero_word;
+    // filled by prepare(): the launch geometry and the argument vector (points into this object)
+    const void* func;
+    uint32_t blocks, threads;
+    void* argv[9];
+    bool prepare();  // false: nothing to launch (n == 0)
+    hipError_t launch(hipStream_t stream);
+    hipError_t update_node(hipGraphExec_t exec, hipGraphNode_t node);  // same launch, as a graph node update
+};
 
 // Standalone digit histograms of existing pairs (used by bgs_radix_sort_pairs).
 void launch_histogram(hipStream_t stream, const uint2* pairs, uint32_t n, uint32_t* hist /*[4][256]*/,

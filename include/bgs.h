@@ -122,7 +122,9 @@ typedef struct bgs_view {
      *     index >= n among them read as n - 1.
      *     Works with both binning modes, every cloud format, sample count, raster / draw mode, the depth attachment, the
      *     packed outputs, particle steps, and asynchronous frames on every lane (no host round trip). Under
-     *     bgs_set_graphs(1) such a frame is launched directly, as timed frames are.
+     *     bgs_set_graphs(1) such a frame is replayed from a captured graph of its own kind, which a lane keeps beside the
+     *     one of its sorting frames: the compaction is the node that is updated, and its arguments carry the chunk, so
+     *     the chunk address may change between replays (a host with several cameras) without a new capture.
      *     Stats: sort_path = 2, depth_passes = 0, stage_ms[BGS_STAGE_KEYGEN] = the compaction of the chunk into the draw
      *     list, stage_ms[BGS_STAGE_DEPTH_SORT] = 0, draw_count = entries that pass the key / index test, visible_count
      *     as in every rendered frame (drawn splats that pass the vertex stage's tests). bgs_sorted_entries_device_ptr
@@ -460,7 +462,9 @@ int bgs_set_pipeline_streams(bgs_ctx* ctx, uint32_t streams);
 /* Frame graphs (opt-in, default off). An asynchronous BINNING_SCAN frame (bgs_set_async) in the
  * steady state is replayed from a hipGraph captured once per (lane, parity): the frame's first kernel
  * receives the new view/settings as its arguments (one graph-node update) and leaves them in device
- * memory for the kernels behind it. A replay costs the host ~10 us instead of ~19 us for 7 direct
+ * memory for the kernels behind it. A kept-order frame (bgs_view.entries_device_ptr) has a graph of its
+ * own per (lane, parity), whose first kernel also receives the chunk's address: a lane that draws
+ * kept and sorting frames in turn replays both. A replay costs the host ~10 us instead of ~19 us for 7 direct
  * launches, but runs ~5 % slower on the GPU than the same launches issued directly (measured), so it
  * is meant for hosts short of CPU time. The graph is rebuilt when anything else a launch depends on
  * changes (cloud, buffers, viewport size, pipeline variant, grid sizes, debug flags); frames whose
