@@ -31,7 +31,7 @@ STAGE_NAMES = ("keygen", "depth_sort", "project", "tile_sort", "ranges", "raster
 COMM_ID_BYTES = 128
 # what this binding was written against (include/bgs.h BGS_VERSION_*): load() hands it to bgs_abi_check together with
 # the sizes of its ctypes structs
-ABI_VERSION = (0 << 16) | 6
+ABI_VERSION = (0 << 16) | 7
 
 
 class BgsSortEntry(ctypes.Structure):
@@ -79,7 +79,20 @@ class BgsFrameListsInfo(ctypes.Structure):
                 ("reserved", ctypes.c_uint32)]
 
 
+class BgsRasterSelftest(ctypes.Structure):
+    """bgs_raster_selftest (include/bgs_diag.h)."""
+
+    _fields_ = [(name, ctypes.c_uint32) for name in ("width", "height", "sample_count", "variant", "overlay", "mode", "sup_edge",
+                                                     "coarse_cap", "color_max_bits", "record_count", "heavy_count", "reserved")] + \
+               [("viewport_w", ctypes.c_float), ("viewport_h", ctypes.c_float), ("clear", ctypes.c_float * 4)] + \
+               [(name, ctypes.c_void_p) for name in ("records", "lists", "totals", "depth", "heavy_tiles", "order")]
+
+
 SELFTEST_BIN_GUARD = 64   # BGS_SELFTEST_BIN_GUARD (include/bgs_diag.h)
+SELFTEST_RASTER_GUARD = 64   # BGS_SELFTEST_RASTER_GUARD (include/bgs_diag.h)
+# the HeavyFeedback buffer bgs_selftest_raster returns (csrc/kernels.h): [count | list u16[HEAVY_CAP] | flag u8[tiles]]
+HEAVY_CAP, HEAVY_LIST_OFFSET = 256, 128
+HEAVY_FLAGS_OFFSET = HEAVY_LIST_OFFSET + 2 * HEAVY_CAP
 SELFTEST_BUCKET_GUARD = 64   # BGS_SELFTEST_BUCKET_GUARD (include/bgs_diag.h)
 
 
@@ -158,6 +171,7 @@ PROTOTYPES = (
     ("bgs_debug_frame_lists", c_int, (vp, up, u32, up, u64, up, u32, POINTER(BgsFrameListsInfo))),
     ("bgs_selftest_bucket_sort", c_int, (vp, u32, u32, u32, up, up, u32, up, u64, up)),
     ("bgs_selftest_keygen_buckets", c_int, (vp, vp, view_p, settings_p, up, u32, u32, u32, u32, up, up, u64, up, u64, up)),
+    ("bgs_selftest_raster", c_int, (vp, POINTER(BgsRasterSelftest), fp, fp, u64, vp, vp, u64, up)),
 )
 EXPORTED_SYMBOLS = tuple(name for name, _, _ in PROTOTYPES)
 

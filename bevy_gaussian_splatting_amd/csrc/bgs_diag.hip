@@ -503,4 +503,176 @@ int bgs_selftest_keygen_buckets(bgs_ctx* ctx, const bgs_cloud* cloud, const bgs_
     return BGS_OK;
 }
 
+// The two rasterisers alone, on the caller's stage inputs. What the kernels index (render_kernels.hip), and what bounds it:
+//   raster_scan_kernel   coarse_total[st < supertiles <= 256]; list[st * coarse_cap + i], i < min(total, coarse_cap);
+//                        records[rank]: every rank in those positions is checked against record_count here; heavy_in's count
+//                        (<= HEAVY_CAP), list[sb < count] (tile ids checked here) and flags[tile < tiles]; order[block <
+//                        (tiles + 3) / 4] (a checked permutation, so every tile is drawn once); cost_out[tile], heavy_out's
+//                        list[at < HEAVY_CAP] and flags[tile]; the depth plane and the target at pixels inside width x height.
+//   raster_kernel        ranges[ty << 8 | tx] (65 536 entries), instances[range) and records[rank] of instances built here from
+//                        the checked lists; the same pixels.
+// The records' and rectangles' CONTENTS may be anything: no index is formed from them (a rectangle is only compared with the
+// tile's coordinates, a record only feeds arithmetic).
+int bgs_selftest_raster(bgs_ctx* ctx, const bgs_raster_selftest* in, float* host_scan, float* host_sort,
+                        uint64_t image_capacity_floats, uint16_t* host_cost, uint8_t* host_heavy, uint64_t heavy_capacity_bytes,
+                        uint32_t* error_out) {
+    if (!ctx) return fail(nullptr, BGS_EINVAL, "ctx is NULL");
+    if (!in || !host_scan || !host_sort || !host_cost || !host_heavy || !error_out)
+        return fail(ctx, BGS_EINVAL, "raster self-test: in, host_scan, host_sort, host_cost, host_heavy and error_out must be non-NULL");
+    const auto num = [](uint64_t v) { return std::to_string(v); };
+    if (in->width < 1u || in->width > 512u) return fail(ctx, BGS_EINVAL, "raster self-test: width must be 1 .. 512, got " + num(in->width));
+    if (in->height < 1u || in->height > 512u) return fail(ctx, BGS_EINVAL, "raster self-test: height must be 1 .. 512, got " + num(in->height));
+    const uint32_t ms = in->sample_count;
+    if (ms != 1u && ms != 2u && ms != 4u && ms != 8u) return fail(ctx, BGS_EINVAL, "raster self-test: sample_count must be 1, 2, 4 or 8, got " + num(ms));
+    if (in->variant > 2u) return fail(ctx, BGS_EINVAL, "raster self-test: variant must be 0 (OBB), 1 (AABB3D) or 2 (surfel), got " + num(in->variant));
+    if (in->overlay > 1u) return fail(ctx, BGS_EINVAL, "raster self-test: overlay must be 0 or 1, got " + num(in->overlay));
+    if (in->mode > 2u) return fail(ctx, BGS_EINVAL, "raster self-test: mode must be 0, 1 or 2, got " + num(in->mode));
+    if (in->mode != 0u) {
+        // what a frame can be given: raster_scan_mode at a low and a high supertile level, with the kind's say and frames in flight
+        const int lo = raster_scan_mode((int)in->variant, ms, in->overlay != 0u, 0u, true, 2, 0u);
+        const int hi = raster_scan_mode((int)in->variant, ms, in->overlay != 0u, 3u, true, 2, 0u);
+        if ((int)in->mode != lo && (int)in->mode != hi)
+            return fail(ctx, BGS_EINVAL, "raster self-test: mode " + num(in->mode) + " is never chosen for variant " + num(in->variant) + " at " + num(ms) +
+                                             " samples" + (in->overlay ? " with the overlay" : "") + " (raster_scan_mode)");
+    }
+    if (in->reserved != 0u) return fail(ctx, BGS_EINVAL, "raster self-test: reserved must be 0");
+    if (!(in->viewport_w > 0.0f) || !(in->viewport_h > 0.0f)) return fail(ctx, BGS_EINVAL, "raster self-test: viewport_w and viewport_h must be > 0");
+    const uint32_t tiles_x = (in->width + TILE_PX - 1u) / TILE_PX, tiles_y = (in->height + TILE_PX - 1u) / TILE_PX, ntiles = tiles_x * tiles_y;
+    if (in->sup_edge < 1u || in->sup_edge > 32u) return fail(ctx, BGS_EINVAL, "raster self-test: sup_edge must be 1 .. 32, got " + num(in->sup_edge));
+    if (!supertile_bins_fit(tiles_x, tiles_y, in->sup_edge))
+        return fail(ctx, BGS_EINVAL, "raster self-test: sup_edge " + num(in->sup_edge) + " gives more than " + num(MAX_SUPERTILES) +
+                                         " supertiles, or more than " + num(MAX_SUPERTILES_PER_AXIS) + " on an axis");
+    const uint32_t sup_x = (tiles_x + in->sup_edge - 1u) / in->sup_edge, sup_y = (tiles_y + in->sup_edge - 1u) / in->sup_edge, num_st = sup_x * sup_y;
+    const uint32_t cap = in->coarse_cap;
+    if (cap < 1u || (uint64_t)num_st * cap > (1ull << 20))
+        return fail(ctx, BGS_EINVAL, "raster self-test: coarse_cap must be >= 1 and supertiles x coarse_cap <= 2^20, got " + num(cap));
+    if (in->record_count > (1u << 20)) return fail(ctx, BGS_EINVAL, "raster self-test: record_count must be <= 2^20, got " + num(in->record_count));
+    if (!in->lists || !in->totals || (!in->records && in->record_count))
+        return fail(ctx, BGS_EINVAL, "raster self-test: records, lists and totals must be non-NULL");
+    for (uint32_t s = 0; s < num_st; ++s) {
+        const uint32_t len = std::min(in->totals[s], cap);
+        for (uint32_t i = 0; i < len; ++i) {
+            const uint32_t rank = in->lists[((size_t)s * cap + i) * 2u];
+            if (rank >= in->record_count)
+                return fail(ctx, BGS_EINVAL, "raster self-test: lists: entry " + num(i) + " of list " + num(s) + " holds rank " + num(rank) +
+                                                 ", record_count is " + num(in->record_count));
+        }
+    }
+    if (in->heavy_tiles || in->heavy_count) {
+        if (in->mode == 0u) return fail(ctx, BGS_EINVAL, "raster self-test: heavy_tiles needs mode 1 or 2 (the plain instantiation has no strip workgroups)");
+        if (!in->heavy_tiles || in->heavy_count > HEAVY_CAP)
+            return fail(ctx, BGS_EINVAL, "raster self-test: heavy_count must be <= " + num(HEAVY_CAP) + " with heavy_tiles non-NULL, got " + num(in->heavy_count));
+    }
+    std::vector<uint8_t> heavy_host(heavy_feedback_bytes(ntiles), 0u);
+    for (uint32_t i = 0; i < in->heavy_count; ++i) {
+        const uint32_t t = in->heavy_tiles[i];
+        if (t >= ntiles) return fail(ctx, BGS_EINVAL, "raster self-test: heavy_tiles[" + num(i) + "] is " + num(t) + ", the target has " + num(ntiles) + " tiles");
+        if (heavy_host[HEAVY_FLAGS_OFFSET + t]) return fail(ctx, BGS_EINVAL, "raster self-test: heavy_tiles names tile " + num(t) + " twice");
+        heavy_host[HEAVY_FLAGS_OFFSET + t] = 1u;
+        const uint16_t t16 = (uint16_t)t;
+        memcpy(&heavy_host[HEAVY_LIST_OFFSET + 2u * i], &t16, 2u);
+    }
+    memcpy(&heavy_host[0], &in->heavy_count, 4u);
+    const uint32_t nblocks = (ntiles + 3u) / 4u;
+    if (in->order) {
+        std::vector<uint8_t> seen(nblocks, 0u);
+        for (uint32_t b = 0; b < nblocks; ++b) {
+            const uint32_t g = in->order[b];
+            if (g >= nblocks || seen[g])
+                return fail(ctx, BGS_EINVAL, "raster self-test: order is not a permutation of 0 .. " + num(nblocks - 1u) + " (entry " + num(b) + " is " + num(g) + ")");
+            seen[g] = 1u;
+        }
+    }
+    const uint64_t pixels = (uint64_t)in->width * in->height, image_floats = (pixels + BGS_SELFTEST_RASTER_GUARD) * 4u;
+    if (image_capacity_floats < image_floats)
+        return fail(ctx, BGS_EINVAL, "raster self-test: host_scan / host_sort hold " + num(image_capacity_floats) + " floats, an image and its guard are " +
+                                         num(image_floats));
+    if (heavy_capacity_bytes < heavy_host.size())
+        return fail(ctx, BGS_EINVAL, "raster self-test: host_heavy holds " + num(heavy_capacity_bytes) + " bytes, the buffer is " + num(heavy_host.size()));
+    // the instance-sort rasteriser's inputs, from the same lists: per tile the entries of its supertile's list whose rectangle holds it
+    std::vector<uint2> instances;
+    std::vector<uint2> ranges((size_t)RADIX_BASE * RADIX_BASE, make_uint2(0u, 0u));
+    for (uint32_t ty = 0; ty < tiles_y; ++ty)
+        for (uint32_t tx = 0; tx < tiles_x; ++tx) {
+            const uint32_t s = (ty / in->sup_edge) * sup_x + tx / in->sup_edge, len = std::min(in->totals[s], cap);
+            const uint32_t start = (uint32_t)instances.size();
+            for (uint32_t i = 0; i < len; ++i) {
+                const uint32_t rank = in->lists[((size_t)s * cap + i) * 2u], rect = in->lists[((size_t)s * cap + i) * 2u + 1u];
+                if (tx >= (rect & 255u) && tx <= ((rect >> 8) & 255u) && ty >= ((rect >> 16) & 255u) && ty <= (rect >> 24))
+                    instances.push_back(make_uint2((ty << 8) | tx, rank));
+            }
+            if (instances.size() > (1u << 24)) return fail(ctx, BGS_EINVAL, "raster self-test: the lists hold more than 2^24 tile instances");
+            ranges[(ty << 8) | tx] = make_uint2(start, (uint32_t)instances.size());
+        }
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, BGS_EHIP, "hipSetDevice failed");
+    int rc = finish_all(ctx);
+    if (rc != BGS_OK) return rc;
+    const size_t stride = in->variant == (uint32_t)RV_SURFEL ? sizeof(RecordSurfel) : sizeof(Record);
+    const size_t list_words = (size_t)num_st * cap * 2u, depth_floats = (size_t)pixels * ms;
+    DeviceBuffer<uint8_t> rec_buf, heavy_in_buf, heavy_out_buf;
+    DeviceBuffer<uint32_t> lists_buf;
+    DeviceBuffer<float> depth_buf, scan_buf, sort_buf;
+    DeviceBuffer<uint2> inst_buf, ranges_buf;
+    DeviceBuffer<uint16_t> order_buf, cost_buf;
+    DeviceBuffer<Control> ctl_buf;
+    DeviceBuffer<FrameParams> fp_buf;
+    if (!rec_buf.reserve((size_t)in->record_count * stride) || !lists_buf.reserve(list_words) || !scan_buf.reserve((size_t)image_floats) ||
+        !sort_buf.reserve((size_t)image_floats) || !inst_buf.reserve(instances.size()) || !ranges_buf.reserve(ranges.size()) ||
+        !heavy_in_buf.reserve(heavy_host.size()) || !heavy_out_buf.reserve(heavy_host.size()) || !order_buf.reserve(nblocks) ||
+        !cost_buf.reserve(tile_cost_bytes(ntiles) / 2u) || !ctl_buf.reserve(1) || !fp_buf.reserve(1) || (in->depth && !depth_buf.reserve(depth_floats)))
+        return fail(ctx, BGS_ENOMEM, "hipMalloc(raster self-test) failed");
+    FrameParams fp;
+    memset(&fp, 0, sizeof fp);
+    fp.viewport_w = in->viewport_w;
+    fp.viewport_h = in->viewport_h;
+    fp.inv_viewport_w = 1.0f / in->viewport_w;
+    fp.inv_viewport_h = 1.0f / in->viewport_h;
+    fp.width = (int32_t)in->width;
+    fp.height = (int32_t)in->height;
+    fp.tiles_x = (int32_t)tiles_x;
+    fp.tiles_y = (int32_t)tiles_y;
+    fp.aabb = in->variant == (uint32_t)RV_OBB ? 0u : 1u;
+    fp.gaussian_mode = in->variant == (uint32_t)RV_SURFEL ? 0u : 1u;
+    fp.visualize_bbox = in->overlay;
+    fp.sample_count = ms;
+    fp.depth_ptr = in->depth ? (uint64_t)reinterpret_cast<uintptr_t>(depth_buf.ptr) : 0ull;
+    fp.n = in->record_count;
+    memcpy(fp.clear, in->clear, sizeof fp.clear);
+    Control* const ctl = ctl_buf.ptr;
+    hipStream_t st = ctx->lanes[0].stream;
+    bool ok = hipMemsetAsync(ctl, 0, sizeof(Control), st) == hipSuccess &&
+              hipMemsetAsync(scan_buf.ptr, 0xFF, (size_t)image_floats * sizeof(float), st) == hipSuccess &&
+              hipMemsetAsync(sort_buf.ptr, 0xFF, (size_t)image_floats * sizeof(float), st) == hipSuccess &&
+              hipMemsetAsync(cost_buf.ptr, 0xFF, tile_cost_bytes(ntiles), st) == hipSuccess &&
+              hipMemsetAsync(heavy_out_buf.ptr, 0, heavy_host.size(), st) == hipSuccess &&
+              hipMemcpyAsync(heavy_in_buf.ptr, heavy_host.data(), heavy_host.size(), hipMemcpyHostToDevice, st) == hipSuccess &&
+              hipMemcpyAsync(fp_buf.ptr, &fp, sizeof fp, hipMemcpyHostToDevice, st) == hipSuccess &&
+              hipMemcpyAsync(lists_buf.ptr, in->lists, list_words * sizeof(uint32_t), hipMemcpyHostToDevice, st) == hipSuccess &&
+              hipMemcpyAsync(ranges_buf.ptr, ranges.data(), ranges.size() * sizeof(uint2), hipMemcpyHostToDevice, st) == hipSuccess &&
+              hipMemcpyAsync(ctl->coarse_total, in->totals, (size_t)num_st * sizeof(uint32_t), hipMemcpyHostToDevice, st) == hipSuccess &&
+              hipMemcpyAsync(&ctl->color_max_bits, &in->color_max_bits, sizeof(uint32_t), hipMemcpyHostToDevice, st) == hipSuccess &&
+              hipMemcpyAsync(&ctl->draw_count, &in->record_count, sizeof(uint32_t), hipMemcpyHostToDevice, st) == hipSuccess;
+    if (ok && in->record_count) ok = hipMemcpyAsync(rec_buf.ptr, in->records, (size_t)in->record_count * stride, hipMemcpyHostToDevice, st) == hipSuccess;
+    if (ok && !instances.empty()) ok = hipMemcpyAsync(inst_buf.ptr, instances.data(), instances.size() * sizeof(uint2), hipMemcpyHostToDevice, st) == hipSuccess;
+    if (ok && in->depth) ok = hipMemcpyAsync(depth_buf.ptr, in->depth, depth_floats * sizeof(float), hipMemcpyHostToDevice, st) == hipSuccess;
+    if (ok && in->order) ok = hipMemcpyAsync(order_buf.ptr, in->order, (size_t)nblocks * sizeof(uint16_t), hipMemcpyHostToDevice, st) == hipSuccess;
+    if (ok) {
+        const bool exits = in->mode != 0u;
+        launch_raster_scan(st, fp, fp_buf.ptr, rec_buf.ptr, lists_buf.ptr, cap, in->sup_edge, ctl, reinterpret_cast<float4*>(scan_buf.ptr),
+                           /*srgb8_default=*/nullptr, /*out_format=*/0u, FrameCleanup{}, /*tile_trace=*/nullptr, (int)in->mode,
+                           exits && in->heavy_count ? heavy_in_buf.ptr : nullptr, exits ? heavy_out_buf.ptr : nullptr,
+                           in->order ? order_buf.ptr : nullptr, cost_buf.ptr);
+        launch_raster(st, fp, rec_buf.ptr, inst_buf.ptr, ranges_buf.ptr, reinterpret_cast<float4*>(sort_buf.ptr), in->clear, ctl);
+        ok = hipGetLastError() == hipSuccess &&
+             hipMemcpyAsync(host_scan, scan_buf.ptr, (size_t)image_floats * sizeof(float), hipMemcpyDeviceToHost, st) == hipSuccess &&
+             hipMemcpyAsync(host_sort, sort_buf.ptr, (size_t)image_floats * sizeof(float), hipMemcpyDeviceToHost, st) == hipSuccess &&
+             hipMemcpyAsync(host_cost, cost_buf.ptr, (size_t)ntiles * sizeof(uint16_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
+             hipMemcpyAsync(host_heavy, heavy_out_buf.ptr, heavy_host.size(), hipMemcpyDeviceToHost, st) == hipSuccess &&
+             hipMemcpyAsync(error_out, &ctl->error, sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
+             hipStreamSynchronize(st) == hipSuccess;
+    }
+    if (!ok) { (void)hipGetLastError(); return fail(ctx, BGS_EHIP, "raster self-test failed on the device"); }
+    return BGS_OK;
+}
+
 }  // extern "C"

@@ -856,8 +856,12 @@ constexpr float MS_OX0 = -0.125f, MS_OY0 = -0.375f, MS_OX1 = 0.375f, MS_OY1 = -0
 __device__ __forceinline__ float ms_margin(const float a, const float b) {
     return fmaxf(fabsf(fmaf(b, MS_OY0, a * MS_OX0)), fabsf(fmaf(b, MS_OY1, a * MS_OX1)));
 }
-// 1 where |x| <= lim, 0 where |x| > lim (exactly: clamp((lim - |x|) * 2^60) — 1 from lim - |x| >= 2^-60 on, 0 from
-// lim - |x| <= 0 down; see blend_px_ms): ONE v_fma_f32 with the abs / neg input and the clamp output modifier
+// 1 where |x| <= lim, 0 where |x| > lim: clamp((lim' - |x|) * 2^60) with lim' = the binary32 number after lim (limbig = lim' 2^60;
+// see blend_px_ms) — the fma is exact before its one rounding, so the value is >= 2^37 for every binary32 |x| <= lim and <= 0 for
+// every one above: ONE v_fma_f32 with the abs / neg input and the clamp output modifier. (With lim itself a sample exactly ON
+// the quad's edge came out uncovered, against blend_px's `<=` and the reference's rule: tests/test_raster_stage_gpu.py,
+// exact_edge_on_sample_s4.)
+__device__ __forceinline__ constexpr float ms_next_up(const float lim) { return __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, lim) + 1u); }   // (lim > 0, finite)
 __device__ __forceinline__ float ms_inside(const float x, const float big, const float limbig) {
     float r;
     asm("v_fma_f32 %0, -|%1|, %2, %3 clamp" : "=v"(r) : "v"(x), "v"(big), "v"(limbig));
@@ -952,10 +956,10 @@ __device__ __forceinline__ void blend_px_ms(const StagedRecord<VARIANT>& s, cons
         const bool all_full = !(DEPTH && zmixed) && __builtin_amdgcn_ballot_w64(!full) == 0ull;
         // Coverage of a sample as a 0 / 1 factor out of multiplications, additions and the clamp output modifier:
         // min / max, compares and selects issue at half the rate of those on this chip (wave64: 4 clocks against 2;
-        // profiles/r4_micro/valu_issue.txt). clamp((lim - |x|) * 2^60) is 1 for |x| <= lim - 2^-60, 0 for |x| >= lim —
-        // and something in between for a sample closer to the quad's edge than any rasteriser's rounding can place it.
+        // profiles/r4_micro/valu_issue.txt). clamp((lim' - |x|) * 2^60), lim' the binary32 number after lim, is 1 for every
+        // binary32 |x| <= lim and 0 for every one above (ms_inside).
         auto per_sample = [&](float& w) {
-            const float big = 1.152921504606846976e18f, limbig = lim * 1.152921504606846976e18f;   // 2^60
+            const float big = 1.152921504606846976e18f, limbig = ms_next_up(lim) * 1.152921504606846976e18f;   // 2^60
             float t0 = ms_inside(u + du0, big, limbig) * ms_inside(v + dv0, big, limbig) * t.r0;
             float t1 = ms_inside(u + du1, big, limbig) * ms_inside(v + dv1, big, limbig) * t.r1;
             float t2 = ms_inside(u - du1, big, limbig) * ms_inside(v - dv1, big, limbig) * t.r2;
@@ -1080,7 +1084,7 @@ __device__ __forceinline__ void blend_px_msn(const StagedRecord<VARIANT>& s, con
         if (all_full) t.S = fmaf(-alpha, t.S, t.S);
         asm volatile("");
         if (!all_full) {
-            const float big = 1.152921504606846976e18f, limbig = lim * 1.152921504606846976e18f;   // 2^60
+            const float big = 1.152921504606846976e18f, limbig = ms_next_up(lim) * 1.152921504606846976e18f;   // 2^60
             float ts[NS];
 #pragma unroll
             for (int k = 0; k < NS; ++k) {

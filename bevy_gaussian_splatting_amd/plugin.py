@@ -778,6 +778,68 @@ class GaussianSplattingPlugin:
         return {"counts": counts, "slots": slots, "culled": culled, "draw_count": int(info[0]), "splat_count": int(info[1]),
                 "error": int(info[2]), "threads": int(info[3]), "blocks": int(info[4])}
 
+    def selftest_raster(self, width: int, height: int, sample_count: int, variant: int, records: np.ndarray, lists: np.ndarray,
+                        totals: np.ndarray, sup_edge: int, coarse_cap: int, mode: int = 0, overlay: int = 0,
+                        clear=(0.0, 0.0, 0.0, 0.0), color_max_bits: int = 0, viewport=None, depth: Optional[np.ndarray] = None,
+                        heavy_tiles: Optional[np.ndarray] = None, order: Optional[np.ndarray] = None) -> dict:
+        """`bgs_selftest_raster`: both tile rasterisers alone on `records` uint32 / float32 [n, 12] (variant 0 OBB, 1 AABB3D)
+        or [n, 24] (2 surfel), the supertile `lists` uint32[supertiles, coarse_cap, 2] (rank, packed rectangle) and `totals`
+        uint32[supertiles]; `depth` float32[height, width, sample_count], `heavy_tiles` and `order` uint16 or None. `scan` and
+        `sort` float32[height, width, 4] (the two images), `scan_guard` / `sort_guard` uint32[64, 4] (the pixels behind each,
+        filled with 0xFF bytes before the launch), `cost` uint16[tiles], `heavy_count`, `heavy_list`, `heavy_flags` (the
+        scan rasteriser's heavy_out) and `error` (Control::error). Test hook (see include/bgs_diag.h)."""
+        w, h, ms = int(width), int(height), int(sample_count)
+        rec = np.ascontiguousarray(records).view(np.uint32).reshape(-1, 24 if int(variant) == 2 else 12)
+        li = np.ascontiguousarray(lists, dtype=np.uint32)
+        to = np.ascontiguousarray(totals, dtype=np.uint32)
+        tiles = max(-(-w // 16) * -(-h // 16), 0)
+        edge = max(int(sup_edge), 1)
+        num_st = -(-(-(-w // 16)) // edge) * -(-(-(-h // 16)) // edge)
+        if 1 <= w <= 512 and 1 <= h <= 512 and 1 <= int(sup_edge) <= 32 and int(coarse_cap) >= 1:   # (anything else is the library's to refuse)
+            if li.size != num_st * int(coarse_cap) * 2 or to.size != num_st:
+                raise ValueError("lists holds supertiles x coarse_cap entries of two words, totals one word per supertile")
+        arg = _native.BgsRasterSelftest()
+        arg.width, arg.height, arg.sample_count, arg.variant, arg.overlay, arg.mode = w, h, ms, int(variant), int(overlay), int(mode)
+        arg.sup_edge, arg.coarse_cap, arg.color_max_bits, arg.record_count = int(sup_edge), int(coarse_cap), int(color_max_bits) & 0xFFFFFFFF, rec.shape[0]
+        vw, vh = viewport if viewport is not None else (float(w), float(h))
+        arg.viewport_w, arg.viewport_h = float(vw), float(vh)
+        arg.clear[:] = [float(c) for c in clear]
+        keep = [rec, li, to]
+        arg.records, arg.lists, arg.totals = rec.ctypes.data, li.ctypes.data, to.ctypes.data
+        if depth is not None:
+            d = np.ascontiguousarray(depth, dtype=np.float32)
+            if d.size != w * h * ms:
+                raise ValueError("depth holds width x height x sample_count floats")
+            keep.append(d)
+            arg.depth = d.ctypes.data
+        if heavy_tiles is not None:
+            hv = np.ascontiguousarray(heavy_tiles, dtype=np.uint16)
+            keep.append(hv)
+            arg.heavy_tiles, arg.heavy_count = hv.ctypes.data, hv.size
+        if order is not None:
+            od = np.ascontiguousarray(order, dtype=np.uint16)
+            if od.size != (tiles + 3) // 4:
+                raise ValueError("order holds one entry per raster workgroup: (tiles + 3) // 4")
+            keep.append(od)
+            arg.order = od.ctypes.data
+        pixels = max(w * h, 0)
+        scan = np.zeros((pixels + _native.SELFTEST_RASTER_GUARD, 4), np.float32)
+        sort = np.zeros_like(scan)
+        cost = np.zeros(max(tiles, 1), np.uint16)
+        heavy = np.zeros(_native.HEAVY_FLAGS_OFFSET + tiles, np.uint8)
+        err = ctypes.c_uint32()
+        self._check(self._lib.bgs_selftest_raster(self._ctx, ctypes.byref(arg), scan.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                                  sort.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), scan.size,
+                                                  cost.ctypes.data_as(ctypes.c_void_p), heavy.ctypes.data_as(ctypes.c_void_p), heavy.size,
+                                                  ctypes.byref(err)))
+        count = int(heavy[:4].view(np.uint32)[0])
+        return {"scan": scan[:pixels].reshape(h, w, 4), "sort": sort[:pixels].reshape(h, w, 4),
+                "scan_guard": scan[pixels:].view(np.uint32), "sort_guard": sort[pixels:].view(np.uint32), "cost": cost[:tiles],
+                "heavy_count": count,
+                "heavy_list": heavy[_native.HEAVY_LIST_OFFSET:_native.HEAVY_FLAGS_OFFSET].view(np.uint16)[:min(count, _native.HEAVY_CAP)].copy(),
+                "heavy_flags": heavy[_native.HEAVY_FLAGS_OFFSET:],
+                "error": int(err.value)}
+
     def set_pipeline_streams(self, streams: int) -> None:
         """HIP streams the lanes are multiplexed onto (0 = one per lane); see bgs_set_pipeline_streams."""
         self._check(self._lib.bgs_set_pipeline_streams(self._ctx, int(streams)))

@@ -238,6 +238,51 @@ int bgs_selftest_keygen_buckets(bgs_ctx* ctx, const bgs_cloud* cloud, const bgs_
                                 uint32_t alone, uint32_t* host_counts, uint32_t* host_slots, uint64_t slots_capacity_words,
                                 uint32_t* host_culled, uint64_t culled_capacity_words, uint32_t* info_out);
 
+/* The two tile rasterisers alone, launched once each through the frames' own launchers (launch_raster_scan: raster_scan_kernel
+ * / raster_tile; launch_raster: raster_kernel) on caller-supplied stage inputs — what the vertex and binning stages leave:
+ *   width, height      the target, 1 .. 512 px each; tiles of 16 x 16 px, supertiles of sup_edge x sup_edge tiles (at most 256
+ *                      of them, 32 per axis);
+ *   sample_count       1, 2, 4 or 8; variant 0 OBB, 1 AABB3D, 2 surfel; overlay 0 / 1 (the bounding-box overlay);
+ *   mode               raster_scan_kernel's MODE: 0 plain, 1 dense + mid-round exit, 2 sparse + mid-round exit. Refused when
+ *                      raster_scan_mode (csrc/frame_params.h) never gives it for the variant, samples and overlay;
+ *   viewport_w / _h    FrameParams::viewport_w / _h (the surfel variant's aspect); clear[4]; color_max_bits: what
+ *                      Control::color_max_bits holds (the bits of the frame's largest colour magnitude: the cut-off);
+ *   records            record_count records of 48 bytes (OBB, AABB3D: Record) or 96 (surfel: RecordSurfel), csrc/bgs_device.h;
+ *   lists, totals      the supertile lists: supertiles x coarse_cap entries of two words (rank, packed rectangle x0 | x1 << 8 |
+ *                      y0 << 16 | y1 << 24), list s at entry s * coarse_cap, and totals[supertiles] (Control::coarse_total; a
+ *                      total may exceed coarse_cap: the kernel reads min(total, coarse_cap) entries);
+ *   depth              NULL, or width * height * sample_count floats ([y][x][sample], reverse-Z; FrameParams::depth_ptr);
+ *   heavy_tiles        NULL, or heavy_count (<= 256) distinct tile ids (ty * tiles_x + tx) the strip workgroups draw; modes 1 and
+ *                      2 only. The hook builds the HeavyFeedback buffer (count, list, flag per tile) the launch reads;
+ *   order              NULL, or the raster workgroups' order: a permutation of 0 .. (tiles + 3) / 4 - 1.
+ * The instance-sort rasteriser's instances and tile ranges are derived on the host from the same lists: for each tile the
+ * entries of its supertile's list, in list order, whose rectangle holds the tile. FrameCleanup is all-null, there is no
+ * trace buffer, and only the f32 target is written. Everything the kernels read or write is allocated for the call.
+ *   host_scan, host_sort   (width * height + BGS_SELFTEST_RASTER_GUARD) RGBA f32 pixels each: the image, then the guard;
+ *                      both buffers are filled with 0xFF bytes before the launch; image_capacity_floats: what each holds;
+ *   host_cost          tiles words (u16): the scan rasteriser's cost_out, filled with 0xFF bytes before the launch;
+ *   host_heavy         128 + 512 + tiles bytes: the heavy_out buffer (zeroed before the launch; modes 1 and 2 write it);
+ *   error_out          Control::error.
+ * BGS_EINVAL, naming the argument, and nothing launched: a size, count or flag outside the above; a rank >= record_count in a
+ * list position below min(total, coarse_cap); a tile id >= tiles or twice in heavy_tiles; an order that is no permutation;
+ * more than 2^24 tile instances; a capacity that is too small. Nothing the caller passes can then index outside an
+ * allocation. Completes the frames in flight. Test hook (tests/test_raster_stage_gpu.py). */
+#define BGS_SELFTEST_RASTER_GUARD 64u
+typedef struct bgs_raster_selftest {
+    uint32_t width, height, sample_count, variant, overlay, mode;
+    uint32_t sup_edge, coarse_cap, color_max_bits, record_count, heavy_count, reserved;
+    float viewport_w, viewport_h, clear[4];
+    const void* records;
+    const uint32_t* lists;
+    const uint32_t* totals;
+    const float* depth;
+    const uint16_t* heavy_tiles;
+    const uint16_t* order;
+} bgs_raster_selftest;
+int bgs_selftest_raster(bgs_ctx* ctx, const bgs_raster_selftest* in, float* host_scan, float* host_sort,
+                        uint64_t image_capacity_floats, uint16_t* host_cost, uint8_t* host_heavy, uint64_t heavy_capacity_bytes,
+                        uint32_t* error_out);
+
 #ifdef __cplusplus
 }
 #endif
