@@ -21,6 +21,7 @@
 #include "../../include/bgs.h"
 #include "../../include/bgs_diag.h"
 #include "bgs_device.h"
+#include "adaptive_state.h"
 #include "device_buffer.h"
 #include "frame_params.h"
 #include "kernels.h"
@@ -141,6 +142,58 @@ struct FramePlan {
     // behind its order, whose saturation counts the frame reports (0: none); may replay a captured graph
     bool heavy = false, cost = false, ordered = false, refresh = false, graph_ok = false;
     uint64_t sat_kind = 0;
+    // what the frame is to the stage timings (Lane::ev_kind, result_kind): 1 sort-only frame, 2 render/scan, 3 render/sort-binning,
+    // 4 / 5: 2 / 3 drawn in a kept order (0: an unused ring slot)
+    uint8_t ev_kind() const { return (uint8_t)(!render ? 1 : (scan ? 2 : 3) + (kept ? 2 : 0)); }
+    struct EvKind { bool render, scan, kept; };
+    static EvKind decode_ev_kind(uint8_t kind) { return {kind != 1, kind == 2 || kind == 4, kind >= 4}; }
+};
+
+// The tile feedback a lane's BINNING_SCAN frames leave for its next ones: balance only, every tile is drawn exactly once
+// whatever the buffers hold.
+struct TileFeedback {
+    // heavy-tile feedback of the rasteriser (kernels.h HeavyFeedback): two buffers per lane, written alternately, so that
+    // frames of other lanes can still be reading the one this lane's previous frame completed
+    DeviceBuffer<uint8_t> heavy[2];
+    uint32_t heavy_parity = 0;  // heavy[heavy_parity] is what the lane's NEXT frame writes; flipped when a frame COMPLETES
+    // The feedback the lane's next dense frame consumes: the buffer its most recently COMPLETED dense frame wrote (any
+    // view: a stale list costs balance, never pixels — every tile is drawn exactly once, by its regular wave or by a
+    // strip workgroup, whichever the list it reads says). Per LANE: a lane's frames run one after the other, so the
+    // buffer a frame reads (heavy[parity ^ 1], complete) is never the one it — or a re-run of it — writes
+    // (heavy[parity]), and no frame of another lane ever reads either.
+    const uint8_t* heavy_done = nullptr;
+    uint32_t heavy_done_grid = 0;   // tile_grid_word of that frame
+    // per-tile cost feedback (kernels.h TileCost), the same life cycle as the heavy-tile lists: cost[cost_parity] is what
+    // the lane's next frame writes, cost_done what its most recently completed frame wrote; `order` is made of
+    // cost_done at the start of a frame and read by that frame's rasteriser only
+    DeviceBuffer<uint16_t> cost[2], order;   // (cost planes: tile_cost_bytes / 2 elements)
+    uint32_t cost_parity = 0;
+    const uint16_t* cost_done = nullptr;
+    uint32_t cost_done_grid = 0;
+    uint64_t cost_done_kind = 0;    // kind of the frame that left cost_done
+    uint32_t order_grid = 0xFFFFFFFFu, order_age = 0;   // the grid `order` is a permutation for; frames drawn with it since it was made
+    uint64_t order_kind = 0;        // kind of the frame whose cost plane the lane's order (and its saturation counts) was made of
+
+    // nothing a completed frame left is used again (the buffers stay)
+    void forget_heavy() { heavy_done = nullptr; }
+    void forget_cost() { cost_done = nullptr; order_grid = 0xFFFFFFFFu; }
+    void forget() { forget_heavy(); forget_cost(); }
+    // A frame is ENQUEUED: one that makes the order anew makes it of cost_done, for its grid
+    void enqueued(const FramePlan& p) {
+        if (p.refresh) { order_kind = cost_done_kind; order_grid = tile_grid_word(p.fp); order_age = 0; }
+        else if (p.ordered) order_age += 1u;
+    }
+    // The frame is COMPLETE: what it wrote is what the lane's next dense frames read (null after a frame that left none).
+    // Only now does the lane's next frame write the OTHER buffer: a re-run wrote the one its failed attempt wrote, never
+    // the completed frame's list it was reading
+    void completed(const FramePlan& p, uint64_t kind) {
+        heavy_done = p.heavy ? heavy[heavy_parity].ptr : nullptr;
+        heavy_done_grid = cost_done_grid = tile_grid_word(p.fp);
+        if (p.heavy) heavy_parity ^= 1u;
+        cost_done = p.cost ? cost[cost_parity].ptr : nullptr;
+        cost_done_kind = kind;
+        if (p.cost) cost_parity ^= 1u;
+    }
 };
 
 // Everything one in-flight frame owns. The buffers free themselves (lane_destroy: L = Lane()); a buffer's capacity is in
@@ -176,26 +229,8 @@ struct Lane {
     // copied from, ahead of keygen, on the frame's stream (one group)
     DeviceBuffer<uint32_t> d_split_keys;
     PinnedBuffer<uint32_t> h_split_keys;
-    // heavy-tile feedback of the rasteriser (kernels.h HeavyFeedback): two buffers per lane, written alternately, so that
-    // frames of other lanes can still be reading the one this lane's previous frame completed
-    DeviceBuffer<uint8_t> heavy[2];
-    uint32_t heavy_parity = 0;  // heavy[heavy_parity] is what the lane's NEXT frame writes; flipped when a frame COMPLETES
-    // The feedback the lane's next dense frame consumes: the buffer its most recently COMPLETED dense frame wrote (any
-    // view: a stale list costs balance, never pixels — every tile is drawn exactly once, by its regular wave or by a
-    // strip workgroup, whichever the list it reads says). Per LANE: a lane's frames run one after the other, so the
-    // buffer a frame reads (heavy[parity ^ 1], complete) is never the one it — or a re-run of it — writes
-    // (heavy[parity]), and no frame of another lane ever reads either.
-    const uint8_t* heavy_done = nullptr;
-    uint32_t heavy_done_grid = 0;   // tiles_x | tiles_y << 16 of that frame
-    // per-tile cost feedback (kernels.h TileCost), the same life cycle as the heavy-tile lists: cost[cost_parity] is what
-    // the lane's next frame writes, cost_done what its most recently completed frame wrote; `order` is made of
-    // cost_done at the start of a frame and read by that frame's rasteriser only
-    bool ready = false;   // the lane's frame is complete but nobody has taken it yet (bgs_pipeline_pop): a frame finished early, see bgs_ctx::kinds
-    DeviceBuffer<uint16_t> cost[2], order;   // (cost planes: tile_cost_bytes / 2 elements)
-    uint32_t cost_parity = 0;
-    const uint16_t* cost_done = nullptr;
-    uint32_t cost_done_grid = 0;
-    uint32_t order_grid = 0xFFFFFFFFu, order_age = 0;   // the grid `order` is a permutation for; frames drawn with it since it was made
+    TileFeedback feedback;
+    bool ready = false;   // the lane's frame is complete but nobody has taken it yet (bgs_pipeline_pop): a frame finished early, see AdaptiveState::kinds
     DeviceBuffer<float4> fb;
     DeviceBuffer<uint32_t> fb8;  // the packed image (optional): two words per pixel, room for either format (4 or 8 bytes)
     uint32_t* fb8_out = nullptr; // where the last frame's packed image went (fb8 or a caller's target)
@@ -206,7 +241,7 @@ struct Lane {
     PinnedBuffer<Control> h_ctl;  // filled by a copy enqueued with the frame, or by the rasteriser
     Control* h_ctl_dev = nullptr;  // the same memory as the device sees it
     hipEvent_t ev_ring[EV_RING][EV_COUNT] = {};
-    uint8_t ev_kind[EV_RING] = {};  // 0 unused, 1 sort-only frame, 2 render/scan, 3 render/sort-binning, 4 / 5: 2 / 3 drawn in a kept order
+    uint8_t ev_kind[EV_RING] = {};  // FramePlan::ev_kind() of the frame timed in the slot, 0 unused
     uint32_t ev_head = 0;
     uint32_t frames_timed = 0;  // timed frames since the last stats read-back
 
@@ -214,8 +249,6 @@ struct Lane {
     FrameInputs in;        // what the lane's frame was enqueued with (a re-run enqueues it again)
     FramePlan plan;        // ... and the choices it was enqueued with
     uint32_t pending_coarse_cap = 0;   // entries per supertile list the pending frame was given
-    uint64_t cost_done_kind = 0;       // kind of the frame that left cost_done
-    uint64_t order_kind = 0;           // kind of the frame whose cost plane the lane's order (and its saturation counts) was made of
     uint64_t seq = 0;  // enqueue sequence number (to find the oldest pending lane)
 
     const uint2* last_sorted = nullptr;
@@ -260,72 +293,9 @@ struct bgs_ctx {
     bool packed_only = false;      // frames with a packed image do not write the f32 target
     uint32_t* next_srgb8_target = nullptr;  // bgs_set_srgb8_target: one-shot destination of the next frame
 
-    // Sizes the grids of the next frames' sort and projection launches: the draw_count of a completed
-    // frame plus head-room, raised at once and lowered only after 64 frames at under a quarter of it, so that a
-    // captured frame graph (whose grids are frozen) survives a moving camera. A hint only — the
-    // kernels read the real count on the device and loop over tickets if the grid is short.
-    uint32_t draw_hint = 0;
-    bool draw_hint_valid = false;
-    uint32_t draw_shrink_votes = 0;
-    uint32_t sup_level = 1;  // supertile edge level of the next frames (see plan_frame)
-    // Bucket sort (one launch instead of four digit passes) is used while a completed frame's quantile keys
-    // are known, the draw count fits the bucket geometry, and it has not just failed.
-    // Splitter tables: the quantile keys of completed frames' sorted lists, kept per "view slot" — a context that
-    // alternates between cameras (the reference's multi_camera example), clouds or model transforms would
-    // otherwise hand every frame the table of the wrong view. A table is used for a frame of the same cloud and
-    // transform whose camera is near the pose it was measured at; it is dropped when a frame it served overflows.
-    struct SplitterSlot {
-        SplitterKeys table{};
-        const bgs_cloud* cloud = nullptr;
-        uint32_t n = 0;
-        uint32_t sort_mode = 0;   // Radix culls (a frustum's worth of keys), Rayon / Std keep every splat
-        float transform[16] = {};
-        float pos[3] = {}, fwd[3] = {};
-        // SORT_RADIX keys only what the frustum keeps, so the key set also depends on the projection and viewport:
-        // two cameras at one pose with different fov / zoom / target size must not share (and overwrite) a table
-        float clip_from_view[16] = {};
-        float viewport_wh[2] = {};
-        float reach = 0.0f;       // median view distance of the list the table came from (scale of "near")
-        uint64_t epoch = 0;       // 0 = empty
-        uint64_t last_used = 0;
-    };
-    static constexpr int SPLITTER_SLOTS = 16;  // (1 KB each; the key includes the projection since round 3, so zooms / resizes take slots too)
-    SplitterSlot split_slots[SPLITTER_SLOTS];
-    uint64_t split_epoch = 0;         // epochs handed out so far
-    uint64_t split_failed_epoch = 0;  // newest epoch whose table overflowed (escalation looks at newer ones only)
-    uint32_t bucket_block = 0;        // frames to stay on the onesweep passes after a bucket-sort overflow
-    uint32_t bucket_fail_streak = 0;  // tables in a row that overflowed on their first use
-    uint32_t list_shrink_votes = 0;   // completed frames in a row whose lists would fit a much smaller capacity
+    AdaptiveState state;   // everything completed frames leave for the next ones, and the rules that write it
     uint64_t bucket_frames = 0, onesweep_frames = 0;  // frames enqueued on either sort path (incl. re-runs)
     uint64_t reruns_sort = 0, reruns_lists = 0, reruns_instances = 0, level_changes = 0;
-    // entries per supertile list the next frames allocate (grown from the longest list seen; a frame whose
-    // lists overflow is re-run): the worst case is n entries in each of up to 256 lists (1.9 GB per lane at
-    // 1 M splats), the real lists of a frame hold ~1 % of that
-    uint32_t coarse_cap_hint = 0;
-    // KINDS OF FRAME. What a completed frame teaches (list capacity, supertile level) depends on the kind of frame it was:
-    // (splat count and storage format of the cloud, mode, quad shape, global scale to half an octave, viewport size,
-    // sample count, depth buffer or not) — frame_kind(); poses do not count, a moving camera stays pipelined. An async
-    // frame of a kind the context has not settled on is completed at once (re-running it if a first guess was too
-    // small) instead of sending pipeline-depth frames out on first guesses and re-running every one of them (round 3's
-    // verdict: "reruns: 8" on every first use); the frames behind it start from what it learnt. A kind is settled once
-    // a frame of it has run with everything it needed (no re-run, no change of supertile level) — or, at the latest,
-    // after LEARN_MAX frames of it IN TOTAL were completed early (a frame that always re-runs, a level that oscillates:
-    // bounded, not a phase the context can stay in — counted per kind since round 6: round 5 counted frames "in a row",
-    // and a host that alternated two kinds that never ran clean reset the streak with every frame and stayed blocking). The set NEVER FORGETS (round 4 kept the last 16 kinds FIFO and
-    // hashed the cloud's ADDRESS and the raw scale bits into the kind: a host with more than 16 clouds or settings, a new
-    // cloud handle per frame or an animated global_scale lost its pipelining for good, silently), and every kind keeps
-    // its own supertile level, so a context that alternates between kinds does not run each at the other's level.
-    // midround: frames of the kind run the rasteriser's mid-round-exit instantiation whatever their supertile level — set
-    // (with hysteresis) from the share of a completed frame's tiles that ended SATURATED rather than at the end of their
-    // lists (round 6: a cloud of opaque surfaces saturates its tiles inside a staging round like a dense one does)
-    struct KindState { uint32_t sup_level = 1; bool midround = false; };
-    std::unordered_map<uint64_t, KindState> kinds;   // the kinds settled on (8 + 4 bytes each; reset by bgs_reset_adaptive_state)
-    static constexpr uint32_t LEARN_MAX = 3;
-    // share of a frame's tile work in tiles that ended saturated at/above which frames of its kind run the mid-round-exit
-    // rasteriser, and at/below which they stop (hysteresis; measured: profiles/r6_notes.md §9)
-    static constexpr double MIDROUND_ON = 0.30, MIDROUND_OFF = 0.15;
-    uint64_t cur_kind = 0;          // kind of the most recently enqueued frame (ctx->sup_level is that kind's level)
-    std::unordered_map<uint64_t, uint32_t> learning;   // kinds being learnt: frames of each completed early so far
     uint64_t early_frames = 0;      // async frames completed inside their bgs_render call (bgs_learning_counters)
     uint4* tile_trace = nullptr;  // bgs_set_tile_trace: caller-owned device buffer the rasteriser's TRACE instantiation fills
     bool use_graphs = false;  // async BINNING_SCAN frames replay a captured hipGraph (bgs_set_graphs)

@@ -1,5 +1,6 @@
-// bgs_frame.hip — libbgs host side: the frame engine. Lanes and their buffers, the adaptive state completed frames leave,
-// one frame's launches (directly or as a captured graph), completion with its capacity checks and re-runs.
+// bgs_frame.hip — libbgs host side: the frame engine. Lanes and their buffers, one frame's launches (directly or as a
+// captured graph), completion with its capacity checks and re-runs. What completed frames leave for the next ones, and
+// every rule that writes it, is AdaptiveState (adaptive_state.h): this file calls the rules and reads the state.
 // (The comment at the top of bgs_api.hip is the overview.)
 #include "bgs_context.h"
 
@@ -133,13 +134,11 @@ int ensure_records(bgs_ctx* ctx, Lane& L, size_t bytes) {
 }
 
 // Supertile lists: `num_st` lists of `cap` (rank, tile rect) entries each. `cap` follows the longest list
-// seen so far (ctx->coarse_cap_hint, never more than n: a list holds each rank at most once); a frame
+// seen so far (AdaptiveState::list_capacity, never more than n: a list holds each rank at most once); a frame
 // that overflows a list is detected when it completes (coarse_total > cap) and re-run with larger lists.
 int ensure_coarse(bgs_ctx* ctx, Lane& L, uint32_t n, uint32_t num_st, uint32_t debug_flags, uint32_t* cap_out) {
     const uint32_t n1 = std::max<uint32_t>(n, 1);
-    if (ctx->coarse_cap_hint == 0)
-        ctx->coarse_cap_hint = (debug_flags & BGS_DEBUG_SMALL_LISTS) ? 64u : std::max<uint32_t>(pow2_ceil_u32(n1 / 64u), 4096u);  // a first guess: a frame that outgrows it is re-run
-    const uint32_t want = std::min<uint32_t>(n1, ctx->coarse_cap_hint);
+    const uint32_t want = ctx->state.list_capacity(n, (debug_flags & BGS_DEBUG_SMALL_LISTS) != 0u);
     const size_t need = (size_t)num_st * want;   // 8-byte entries, all lists together
     // (grown when too small; a lane keeps what it has when the hint falls — a context that alternates between
     // views of different density would otherwise free and allocate every frame)
@@ -172,30 +171,31 @@ int ensure_split_keys(bgs_ctx* ctx, Lane& L) {
 
 int ensure_heavy(bgs_ctx* ctx, Lane& L, uint32_t tiles) {
     const size_t bytes = heavy_feedback_bytes(tiles);
-    if (L.heavy[0].holds(bytes)) return BGS_OK;
+    TileFeedback& F = L.feedback;
+    if (F.heavy[0].holds(bytes)) return BGS_OK;
     // (freeing waits for the device: no frame in flight still reads the old buffers)
-    L.heavy_done = nullptr;
-    if (reserve_group(bytes, L.heavy[0], L.heavy[1]) >= 0) return fail(ctx, BGS_ENOMEM, "hipMalloc(heavy-tile feedback) failed");
+    F.forget_heavy();
+    if (reserve_group(bytes, F.heavy[0], F.heavy[1]) >= 0) return fail(ctx, BGS_ENOMEM, "hipMalloc(heavy-tile feedback) failed");
     return BGS_OK;
 }
 
 // whether the lane's cost planes (and the order made of them) serve a grid of `tiles` as they are
-bool cost_holds(const Lane& L, uint32_t tiles) { return L.cost[0].holds(tile_cost_bytes(tiles) / 2u); }
+bool cost_holds(const Lane& L, uint32_t tiles) { return L.feedback.cost[0].holds(tile_cost_bytes(tiles) / 2u); }
 
 int ensure_cost(bgs_ctx* ctx, Lane& L, uint32_t tiles) {
     if (cost_holds(L, tiles)) return BGS_OK;
-    L.cost_done = nullptr;
-    L.order_grid = 0xFFFFFFFFu;
-    L.order.reset();
-    bool ok = reserve_group(tile_cost_bytes(tiles) / 2u, L.cost[0], L.cost[1]) < 0;
-    for (auto& c : L.cost)   // new planes start zeroed
+    TileFeedback& F = L.feedback;
+    F.forget_cost();
+    F.order.reset();
+    bool ok = reserve_group(tile_cost_bytes(tiles) / 2u, F.cost[0], F.cost[1]) < 0;
+    for (auto& c : F.cost)   // new planes start zeroed
         if (ok && hipMemset(c.ptr, 0, tile_cost_bytes(tiles)) != hipSuccess) { (void)hipGetLastError(); ok = false; }
     if (!ok) {
-        for (auto& c : L.cost) c.reset();
+        for (auto& c : F.cost) c.reset();
         return fail(ctx, BGS_ENOMEM, "hipMalloc(tile cost feedback) failed");
     }
-    if (!L.order.reserve(tile_order_bytes(tiles) / 2u)) {
-        for (auto& c : L.cost) c.reset();
+    if (!F.order.reserve(tile_order_bytes(tiles) / 2u)) {
+        for (auto& c : F.cost) c.reset();
         return fail(ctx, BGS_ENOMEM, "hipMalloc(tile order) failed");
     }
     return BGS_OK;
@@ -259,64 +259,6 @@ int validate(bgs_ctx* ctx, const bgs_cloud* cloud, const bgs_view* view, const b
     return BGS_OK;
 }
 
-// camera pose of a view: world position and viewing direction (-Z of the view frame)
-void view_pose(const bgs_view* v, float pos[3], float fwd[3]) {
-    for (int k = 0; k < 3; ++k) { pos[k] = v->world_from_view[12 + k]; fwd[k] = -v->world_from_view[8 + k]; }
-    const float len = std::sqrt(fwd[0] * fwd[0] + fwd[1] * fwd[1] + fwd[2] * fwd[2]);
-    if (len > 0.0f) for (int k = 0; k < 3; ++k) fwd[k] /= len;
-}
-
-// The splitter slot that fits a frame (same cloud, sort mode and model transform, camera within 5 % of the
-// slot's reach and 10 degrees of its direction), or -1.
-int find_splitter_slot(const bgs_ctx* ctx, const bgs_cloud* cloud, const bgs_view* view, const bgs_settings* s) {
-    float pos[3], fwd[3];
-    view_pose(view, pos, fwd);
-    int best = -1;
-    float best_d = 0.0f;
-    for (int i = 0; i < bgs_ctx::SPLITTER_SLOTS; ++i) {
-        const auto& sl = ctx->split_slots[i];
-        if (!sl.epoch || sl.cloud != cloud || sl.n != cloud->ptrs.n || sl.sort_mode != s->sort_mode) continue;
-        if (std::memcmp(sl.transform, s->transform, sizeof sl.transform) != 0) continue;
-        if (s->sort_mode == BGS_SORT_RADIX &&
-            (std::memcmp(sl.clip_from_view, view->clip_from_view, sizeof sl.clip_from_view) != 0 ||
-             sl.viewport_wh[0] != view->viewport[2] || sl.viewport_wh[1] != view->viewport[3]))
-            continue;
-        const float dx = pos[0] - sl.pos[0], dy = pos[1] - sl.pos[1], dz = pos[2] - sl.pos[2];
-        const float d = std::sqrt(dx * dx + dy * dy + dz * dz);
-        const float c = fwd[0] * sl.fwd[0] + fwd[1] * sl.fwd[1] + fwd[2] * sl.fwd[2];
-        if (!(d <= 0.05f * sl.reach) || !(c >= 0.9848f)) continue;
-        const float score = d / std::max(sl.reach, 1e-30f) + (1.0f - c);
-        if (best < 0 || score < best_d) { best = i; best_d = score; }
-    }
-    return best;
-}
-
-// What bgs_ctx::kinds is keyed by: a hash of the inputs the data-dependent capacities depend on (never 0). The cloud
-// enters by its size and storage format, not by its address (a host that uploads a new cloud per frame — a stream of
-// same-sized captures — stays pipelined; a different cloud of the same size is at worst a re-run, as for any stale
-// hint), the global scale to half an octave (an animated scale crosses a step now and then, not with every frame).
-uint64_t frame_kind(const bgs_cloud* cloud, const bgs_view* view, const bgs_settings* s) {
-    int32_t scale_step = INT32_MIN;
-    if (s->global_scale > 0.0f && std::isfinite(s->global_scale)) scale_step = (int32_t)std::lround(2.0 * std::log2((double)s->global_scale));
-    const uint64_t words[6] = {((uint64_t)cloud->ptrs.n << 32) | cloud->ptrs.format, ((uint64_t)s->gaussian_mode << 32) | s->aabb,
-                               ((uint64_t)(uint32_t)scale_step << 32) | s->opacity_adaptive_radius,
-                               ((uint64_t)(uint32_t)view->viewport[2] << 32) | (uint32_t)view->viewport[3],
-                               ((uint64_t)(view->sample_count ? view->sample_count : 4u) << 32) | (view->depth_device_ptr ? 1u : 0u),
-                               ((uint64_t)s->rasterize_mode << 32) | (s->draw_mode << 1) | (s->visualize_bounding_box ? 1u : 0u)};
-    uint64_t hsh = 0xcbf29ce484222325ull;   // FNV-1a over the words
-    for (uint64_t w : words)
-        for (int b = 0; b < 8; ++b) { hsh ^= (w >> (8 * b)) & 0xFFu; hsh *= 0x100000001b3ull; }
-    return hsh ? hsh : 1ull;
-}
-
-// The frame about to be enqueued is of `kind`: ctx->sup_level becomes that kind's level (if it has one).
-void switch_kind(bgs_ctx* ctx, uint64_t kind) {
-    if (kind == ctx->cur_kind) return;
-    const auto it = ctx->kinds.find(kind);
-    if (it != ctx->kinds.end()) ctx->sup_level = it->second.sup_level;
-    ctx->cur_kind = kind;
-}
-
 // What a completed frame's Control block says about the size of its work: tile instances (BINNING_SCAN: the
 // supertile lists' entries) and the longest supertile list.
 struct FrameTotals { uint64_t instances = 0; uint32_t longest = 0; };
@@ -340,56 +282,24 @@ int check_watchdog(bgs_ctx* ctx, Lane& L) {
     const Control& h = *L.h_ctl.ptr;
     if (!h.error) return BGS_OK;
     L.scratch_clean = false;
-    ctx->draw_hint_valid = false;
-    for (auto& sl : ctx->split_slots) sl.epoch = 0;
+    ctx->state.distrust();
     return fail(ctx, BGS_EINTERNAL, "device watchdog tripped (look-back spin bound), code " + std::to_string(h.error));
 }
 
-// finish_lane, step 2: the capacities that depend on the data. *rerun: the frame must be run again.
+// finish_lane, step 2: the capacities that depend on the data (the verdicts: adaptive_state.h). *rerun: the frame must be
+// run again.
 int check_capacities(bgs_ctx* ctx, Lane& L, const FrameTotals& t, int attempt, bool* rerun) {
     const FramePlan& p = L.plan;
     const Control& h = *L.h_ctl.ptr;
     *rerun = false;
-    if (p.bucket && h.sort_overflow) {
-        // A bucket over capacity (1): the view changed faster than the splitters follow; the table is dropped
-        // and the re-run (always on the digit passes) delivers a fresh one. Frames already in flight
-        // with the same stale table fail for the same reason, so only a table NEWER than the last failed one
-        // counts towards the back-off (three such tables in a row: 7, 15, ... 255 frames on the passes).
-        // One key value far too often (2): no table can split that; 256 frames on the passes.
-        if (p.split_slot >= 0 && ctx->split_slots[p.split_slot].epoch == p.split_epoch)
-            ctx->split_slots[p.split_slot].epoch = 0;  // drop the table
-        if (h.sort_overflow & 2u) {
-            ctx->bucket_block = 256u;
-        } else if (p.split_epoch > ctx->split_failed_epoch) {
-            ctx->bucket_fail_streak = std::min(ctx->bucket_fail_streak + 1u, 8u);
-            if (ctx->bucket_fail_streak >= 3u) ctx->bucket_block = (1u << ctx->bucket_fail_streak) - 1u;
-        }
-        ctx->split_failed_epoch = std::max(ctx->split_failed_epoch, p.split_epoch);
+    if (p.bucket && ctx->state.learn_bucket_sort(h.sort_overflow, p.split_slot, p.split_epoch)) {
         ctx->reruns_sort += 1;
-        L.in.force_passes = true;   // stays for every further attempt of this frame
+        L.in.force_passes = true;   // the re-run is on the digit passes, and so is every further attempt of this frame
         *rerun = true;
-    } else if (p.bucket) {
-        ctx->bucket_fail_streak = 0;
     }
-    if (p.render && p.scan) {
-        // the capacity the next allocations aim at follows the longest list SEEN (25 % head-room, power of
-        // two): up at once, down only after 64 completed frames in a row that would fit an eighth of it
-        const uint32_t want = std::max<uint32_t>(pow2_ceil_u32((uint64_t)t.longest + t.longest / 4), 4096u);
-        if (p.level == ctx->sup_level) {
-            if (want > ctx->coarse_cap_hint) {
-                ctx->coarse_cap_hint = want;
-                ctx->list_shrink_votes = 0;
-            } else if ((uint64_t)want * 8u <= ctx->coarse_cap_hint) {
-                if (++ctx->list_shrink_votes >= 64u) { ctx->coarse_cap_hint = want * 2u; ctx->list_shrink_votes = 0; }
-            } else {
-                ctx->list_shrink_votes = 0;
-            }
-        }
-        if (t.longest > L.pending_coarse_cap) {  // this frame dropped entries
-            if (want > ctx->coarse_cap_hint) ctx->coarse_cap_hint = want;
-            *rerun = true;
-            ctx->reruns_lists += 1;
-        }
+    if (p.render && p.scan && ctx->state.learn_list_capacity(t.longest, p.level, L.pending_coarse_cap)) {
+        ctx->reruns_lists += 1;
+        *rerun = true;
     }
     if (p.render && !p.scan && h.overflow) {
         // BINNING_SORT overflow: grow to the next power of two with 25 % headroom
@@ -410,114 +320,22 @@ int check_capacities(bgs_ctx* ctx, Lane& L, const FrameTotals& t, int attempt, b
     return BGS_OK;
 }
 
-// finish_lane, step 3a: the completed frame's heavy-tile and cost feedback is what the lane's next dense frames read
-// (null after a frame that left none); its saturation counts move its kind's mid-round-exit choice
-void learn_feedback(bgs_ctx* ctx, Lane& L) {
+// finish_lane, step 3: what the completed frame (its first attempt, if `clean`) teaches the next ones: adaptive_state.h
+void learn_from_frame(bgs_ctx* ctx, Lane& L, const FrameTotals& t, bool clean) {
     const FramePlan& p = L.plan;
     const Control& h = *L.h_ctl.ptr;
-    const uint32_t grid = (uint32_t)p.fp.tiles_x | ((uint32_t)p.fp.tiles_y << 16);
-    // only now does the lane's next frame write the OTHER buffer: a re-run wrote the one its failed attempt wrote,
-    // never the completed frame's list it was reading
-    L.heavy_done = p.heavy ? L.heavy[L.heavy_parity].ptr : nullptr;
-    L.heavy_done_grid = grid;
-    if (p.heavy) L.heavy_parity ^= 1u;
-    L.cost_done = p.cost ? L.cost[L.cost_parity].ptr : nullptr;
-    L.cost_done_kind = L.in.kind;
-    L.cost_done_grid = grid;
-    // what the cost plane behind the lane's tile order said: the share of the frame's tile work that was in tiles which
-    // ended saturated (tile_order_kernel sums, this frame's clean-up block reports; x 0x7FFF)
-    if (p.sat_kind && h.saturated_tiles_prev != 0xFFFFFFFFu) {
-        const auto kit = ctx->kinds.find(p.sat_kind);
-        if (kit != ctx->kinds.end()) {
-            const double share = (double)h.saturated_tiles_prev / (double)0x7FFF;
-            if (share >= bgs_ctx::MIDROUND_ON) kit->second.midround = true;
-            else if (share <= bgs_ctx::MIDROUND_OFF) kit->second.midround = false;
-        }
+    AdaptiveState& state = ctx->state;
+    const bool scan_render = p.render && p.scan;
+    if (scan_render) {
+        L.feedback.completed(p, L.in.kind);
+        state.learn_saturation(p.sat_kind, h.saturated_tiles_prev);
     }
-    if (p.cost) L.cost_parity ^= 1u;
-}
-
-// finish_lane, step 3b: the draw-count hint (up at once; down only after 64 completed frames in a row at under a quarter
-// of it: a context that cycles through cameras seeing different shares of the cloud keeps one hint — and one captured
-// graph per lane)
-void learn_draw_hint(bgs_ctx* ctx, uint32_t draw_count) {
-    if (!ctx->draw_hint_valid || draw_count > ctx->draw_hint) {
-        ctx->draw_hint = (uint32_t)std::min<uint64_t>((uint64_t)draw_count + draw_count / 8 + 1024, 0xFFFFFFFFull);
-        ctx->draw_hint_valid = true;
-        ctx->draw_shrink_votes = 0;
-    } else if ((uint64_t)draw_count * 4 < ctx->draw_hint) {
-        if (++ctx->draw_shrink_votes >= 64u) {
-            ctx->draw_hint = (uint32_t)std::min<uint64_t>((uint64_t)draw_count * 2 + 1024, 0xFFFFFFFFull);
-            ctx->draw_shrink_votes = 0;
-        }
-    } else {
-        ctx->draw_shrink_votes = 0;
-    }
-}
-
-// finish_lane, step 3c: the frame's sorted list is good: its quantile keys balance the buckets of the next frames of its
-// view. bucket() is only monotone for an ascending table, so that is checked, not assumed
-void learn_splitters(bgs_ctx* ctx, const Lane& L) {
-    const FramePlan& p = L.plan;
-    const Control& h = *L.h_ctl.ptr;
-    const uint32_t nkeys = BUCKET_COUNT * p.split_sub_out - 1u;
-    if (p.places != 4 || h.draw_count < BUCKET_COUNT || !splitters_ascending(h.splitters, nkeys) || !L.in.cloud) return;
-    int slot = find_splitter_slot(ctx, L.in.cloud, &L.in.view, &L.in.settings);
-    if (slot < 0) {  // a view not seen lately: take an empty slot, else the least recently used one
-        slot = 0;
-        for (int i = 0; i < bgs_ctx::SPLITTER_SLOTS; ++i) {
-            if (!ctx->split_slots[i].epoch) { slot = i; break; }
-            if (ctx->split_slots[i].last_used < ctx->split_slots[slot].last_used) slot = i;
-        }
-    }
-    auto& sl = ctx->split_slots[slot];
-    std::memcpy(sl.table.key, h.splitters, nkeys * sizeof(uint32_t));   // what the clean-up wrote
-    sl.table.sub = p.split_sub_out;   // (256 * sub - 1 quantile keys: what the frame's clean-up was asked for)
-    sl.cloud = L.in.cloud;
-    sl.n = p.n;
-    sl.sort_mode = L.in.settings.sort_mode;
-    std::memcpy(sl.transform, L.in.settings.transform, sizeof sl.transform);
-    view_pose(&L.in.view, sl.pos, sl.fwd);
-    std::memcpy(sl.clip_from_view, L.in.view.clip_from_view, sizeof sl.clip_from_view);
-    sl.viewport_wh[0] = L.in.view.viewport[2];
-    sl.viewport_wh[1] = L.in.view.viewport[3];
-    // the median key is ~bits(dist^2) of the median drawable splat (keys are 0xFFFFFFFF - bits)
-    const uint32_t mid_bits = 0xFFFFFFFFu - h.splitters[BUCKET_COUNT * p.split_sub_out / 2 - 1];
-    float d2;
-    std::memcpy(&d2, &mid_bits, 4);
-    sl.reach = (d2 > 0.0f && d2 < 3.0e38f) ? std::sqrt(d2) : 1.0f;
-    sl.epoch = ++ctx->split_epoch;
-    sl.last_used = ctx->seq;
-}
-
-// finish_lane, step 3d: list entries per visible splat (~1.2 when splats are smaller than a supertile, 15-20 when they
-// span many) -> the supertile level of the next frames (next_supertile_level, frame_params.h; relative to the level THIS
-// frame ran at, not to ctx->sup_level, which frames completed in the meantime may already have moved). Returns whether
-// the level moved.
-bool learn_level(bgs_ctx* ctx, const Lane& L, const FrameTotals& t) {
-    const FramePlan& p = L.plan;
-    const uint32_t lv = p.level;
-    double longer = 1.0;
-    // (a level whose edge equals a lower level's is that lower level: moving between them is not a change — no new
-    // capacity prediction, no vote reset, no level_changes)
-    const uint32_t target = canonical_supertile_level(
-        next_supertile_level((double)t.instances / (double)L.h_ctl.ptr->visible_count, lv, p.edges, &longer), p.edges);
-    const auto kit = ctx->kinds.find(L.in.kind);
-    // (a settled kind remembers its level for the next time the context comes back to it)
-    if (kit != ctx->kinds.end()) kit->second.sup_level = target;
-    // a frame of ANOTHER kind than the one the context is on by now (kinds alternate while frames are in flight): its
-    // verdict belongs to its own kind, not to ctx->sup_level
-    if (L.in.kind != ctx->cur_kind || target == lv) return target != lv;
-    if (ctx->sup_level != target) {
-        // lists of another level: predicted from THIS frame's longest list (coarser supertiles hold longer lists:
-        // entries scale with the ratio, lists with the area), never from the old hint
-        const double predicted = (double)t.longest * (target > lv ? longer : 1.0) * 1.25;
-        ctx->coarse_cap_hint = std::max<uint32_t>(pow2_ceil_u32((uint64_t)std::min(predicted, 1.0e9)), 4096u);
-        ctx->list_shrink_votes = 0;
-        ctx->level_changes += 1;
-        ctx->sup_level = target;
-    }
-    return true;
+    state.learn_draw_count(h.draw_count);
+    state.store_splitters(h.splitters, p.split_sub_out, p.places, h.draw_count, {L.in.cloud, p.n, &L.in.view, &L.in.settings}, ctx->seq);
+    AdaptiveState::LevelVerdict level{false, false};
+    if (scan_render && h.visible_count > 0) level = state.learn_level(L.in.kind, p.level, p.edges, t.instances, h.visible_count, t.longest);
+    if (level.changed) ctx->level_changes += 1;
+    if (scan_render && clean && !level.moved && L.in.kind) state.settle(L.in.kind, p.level);
 }
 
 // finish_lane, step 4: the lane's counters of the completed frame
@@ -563,7 +381,7 @@ void fill_stats(const bgs_ctx* ctx, Lane& L, const FrameTotals& t) {
     }
     stt.algorithmic_bytes = bytes;
     L.has_result = true;
-    L.result_kind = (uint8_t)(!render ? 1 : (scan ? 2 : 3) + (p.kept ? 2 : 0));
+    L.result_kind = p.ev_kind();
 }
 
 // Complete the frame pending on a lane: wait for it, check the watchdog word of the Control copy that
@@ -589,15 +407,7 @@ int finish_lane(bgs_ctx* ctx, Lane& L) {
             continue;
         }
 
-        if (p.render && p.scan) learn_feedback(ctx, L);
-        learn_draw_hint(ctx, h.draw_count);
-        learn_splitters(ctx, L);
-        const bool level_moved = p.render && p.scan && h.visible_count > 0 && learn_level(ctx, L, t);
-        // the kind is settled: a frame of it ran with everything it needed
-        if (p.render && p.scan && attempt == 0 && !level_moved && L.in.kind) {
-            if (ctx->kinds.size() >= (1u << 20)) ctx->kinds.clear();   // (12 MB of kinds: a host that hashes noise into its settings)
-            ctx->kinds[L.in.kind].sup_level = p.level;
-        }
+        learn_from_frame(ctx, L, t, /*clean=*/attempt == 0);
 
         // after a render only the drawable prefix of the list is materialised (the culled tail stays
         // in its side buffer); bgs_sort appends it so that callers get the reference's full list
@@ -620,14 +430,18 @@ int finish_lane(bgs_ctx* ctx, Lane& L) {
     return BGS_OK;
 }
 
+// The lane whose frame in flight was enqueued first, or -1. Completing lanes oldest first leaves the stats of the most
+// recent frame behind.
+int oldest_pending_lane(const bgs_ctx* ctx) {
+    int best = -1;
+    for (int i = 0; i < MAX_LANES; ++i)
+        if (ctx->lanes[i].pending && (best < 0 || ctx->lanes[i].seq < ctx->lanes[best].seq)) best = i;
+    return best;
+}
+
 int finish_all(bgs_ctx* ctx) {
-    // oldest first, so that the stats left behind are those of the most recent frame
-    for (;;) {
-        int best = -1;
-        for (int i = 0; i < MAX_LANES; ++i)
-            if (ctx->lanes[i].pending && (best < 0 || ctx->lanes[i].seq < ctx->lanes[best].seq)) best = i;
-        if (best < 0) break;
-        int rc = finish_lane(ctx, ctx->lanes[best]);
+    for (int i; (i = oldest_pending_lane(ctx)) >= 0;) {
+        int rc = finish_lane(ctx, ctx->lanes[i]);
         if (rc != BGS_OK) return rc;
     }
     for (auto& L : ctx->lanes) L.ready = false;
@@ -643,7 +457,7 @@ int collect_stats(bgs_ctx* ctx) {
     bgs_stats& stt = ctx->stats;
     if (ctx->profiling >= 1) {
         const uint8_t kind = R.result_kind;
-        const bool render = kind != 1, scan = kind == 2 || kind == 4, kept = kind >= 4;
+        const auto [render, scan, kept] = FramePlan::decode_ev_kind(kind);
         const int last = render ? 6 : 2;
         uint32_t used = 0;
         float acc[BGS_STAGE_COUNT] = {0, 0, 0, 0, 0, 0}, acc_total = 0.0f;
@@ -686,6 +500,8 @@ int collect_stats(bgs_ctx* ctx) {
 // Every choice of one frame, from its inputs and the context's learnt state. Allocates nothing and changes no state.
 FramePlan plan_frame(const bgs_ctx& ctx, const Lane& L, const FrameInputs& in) {
     FramePlan p;
+    const AdaptiveState& state = ctx.state;
+    const TileFeedback& F = L.feedback;
     const uint32_t flags = in.debug_flags;
     const bgs_settings* s = &in.settings;
     FrameParams& fp = p.fp;
@@ -695,7 +511,7 @@ FramePlan plan_frame(const bgs_ctx& ctx, const Lane& L, const FrameInputs& in) {
     const uint32_t n = p.n = fp.n;
     p.render = in.render;
     // A kept order (bgs_view.entries_device_ptr on a render): the caller's entries are the draw order. No keys, no digit
-    // places, no bucket sort, no splitter table read or left (learn_splitters wants 4 places): sort_mode and
+    // places, no bucket sort, no splitter table read or left (store_splitters wants 4 places): sort_mode and
     // radix_depth_bits do not reach such a frame.
     p.kept = in.render && in.view.entries_device_ptr != 0u && fp.n > 0u;
     p.places = p.kept ? 0u : depth_places(s);
@@ -714,31 +530,31 @@ FramePlan plan_frame(const bgs_ctx& ctx, const Lane& L, const FrameInputs& in) {
     // quadratically), a draw count that fits its geometry (a bucket holds <= BUCKET_CAP pairs) and the key
     // range of a recent frame; it is checked on the device and the frame re-run with the digit passes when
     // it does not work out (then bucket_block keeps the following frames on the passes for a while).
-    const bool hint = ctx.draw_hint_valid;
-    const int slot = (p.places == 4 && n > 0) ? find_splitter_slot(&ctx, in.cloud, &in.view, s) : -1;
+    const bool hint = state.draw_hint_valid;
+    const int slot = (p.places == 4 && n > 0) ? state.find_splitter_slot({in.cloud, n, &in.view, s}) : -1;
     // Geometry: NARROW buckets (BUCKET_CAP pairs, 256-thread workgroups) while 256 * BUCKET_SUB_KERNARG of them at BUCKET_TARGET
     // pairs hold the list (1.57 M pairs: every frame of the headline's kind), WIDE ones (BUCKET_CAP_WIDE, 1024 threads, 128 KB
     // of LDS) past that: a 5 M-pair list is 768 wide buckets instead of 2816 narrow ones, which keygen's scatter reached with
     // 1.5 pairs per (tile, bucket).
     const uint32_t narrow_max = BUCKET_COUNT * BUCKET_SUB_KERNARG * BUCKET_TARGET;
-    p.wide = (hint && ctx.draw_hint > narrow_max && !(flags & BGS_DEBUG_BUCKETS_NARROW)) || (flags & BGS_DEBUG_BUCKETS_WIDE);
+    p.wide = (hint && state.draw_hint > narrow_max && !(flags & BGS_DEBUG_BUCKETS_NARROW)) || (flags & BGS_DEBUG_BUCKETS_WIDE);
     const uint32_t cap_out = p.wide ? BUCKET_CAP_WIDE : BUCKET_CAP, target_out = p.wide ? BUCKET_TARGET_WIDE : BUCKET_TARGET;
-    p.bucket = p.places == 4 && n > 0 && !(flags & BGS_DEBUG_NO_BUCKET_SORT) && ctx.bucket_block == 0 && !in.force_passes &&
+    p.bucket = p.places == 4 && n > 0 && !(flags & BGS_DEBUG_NO_BUCKET_SORT) && state.bucket_block == 0 && !in.force_passes &&
                ((slot >= 0 && hint) || (flags & BGS_DEBUG_GUESSED_SPLITTERS)) &&
-               (!hint || ctx.draw_hint <= BUCKET_MAX * (cap_out / 4u) * 3u);
+               (!hint || state.draw_hint <= BUCKET_MAX * (cap_out / 4u) * 3u);
     // Buckets: 256 * sub, as many as keep a bucket near its target (narrow: sub = 1 up to 524 k drawable pairs — the
     // headline's 120 k —, 2 at 1 M, 3 at 1.5 M; wide: 1 up to 2.1 M, 3 at 5 M, 16 up to 50 M). A frame sorts with the table
     // its slot HOLDS (table.sub), in the geometry the hint asks for: a table that is too coarse for the list in that
     // geometry is not used, and every completed frame leaves a table of the sub the current hint asks for (split_sub_out).
     if (hint)
-        p.split_sub_out = std::min<uint32_t>(std::max<uint32_t>((ctx.draw_hint + BUCKET_COUNT * target_out - 1u) / (BUCKET_COUNT * target_out), 1u), BUCKET_SUB_MAX);
+        p.split_sub_out = std::min<uint32_t>(std::max<uint32_t>((state.draw_hint + BUCKET_COUNT * target_out - 1u) / (BUCKET_COUNT * target_out), 1u), BUCKET_SUB_MAX);
     if (flags & BGS_DEBUG_SPLIT_SUB_3) p.split_sub_out = std::max<uint32_t>(p.split_sub_out, BUCKET_SUB_KERNARG);
     if (flags & BGS_DEBUG_SPLIT_SUB_5) p.split_sub_out = std::max<uint32_t>(p.split_sub_out, 5u);
     if (p.bucket && slot >= 0) {
-        p.bucket_sub = std::min<uint32_t>(std::max<uint32_t>(ctx.split_slots[slot].table.sub, 1u), BUCKET_SUB_MAX);
-        if (hint && ctx.draw_hint > BUCKET_COUNT * p.bucket_sub * (cap_out / 4u) * 3u) p.bucket = false;   // too coarse a table
+        p.bucket_sub = std::min<uint32_t>(std::max<uint32_t>(state.split_slots[slot].table.sub, 1u), BUCKET_SUB_MAX);
+        if (hint && state.draw_hint > BUCKET_COUNT * p.bucket_sub * (cap_out / 4u) * 3u) p.bucket = false;   // too coarse a table
     }
-    if (p.bucket && slot >= 0) { p.split_slot = slot; p.split_epoch = ctx.split_slots[slot].epoch; }
+    if (p.bucket && slot >= 0) { p.split_slot = slot; p.split_epoch = state.split_slots[slot].epoch; }
     fp.sort_path = p.bucket ? 1u : 0u;
     if (p.kept) { fp.sort_mode = SORT_NONE; fp.key_shift = 0u; }   // (what the frame is to its kernels: a list drawn in entry order)
 
@@ -749,7 +565,7 @@ FramePlan plan_frame(const bgs_ctx& ctx, const Lane& L, const FrameInputs& in) {
     // 13.3 k frames/s at level 1, 14.6 k at level 2, 15.3 k at level 3). Images do not depend on the level; it follows
     // the entries-per-visible-splat ratio of the completed frames (finish_lane) unless a debug flag forces one.
     supertile_edges((uint32_t)fp.tiles_x, (uint32_t)fp.tiles_y, p.edges);
-    uint32_t level = ctx.sup_level;
+    uint32_t level = state.sup_level;
     if (flags & BGS_DEBUG_LEVEL_0) level = 0;
     else if (flags & BGS_DEBUG_LEVEL_1) level = 1;
     else if (flags & BGS_DEBUG_LEVEL_2) level = 2;
@@ -769,10 +585,10 @@ FramePlan plan_frame(const bgs_ctx& ctx, const Lane& L, const FrameInputs& in) {
     p.bin_blocks = ctx.num_cus * 3;
     p.binning_blocks = ctx.num_cus * 4;
     if (hint && !(flags & BGS_DEBUG_NO_DRAW_HINT)) {
-        const uint64_t want = (uint64_t)ctx.draw_hint / sort_tile_size(p.large) + 8;
+        const uint64_t want = (uint64_t)state.draw_hint / sort_tile_size(p.large) + 8;
         p.sort_blocks = (int)std::min<uint64_t>((uint64_t)p.sort_blocks, std::max<uint64_t>(want, 32));
-        p.bin_blocks = (int)std::min<uint64_t>((uint64_t)p.bin_blocks, std::max<uint64_t>((uint64_t)ctx.draw_hint / 256 + 8, 32));
-        p.binning_blocks = (int)std::min<uint64_t>((uint64_t)p.binning_blocks, std::max<uint64_t>((uint64_t)ctx.draw_hint / 1024 + 4, 16));
+        p.bin_blocks = (int)std::min<uint64_t>((uint64_t)p.bin_blocks, std::max<uint64_t>((uint64_t)state.draw_hint / 256 + 8, 32));
+        p.binning_blocks = (int)std::min<uint64_t>((uint64_t)p.binning_blocks, std::max<uint64_t>((uint64_t)state.draw_hint / 1024 + 4, 16));
     }
     p.want_srgb8 = in.render && (in.output_srgb8 || in.output_rgba16f || in.srgb8_target);
     p.out_format = !p.want_srgb8 ? 0u : ((in.output_rgba16f ? OUT_RGBA16F : OUT_SRGB8) |
@@ -783,8 +599,7 @@ FramePlan plan_frame(const bgs_ctx& ctx, const Lane& L, const FrameInputs& in) {
     // when several frames are in flight: the trained-like 1 M frame 5.75 -> 6.31 k frames/s with 8 lanes, but ALONE on the
     // chip its launch ends with its longest lists' serial chains, which do not saturate and only pay the checks (231 -> 272 us)
     p.raster_cleans = in.render && p.scan && fp.tiles_x > 0 && fp.tiles_y > 0 && !(flags & BGS_DEBUG_NO_RASTER_CLEANUP);
-    bool kind_midround = false;
-    if (ctx.depth > 1) { const auto kit = ctx.kinds.find(in.kind); if (kit != ctx.kinds.end()) kind_midround = kit->second.midround; }
+    const bool kind_midround = ctx.depth > 1 && state.midround(in.kind);
     p.raster = raster_instantiation(fp, p.level, kind_midround, ctx.depth, flags);
     p.ntiles = (uint32_t)(fp.tiles_x * fp.tiles_y);
     // the feedback buffers alternate with every completed frame: not under frame graphs
@@ -802,18 +617,18 @@ FramePlan plan_frame(const bgs_ctx& ctx, const Lane& L, const FrameInputs& in) {
     // frames/s; alone on the chip 6-21 % of the rasteriser's time).
     p.cost = feedback && (ctx.depth == 1 || !(flags & BGS_DEBUG_NO_TILE_COST_PIPELINED)) && !(flags & BGS_DEBUG_NO_TILE_COST);
     if (p.cost && p.ntiles > (uint32_t)(ctx.num_cus * 4 * raster_scan_waves_per_simd(fp))) {
-        // L.order holds a permutation of this grid's workgroups from the moment it was first made for the grid
+        // F.order holds a permutation of this grid's workgroups from the moment it was first made for the grid
         // (order_grid); it is made again from the newest completed costs every TILE_ORDER_REFRESH-th frame. (ensure_cost
         // keeps the lane's buffers, and what they hold, unless the grid outgrew them.)
-        const uint32_t grid = (uint32_t)fp.tiles_x | ((uint32_t)fp.tiles_y << 16);
+        const uint32_t grid = tile_grid_word(fp);
         const bool kept = cost_holds(L, p.ntiles);
-        const bool have_costs = kept && L.cost_done && L.cost_done != L.cost[L.cost_parity].ptr && L.cost_done_grid == grid;
-        const bool have_order = kept && L.order_grid == grid;
-        p.refresh = have_costs && (!have_order || L.order_age + 1u >= TILE_ORDER_REFRESH || (flags & BGS_DEBUG_ORDER_EVERY_FRAME));
+        const bool have_costs = kept && F.cost_done && F.cost_done != F.cost[F.cost_parity].ptr && F.cost_done_grid == grid;
+        const bool have_order = kept && F.order_grid == grid;
+        p.refresh = have_costs && (!have_order || F.order_age + 1u >= TILE_ORDER_REFRESH || (flags & BGS_DEBUG_ORDER_EVERY_FRAME));
         p.ordered = p.refresh || have_order;
     }
     // (a frame that makes the order makes its saturation counts anew, ahead of its own kernels)
-    p.sat_kind = !p.ordered ? 0 : (p.refresh ? L.cost_done_kind : L.order_kind);
+    p.sat_kind = !p.ordered ? 0 : (p.refresh ? F.cost_done_kind : F.order_kind);
     // ---- opt-in (bgs_set_graphs): a steady-state BINNING_SCAN frame as a hipGraph, captured once per
     // (lane, Control parity), then replayed with ONE node update — keygen's arguments carry the new
     // FrameParams, every other kernel reads them from the copy keygen leaves in device memory.
@@ -936,12 +751,12 @@ int enqueue_frame(bgs_ctx* ctx, Lane& L, const FrameInputs& in) {
     uint2* ranges = (uint2*)(scratch + lay.off_ranges);
     uint32_t* bin_status = (uint32_t*)(scratch + lay.off_bin_status);
     uint32_t* part_status = (uint32_t*)(scratch + lay.off_part_status);
-    const uint32_t grid = (uint32_t)fp.tiles_x | ((uint32_t)fp.tiles_y << 16);
-    uint8_t* const heavy_out = p.heavy ? L.heavy[L.heavy_parity].ptr : nullptr;
-    const uint8_t* const heavy_in = (p.heavy && L.heavy_done && L.heavy_done != heavy_out && L.heavy_done_grid == grid) ? L.heavy_done : nullptr;
-    uint16_t* const cost_out = p.cost ? L.cost[L.cost_parity].ptr : nullptr;
-    const uint16_t* const cost_in = p.refresh ? L.cost_done : nullptr;
-    uint16_t* const tile_order = p.ordered ? L.order.ptr : nullptr;
+    TileFeedback& F = L.feedback;
+    uint8_t* const heavy_out = p.heavy ? F.heavy[F.heavy_parity].ptr : nullptr;
+    const uint8_t* const heavy_in = (p.heavy && F.heavy_done && F.heavy_done != heavy_out && F.heavy_done_grid == tile_grid_word(fp)) ? F.heavy_done : nullptr;
+    uint16_t* const cost_out = p.cost ? F.cost[F.cost_parity].ptr : nullptr;
+    const uint16_t* const cost_in = p.refresh ? F.cost_done : nullptr;
+    uint16_t* const tile_order = p.ordered ? F.order.ptr : nullptr;
     uint2* const draw_list = L.entries[places & 1u].ptr;  // the passes ping-pong from entries[0]
     // SortMode::Rayon / Std sort ascending on the inverted key; the last step of either path un-inverts it
     const uint32_t final_xor = (fp.sort_mode == BGS_SORT_RAYON || fp.sort_mode == BGS_SORT_STD) ? 0xFFFFFFFFu : 0u;
@@ -961,7 +776,7 @@ int enqueue_frame(bgs_ctx* ctx, Lane& L, const FrameInputs& in) {
     kg.bucket_status = depth_status;  // the depth passes' look-back words are free in a bucket-sort frame
     if (bucket) {
         if (p.split_slot >= 0) {
-            const SplitterKeys& tk = ctx->split_slots[p.split_slot].table;
+            const SplitterKeys& tk = ctx->state.split_slots[p.split_slot].table;
             const uint32_t nkeys = BUCKET_COUNT * p.bucket_sub - 1u;
             if (p.bucket_sub <= BUCKET_SUB_KERNARG) std::memcpy(kg.split.key, tk.key, nkeys * sizeof(uint32_t));
             else std::memcpy(L.h_split_keys.ptr, tk.key, nkeys * sizeof(uint32_t));   // (the lane's previous frame is complete: nobody reads the staging)
@@ -1006,20 +821,19 @@ int enqueue_frame(bgs_ctx* ctx, Lane& L, const FrameInputs& in) {
     }
 
     // ---- 4. the context's and the lane's state
-    if (ctx->bucket_block > 0 && places == 4) ctx->bucket_block -= 1;
+    ctx->state.frame_enqueued(places, p.split_slot, ctx->seq + 1);   // (split_slot: of a bucket frame only)
+    F.enqueued(p);
     if (bucket) ctx->bucket_frames += 1;
     else if (places > 0) ctx->onesweep_frames += 1;
-    if (bucket && p.split_slot >= 0) ctx->split_slots[p.split_slot].last_used = ctx->seq + 1;
     if (p.cost) ctx->cost_frames += 1;
     if (p.ordered) ctx->ordered_frames += 1;
-    if (p.refresh) { ctx->order_refreshes += 1; L.order_kind = L.cost_done_kind; L.order_grid = grid; L.order_age = 0; }
-    else if (p.ordered) L.order_age += 1u;
+    if (p.refresh) ctx->order_refreshes += 1;
     const bool timed_frame = (ctx->frame_counter++ % ctx->profiling_stride) == 0;
     const int prof = timed_frame ? ctx->profiling : 0;
     const int last_mark = render ? 6 : 2;
     if (prof) {  // untimed frames do not consume a ring slot
         L.ev_head = (L.ev_head + 1) % EV_RING;
-        L.ev_kind[L.ev_head] = (uint8_t)(!render ? 1 : (scan ? 2 : 3) + (p.kept ? 2 : 0));
+        L.ev_kind[L.ev_head] = p.ev_kind();
         L.frames_timed += 1;
     }
     hipEvent_t* const ev = L.ev_ring[L.ev_head];
@@ -1137,18 +951,18 @@ int run(bgs_ctx* ctx, const bgs_cloud* cloud, const bgs_view* view, const bgs_se
     if (async && L.pending && (rc = finish_lane(ctx, L)) != BGS_OK) return rc;
     const FrameInputs in{cloud, *view, *s, render, /*allow_graph=*/async, render ? ctx->next_srgb8_target : nullptr,
                          ctx->output_srgb8, ctx->output_rgba16f, ctx->packed_only, ctx->debug_flags,
-                         render ? frame_kind(cloud, view, s) : 0ull, /*force_passes=*/false};
+                         render ? frame_kind(cloud->ptrs.n, cloud->ptrs.format, view, s) : 0ull, /*force_passes=*/false};
     if (!async) {
         ctx->recent = 0;
         ctx->regrow_count = 0;
-        if (render) switch_kind(ctx, in.kind);
+        if (render) ctx->state.switch_kind(in.kind);
         if ((rc = enqueue_frame(ctx, L, in)) != BGS_OK) return rc;
         ctx->next_srgb8_target = nullptr;   // (one-shot: it belonged to this frame)
         return finish_lane(ctx, L);  // re-runs the frame itself if a capacity was too small
     }
     L.ready = false;
-    const bool learn = ctx->kinds.find(in.kind) == ctx->kinds.end();
-    switch_kind(ctx, in.kind);
+    const bool learn = !ctx->state.settled(in.kind);
+    ctx->state.switch_kind(in.kind);
     if ((rc = enqueue_frame(ctx, L, in)) != BGS_OK) return rc;
     ctx->next_srgb8_target = nullptr;
     ctx->recent = ctx->next;
@@ -1159,14 +973,7 @@ int run(bgs_ctx* ctx, const bgs_cloud* cloud, const bgs_view* view, const bgs_se
         if ((rc = finish_lane(ctx, L)) != BGS_OK) return rc;
         L.ready = true;
         ctx->early_frames += 1;
-        // bounded: a kind whose frames never run clean (every frame re-run, a level that oscillates) is settled on anyway
-        if (ctx->kinds.find(in.kind) != ctx->kinds.end()) {
-            ctx->learning.erase(in.kind);   // (it ran clean: finish_lane settled it)
-        } else if (++ctx->learning[in.kind] >= bgs_ctx::LEARN_MAX) {
-            ctx->kinds[in.kind].sup_level = ctx->sup_level;
-            ctx->learning.erase(in.kind);
-        }
-        if (ctx->learning.size() >= (1u << 16)) ctx->learning.clear();   // (a host that hashes noise into its settings)
+        ctx->state.completed_early(in.kind);   // (bounded: LEARN_MAX of them settle the kind whatever they ran like)
     }
     return BGS_OK;
 }
@@ -1191,14 +998,10 @@ int run(bgs_ctx* ctx, const bgs_cloud* cloud, const bgs_view* view, const bgs_se
 // So staleness is slow at worst, never wrong, and a small step (the usual case) keeps every hint useful.
 int apply_particle_step(bgs_ctx* ctx, bgs_cloud* cloud, void* behaviors, uint32_t count, float dt) {
     if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, BGS_EHIP, "hipSetDevice failed");
-    for (;;) {   // oldest first, so that the stats left behind are those of the most recent frame
-        int best = -1;
-        for (int i = 0; i < MAX_LANES; ++i)
-            if (ctx->lanes[i].pending && (best < 0 || ctx->lanes[i].seq < ctx->lanes[best].seq)) best = i;
-        if (best < 0) break;
-        int rc = finish_lane(ctx, ctx->lanes[best]);
+    for (int i; (i = oldest_pending_lane(ctx)) >= 0;) {
+        int rc = finish_lane(ctx, ctx->lanes[i]);
         if (rc != BGS_OK) return rc;
-        ctx->lanes[best].ready = true;
+        ctx->lanes[i].ready = true;
     }
     if (!ctx->step_done) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->step_done, hipEventDisableTiming));
     hipStream_t st = ctx->lanes[0].stream;

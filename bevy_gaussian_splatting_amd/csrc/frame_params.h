@@ -70,6 +70,9 @@ inline void fill_frame_params(uint32_t n, const bgs_view* view, const bgs_settin
     }
 }
 
+// a frame's tile grid in one word (what tile feedback left by one frame is matched against the next frame by)
+inline uint32_t tile_grid_word(const FrameParams& fp) { return (uint32_t)fp.tiles_x | ((uint32_t)fp.tiles_y << 16); }
+
 // ---- adaptive policies of the host side (plain functions so that the CPU suite can test them) -----------
 
 inline uint32_t pow2_ceil_u32(uint64_t v) {

@@ -84,6 +84,10 @@ class ShimOut(ctypes.Structure):
     ]
 
 
+# what shim_state_get reports of an AdaptiveState (csrc/adaptive_state.h), in its order; kinds / learning: their sizes
+STATE_FIELDS = ("draw_hint", "draw_hint_valid", "draw_shrink_votes", "sup_level", "coarse_cap_hint", "list_shrink_votes", "split_epoch",
+                "split_failed_epoch", "bucket_block", "bucket_fail_streak", "cur_kind", "kinds", "learning")
+
 _shim = None
 
 
@@ -92,7 +96,7 @@ def shim() -> ctypes.CDLL:
     global _shim
     if _shim is not None:
         return _shim
-    deps = [SHIM_SRC, os.path.join(CSRC, "..", "..", "include", "bgs_diag.h")] + [os.path.join(CSRC, f) for f in ("splat_math.h", "exact_log.h", "bgs_device.h", "frame_params.h", "device_buffer.h")]
+    deps = [SHIM_SRC, os.path.join(CSRC, "..", "..", "include", "bgs_diag.h")] + [os.path.join(CSRC, f) for f in ("splat_math.h", "exact_log.h", "bgs_device.h", "frame_params.h", "adaptive_state.h", "device_buffer.h")]
     if not os.path.exists(SHIM_LIB) or any(os.path.getmtime(d) > os.path.getmtime(SHIM_LIB) for d in deps):
         subprocess.run(
             ["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fopenmp", "-shared", "-fPIC",
@@ -145,6 +149,26 @@ def shim() -> ctypes.CDLL:
                             ("shim_buf_move_assign", [vp, vp], None), ("shim_buf_move_new", [vp], vp),
                             ("shim_buf_release_and_free", [vp], None),
                             ("shim_buf_reserve_group", [vp, vp, vp, ctypes.c_uint64], ctypes.c_int)):
+        getattr(l, name).argtypes, getattr(l, name).restype = args, res
+    # the learnt state and its rules (adaptive_state.h): st is shim_state_new's handle, a cloud is (identity, n)
+    u32, u64, cint, u32p = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32)
+    viewp, setp = ctypes.POINTER(BgsView), ctypes.POINTER(BgsSettings)
+    for name, args, res in (("shim_state_new", [], vp), ("shim_state_delete", [vp], None),
+                            ("shim_frame_kind", [u32, u32, viewp, setp], u64),
+                            ("shim_state_switch_kind", [vp, u64], None), ("shim_state_settle", [vp, u64, u32], None),
+                            ("shim_state_completed_early", [vp, u64], None), ("shim_state_learn_saturation", [vp, u64, u32], None),
+                            ("shim_state_learn_draw_count", [vp, u32], None),
+                            ("shim_state_find_splitter_slot", [vp, vp, u32, viewp, setp], cint),
+                            ("shim_state_store_splitters", [vp, u32p, u32, u32, u32, vp, u32, viewp, setp, u64], None),
+                            ("shim_state_frame_enqueued", [vp, u32, cint, u64], None),
+                            ("shim_state_learn_bucket_sort", [vp, u32, cint, u64], cint),
+                            ("shim_state_list_capacity", [vp, u32, cint], u32),
+                            ("shim_state_learn_list_capacity", [vp, u32, u32, u32], cint),
+                            ("shim_state_learn_level", [vp, u64, u32, u32p, u64, u32, u32], cint),
+                            ("shim_state_distrust", [vp], None), ("shim_state_forget_cloud", [vp, vp], None),
+                            ("shim_state_reset", [vp], None), ("shim_state_get", [vp, u64p], None),
+                            ("shim_state_slot", [vp, cint, u64p, fp, u32p, u32], None),
+                            ("shim_state_kind", [vp, u64, u32p, ctypes.POINTER(cint)], cint)):
         getattr(l, name).argtypes, getattr(l, name).restype = args, res
     assert l.shim_frame_params_size() == ctypes.sizeof(FrameParamsC)
     assert l.shim_scratch_layout_size() == ctypes.sizeof(ScratchLayoutC)
