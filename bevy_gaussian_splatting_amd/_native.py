@@ -31,7 +31,7 @@ STAGE_NAMES = ("keygen", "depth_sort", "project", "tile_sort", "ranges", "raster
 COMM_ID_BYTES = 128
 # what this binding was written against (include/bgs.h BGS_VERSION_*): load() hands it to bgs_abi_check together with
 # the sizes of its ctypes structs
-ABI_VERSION = (0 << 16) | 7
+ABI_VERSION = (0 << 16) | 8
 
 
 class BgsSortEntry(ctypes.Structure):
@@ -77,6 +77,26 @@ class BgsFrameListsInfo(ctypes.Structure):
                 ("sup_edge", ctypes.c_uint32), ("sup_x", ctypes.c_uint32), ("sup_y", ctypes.c_uint32), ("level", ctypes.c_uint32),
                 ("coarse_cap", ctypes.c_uint32), ("wide_bin", ctypes.c_uint32), ("instance_count", ctypes.c_uint32),
                 ("reserved", ctypes.c_uint32)]
+
+
+class BgsScratchLayout(ctypes.Structure):
+    """bgs_scratch_layout (include/bgs_diag.h): the lane's scratch region, [Control 0 | the REGIONS | Control 1]."""
+
+    REGIONS = ("off_depth_status", "off_scan_status", "off_tile_status", "off_ranges", "off_bin_status", "off_part_status",
+               "off_ctl1")   # in address order, behind the first Control block at 0
+    _fields_ = [("bytes", ctypes.c_uint64)] + [(name, ctypes.c_uint64) for name in REGIONS] + \
+               [("depth_tiles", ctypes.c_uint64), ("inst_tiles", ctypes.c_uint64), ("inst_cap", ctypes.c_uint64),
+                ("n", ctypes.c_uint32), ("pass_stride", ctypes.c_uint32)]
+
+
+class BgsFrameLeftoversInfo(ctypes.Structure):
+    """bgs_frame_leftovers_info (include/bgs_diag.h)."""
+
+    _fields_ = [("dirty_words", ctypes.c_uint64)] + \
+               [(name, ctypes.c_uint32) for name in ("ctl_block", "scratch_clean", "scratch_reset", "raster_cleans", "bucket", "places",
+                                                     "large", "wide", "wide_bin", "kept", "bucket_sub", "split_sub_out", "keygen_tile",
+                                                     "n", "ntiles", "raster_mode", "strips_appended", "graph_replay", "binning",
+                                                     "control_bytes", "culled_tail", "reserved")]
 
 
 class BgsRasterSelftest(ctypes.Structure):
@@ -172,6 +192,7 @@ PROTOTYPES = (
     ("bgs_selftest_bucket_sort", c_int, (vp, u32, u32, u32, up, up, u32, up, u64, up)),
     ("bgs_selftest_keygen_buckets", c_int, (vp, vp, view_p, settings_p, up, u32, u32, u32, u32, up, up, u64, up, u64, up)),
     ("bgs_selftest_raster", c_int, (vp, POINTER(BgsRasterSelftest), fp, fp, u64, vp, vp, u64, up)),
+    ("bgs_debug_frame_leftovers", c_int, (vp, vp, u64, vp, u32, POINTER(BgsScratchLayout), POINTER(BgsFrameLeftoversInfo))),
 )
 EXPORTED_SYMBOLS = tuple(name for name, _, _ in PROTOTYPES)
 

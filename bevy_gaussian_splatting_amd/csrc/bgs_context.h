@@ -257,6 +257,9 @@ struct Lane {
     // bgs_debug_frame_records: a frame's own block keeps what its project kernel left (visible_count, color_max_bits)
     // until the lane's next frame. Null after a bgs_sort and after anything else that rewrites the scratch region.
     const Control* last_ctl = nullptr;
+    // ... and, for bgs_debug_frame_leftovers, whether that frame was a graph replay and whether its rasteriser's grid had
+    // the strip workgroups behind it
+    bool last_replay = false, last_strips = false;
 
     bgs_stats result{};      // counters of the last completed frame of this lane (no timings)
     bool has_result = false;

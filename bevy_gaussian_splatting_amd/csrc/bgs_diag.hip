@@ -367,6 +367,87 @@ int bgs_debug_frame_lists(bgs_ctx* ctx, uint32_t* host_totals, uint32_t totals_c
     return BGS_OK;
 }
 
+// What lane 0's last frame left for the one behind it: the lane's scratch region and its pinned Control, as they are. Where
+// each is final (bgs_frame.hip, render_kernels.hip):
+//   scratch        a raster_cleans frame's rasteriser zeroes, at its start, the chain words the frame used and the lane's
+//                  OTHER Control block; nothing writes the region behind it until the lane's next frame. Any other frame
+//                  leaves what its kernels wrote on top of the memset ahead of it.
+//   pinned Control written by the last workgroup of that rasteriser, or by the copy enqueued behind the frame; finish_lane
+//                  only reads it.
+// A word that is not zero outside the frame's own Control block while the lane believes the region clean would be read as a
+// published look-back word by the next frame's chained scans: the hook takes the lane's belief back, and that frame memsets.
+int bgs_debug_frame_leftovers(bgs_ctx* ctx, void* host_scratch, uint64_t scratch_capacity_bytes, void* host_control,
+                              uint32_t control_capacity_bytes, bgs_scratch_layout* layout_out, bgs_frame_leftovers_info* info_out) {
+    static_assert(sizeof(bgs_scratch_layout) == sizeof(ScratchLayout) && offsetof(bgs_scratch_layout, off_ctl1) == offsetof(ScratchLayout, off_ctl1) &&
+                      offsetof(bgs_scratch_layout, inst_cap) == offsetof(ScratchLayout, inst_cap) &&
+                      offsetof(bgs_scratch_layout, pass_stride) == offsetof(ScratchLayout, pass_stride),
+                  "bgs_scratch_layout is ScratchLayout, field by field");
+    if (!ctx) return fail(nullptr, BGS_EINVAL, "ctx is NULL");
+    if (!info_out || !layout_out) return fail(ctx, BGS_EINVAL, "frame leftovers: layout_out and info_out must be non-NULL");
+    for (const Lane& lane : ctx->lanes)
+        if (lane.pending) return fail(ctx, BGS_EINVAL, "frame leftovers: frames are in flight");
+    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, BGS_EHIP, "hipSetDevice failed");
+    int rc = finish_all(ctx);
+    if (rc != BGS_OK) return rc;
+    Lane& L = ctx->lanes[0];
+    if (!L.has_result || !L.plan.render || !L.last_ctl || !L.stream || !L.scratch.ptr)
+        return fail(ctx, BGS_EINVAL, "frame leftovers: no frame has been rendered (or a bgs_sort / bgs_radix_sort_pairs ran since)");
+    if (L.in.allow_graph && ctx->depth != 1)
+        return fail(ctx, BGS_EINVAL, "frame leftovers: the last frame was an async frame at a pipeline depth other than 1");
+    const FramePlan& p = L.plan;
+    const ScratchLayout& lay = L.layout;
+    const uint8_t* const own = reinterpret_cast<const uint8_t*>(L.last_ctl);
+    if (lay.bytes % 4u != 0u || lay.bytes > L.scratch.capacity || lay.off_ctl1 + sizeof(Control) > lay.bytes ||
+        (own != L.scratch.ptr && own != L.scratch.ptr + lay.off_ctl1))
+        return fail(ctx, BGS_EINTERNAL, "frame leftovers: the lane's scratch layout does not fit its region");
+    hipStream_t st = L.stream;
+    std::vector<uint32_t> words((size_t)(lay.bytes / 4u));
+    HIP_TRY(ctx, hipMemcpyAsync(words.data(), L.scratch.ptr, (size_t)lay.bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    const size_t own_first = (size_t)(own - L.scratch.ptr) / 4u, own_end = own_first + sizeof(Control) / 4u;
+    uint64_t dirty = 0;
+    for (size_t i = 0; i < words.size(); ++i)
+        if (words[i] != 0u && (i < own_first || i >= own_end)) dirty += 1u;
+    bgs_frame_leftovers_info info{};
+    info.dirty_words = dirty;
+    info.ctl_block = own == L.scratch.ptr ? 0u : 1u;
+    info.scratch_clean = L.scratch_clean ? 1u : 0u;
+    if (dirty != 0u && L.scratch_clean) {   // the lane's next frame memsets (enqueue_frame: need_memset)
+        L.scratch_clean = false;
+        info.scratch_reset = 1u;
+    }
+    info.raster_cleans = p.raster_cleans ? 1u : 0u;
+    info.bucket = p.bucket ? 1u : 0u;
+    info.places = p.places;
+    info.large = p.large ? 1u : 0u;
+    info.wide = p.wide ? 1u : 0u;
+    info.wide_bin = p.wide_bin ? 1u : 0u;
+    info.kept = p.kept ? 1u : 0u;
+    info.bucket_sub = p.bucket_sub;
+    info.split_sub_out = p.split_sub_out;
+    info.keygen_tile = p.kept ? KEYGEN_TILE : keygen_tile_splats(p.n);   // (the compaction's tile: entries_kernels.hip)
+    info.n = p.n;
+    info.ntiles = p.ntiles;
+    info.raster_mode = (uint32_t)p.raster.mode;
+    info.strips_appended = L.last_strips ? 1u : 0u;
+    info.graph_replay = L.last_replay ? 1u : 0u;
+    info.binning = p.scan ? BINNING_SCAN : BINNING_SORT;
+    info.control_bytes = (uint32_t)sizeof(Control);
+    info.culled_tail = p.culled_tail ? 1u : 0u;
+    std::memcpy(layout_out, &lay, sizeof lay);
+    *info_out = info;
+    if (!host_scratch && !host_control) return BGS_OK;   // the sizes only
+    if (!host_scratch || scratch_capacity_bytes < lay.bytes)
+        return fail(ctx, BGS_EINVAL, "frame leftovers: host_scratch holds " + std::to_string(scratch_capacity_bytes) + " bytes, the lane's scratch region is " +
+                                         std::to_string(lay.bytes));
+    if (!host_control || control_capacity_bytes < sizeof(Control))
+        return fail(ctx, BGS_EINVAL, "frame leftovers: host_control holds " + std::to_string(control_capacity_bytes) + " bytes, the Control block is " +
+                                         std::to_string(sizeof(Control)));
+    std::memcpy(host_scratch, words.data(), (size_t)lay.bytes);
+    std::memcpy(host_control, L.h_ctl.ptr, sizeof(Control));
+    return BGS_OK;
+}
+
 // bucket_sort_kernel alone, on the caller's bucket contents: a zeroed Control with the caller's counts, slot regions that
 // hold each bucket's pairs at their start and 0xFF bytes behind them, an output list of n + BGS_SELFTEST_BUCKET_GUARD entries
 // of 0xFF bytes. What the kernel indexes (sort_kernels.hip): bucket_count[i < nb], a region's first min(count, cap) slots

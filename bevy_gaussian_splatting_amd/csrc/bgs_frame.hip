@@ -901,6 +901,7 @@ int enqueue_frame(bgs_ctx* ctx, Lane& L, const FrameInputs& in) {
             launch_encode_srgb8(st, L.fb.ptr, L.fb8.ptr, (uint32_t)fp.width * (uint32_t)fp.height, L.d_fp.ptr, p.out_format);
         return hipGetLastError();
     };
+    const uint64_t replays_before = ctx->graph_replays;
     if (p.graph_ok && !need_memset && prof == 0 && have_keygen) {
         if ((rc = launch_graph(ctx, L, L.graph[0][L.ctl_parity], graph_key(p, in, L, kg, coarse_cap), kg, issue)) != BGS_OK) return rc;
     } else if (p.graph_ok && !need_memset && prof == 0 && have_compact) {
@@ -927,6 +928,8 @@ int enqueue_frame(bgs_ctx* ctx, Lane& L, const FrameInputs& in) {
     L.last_sorted = draw_list;
     L.last_sorted_n = n;
     L.last_ctl = render ? ctl : nullptr;
+    L.last_replay = ctx->graph_replays != replays_before;
+    L.last_strips = render && scan && p.raster.mode != 0 && heavy_in != nullptr;   // (launch_raster_scan's grid)
     L.fb_valid = !(p.out_format & OUT_SKIP_F32) || (flags & BGS_DEBUG_SEPARATE_ENCODE);
     L.fb8_is_f16 = (p.out_format & OUT_RGBA16F) != 0u;
     L.fb8_valid = p.want_srgb8;

@@ -739,6 +739,25 @@ class GaussianSplattingPlugin:
             out.update(instance_count=int(info.instance_count), instances=entries[:count], ranges=ranges)
         return out
 
+    def debug_frame_leftovers(self) -> dict:
+        """`bgs_debug_frame_leftovers`: what lane 0's last completed `render` left for the frame behind it, at any pipeline
+        depth. `scratch` uint32[layout.bytes / 4] (the lane's whole scratch region), `layout` (a BgsScratchLayout),
+        `control` uint32[control_bytes / 4] (the lane's pinned host Control) and every field of bgs_frame_leftovers_info by
+        its name (`dirty_words`, `ctl_block`, `scratch_clean`, ...). A read-back that finds dirty words under a clean flag
+        takes the flag back (`scratch_reset`). Test hook; raises when there is no such frame (see include/bgs_diag.h)."""
+        info, layout = _native.BgsFrameLeftoversInfo(), _native.BgsScratchLayout()
+        self._check(self._lib.bgs_debug_frame_leftovers(self._ctx, None, 0, None, 0, ctypes.byref(layout), ctypes.byref(info)))
+        first = {name: int(getattr(info, name)) for name, _ in info._fields_}
+        scratch = np.zeros(int(layout.bytes) // 4, np.uint32)
+        control = np.zeros(int(info.control_bytes) // 4, np.uint32)
+        self._check(self._lib.bgs_debug_frame_leftovers(self._ctx, scratch.ctypes.data_as(ctypes.c_void_p), scratch.nbytes,
+                                                        control.ctypes.data_as(ctypes.c_void_p), control.nbytes, ctypes.byref(layout),
+                                                        ctypes.byref(info)))
+        if scratch.nbytes != int(layout.bytes) or int(info.dirty_words) != first["dirty_words"]:
+            raise RuntimeError("the frame changed between the two calls of bgs_debug_frame_leftovers")
+        # (the first call is the one that saw the lane's flag as the frame left it: it may have taken it back)
+        return dict(first, scratch=scratch, layout=layout, control=control)
+
     def selftest_bucket_sort(self, sub: int, wide: int, key_xor: int, counts: np.ndarray, pairs: np.ndarray) -> dict:
         """`bgs_selftest_bucket_sort`: bucket_sort_kernel alone on `counts` uint32[256 * sub] (Control::bucket_count) and
         `pairs` uint32[n, 2] (key, index; bucket after bucket, min(count, capacity) of each, in arrival order). `out`

@@ -283,6 +283,50 @@ int bgs_selftest_raster(bgs_ctx* ctx, const bgs_raster_selftest* in, float* host
                         uint64_t image_capacity_floats, uint16_t* host_cost, uint8_t* host_heavy, uint64_t heavy_capacity_bytes,
                         uint32_t* error_out);
 
+/* What lane 0's last completed bgs_render left for the frame behind it, copied to host memory as it is — at ANY pipeline
+ * depth (tests/test_frame_leftovers_gpu.py). A BGS_BINNING_SCAN frame whose plan has raster_cleans set takes neither a memset
+ * of the lane's scratch region nor a copy of its Control block: its rasteriser zeroes the chain words the frame used and the
+ * lane's OTHER Control block, and writes the pinned host Control; the lane's next frame is launched on the strength of
+ * Lane::scratch_clean alone. Returned:
+ *   host_scratch   the lane's whole scratch region (layout_out->bytes bytes): [Control 0 | depth status | scan status | tile
+ *                  status | ranges | bin status | partition status | Control 1], the parts at layout_out's offsets;
+ *   layout_out     the layout the region was made with (csrc/frame_params.h ScratchLayout, field by field);
+ *   host_control   the lane's pinned host Control (info_out->control_bytes bytes) as the frame's completion left it: written by
+ *                  the frame's rasteriser (raster_cleans) or by the copy behind the frame;
+ *   info_out       ctl_block: which of the two Control blocks the frame used (0: at offset 0, 1: at layout_out->off_ctl1; the
+ *                  lane's parity before the flip); scratch_clean as the lane held it when the hook was called; the plan's
+ *                  raster_cleans, bucket, places, large (4096-pair onesweep tiles), wide, wide_bin, kept, bucket_sub and
+ *                  split_sub_out; culled_tail (keygen or the compaction wrote the culled tail: a bucket frame's keygen has a chain only then);
+ *                  keygen_tile: splats per tile of the frame's keygen (2048 for a kept order's compaction); n; ntiles and raster_mode (the
+ *                  rasteriser's grid is ceil(ntiles / 4) workgroups, plus 256 strip workgroups when strips_appended);
+ *                  graph_replay: 1 when the frame was a replay of a captured graph; binning (0 scan, 1 sort);
+ *                  dirty_words: how many 32-bit words of the region OUTSIDE the frame's own Control block are not zero.
+ * If dirty_words != 0 while the lane's scratch_clean is true, the hook sets scratch_clean to false before it returns (and
+ * reports scratch_reset = 1): the lane's next frame then takes the memset path, so that words a clean-up missed never reach
+ * the chained scans of a later frame — a failed check costs a test, not a machine. info_out->scratch_clean is the value
+ * before that.
+ * With host_scratch and host_control both NULL only layout_out and info_out are filled (a caller sizes its buffers with them).
+ * Launches no kernel: copies on the lane's stream, then waits for them. BGS_EINVAL, with the reason in bgs_last_error, when
+ * no frame has been rendered (or a bgs_sort / bgs_radix_sort_pairs ran since), when frames are in flight, when the last frame
+ * was an async one at a pipeline depth other than 1 (at depth 1 a completed async frame — the only kind a captured graph
+ * replays — ran on lane 0 and is read like a synchronous one), and when a capacity (bytes) is too small — nothing is written
+ * to the host buffers then. Test hook. */
+typedef struct bgs_scratch_layout {
+    uint64_t bytes;
+    uint64_t off_depth_status, off_scan_status, off_tile_status, off_ranges, off_bin_status, off_part_status, off_ctl1;
+    uint64_t depth_tiles, inst_tiles, inst_cap;
+    uint32_t n, pass_stride;
+} bgs_scratch_layout;
+typedef struct bgs_frame_leftovers_info {
+    uint64_t dirty_words;
+    uint32_t ctl_block, scratch_clean, scratch_reset, raster_cleans;
+    uint32_t bucket, places, large, wide, wide_bin, kept, bucket_sub, split_sub_out;
+    uint32_t keygen_tile, n, ntiles, raster_mode, strips_appended, graph_replay, binning, control_bytes;
+    uint32_t culled_tail, reserved;
+} bgs_frame_leftovers_info;
+int bgs_debug_frame_leftovers(bgs_ctx* ctx, void* host_scratch, uint64_t scratch_capacity_bytes, void* host_control,
+                              uint32_t control_capacity_bytes, bgs_scratch_layout* layout_out, bgs_frame_leftovers_info* info_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -62,6 +62,21 @@ class ScratchLayoutC(ctypes.Structure):
                  ("n", ctypes.c_uint32), ("pass_stride", ctypes.c_uint32)])
 
 
+# what shim_control_offsets reports, in its order: everything in 32-bit words (bucket_max_keys: BUCKET_MAX, the length of
+# Control::splitters and Control::bucket_count)
+CONTROL_FIELDS = ("words", "header_words", "draw_count", "instance_count", "error", "visible_count", "splat_count", "sort_overflow",
+                  "bucket_max", "strip_tiles", "saturated_tiles_prev", "ticket", "color_max_bits", "hist_depth", "coarse_total",
+                  "splitters", "bucket_count", "bucket_max_keys")
+
+
+def control_offsets() -> dict:
+    """Word offsets of the fields of a Control block (csrc/bgs_device.h), from the host build of the header itself."""
+    out = (ctypes.c_uint32 * 32)()
+    got = shim().shim_control_offsets(out)
+    assert got == len(CONTROL_FIELDS)
+    return {name: int(out[i]) for i, name in enumerate(CONTROL_FIELDS)}
+
+
 def scratch_layout(n: int, inst_cap: int) -> ScratchLayoutC:
     out = ScratchLayoutC()
     shim().shim_scratch_layout(n, inst_cap, ctypes.byref(out))
@@ -139,6 +154,8 @@ def shim() -> ctypes.CDLL:
     l.shim_distance_to_camera.restype = ctypes.c_float
     l.shim_scratch_layout.argtypes = [ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(ScratchLayoutC)]
     l.shim_scratch_layout.restype = None
+    l.shim_control_offsets.argtypes = [ctypes.POINTER(ctypes.c_uint32)]
+    l.shim_control_offsets.restype = ctypes.c_uint32
     l.shim_scratch_layout_size.argtypes = []
     l.shim_scratch_layout_size.restype = ctypes.c_uint32
     i64p, u64p, vp = ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p

@@ -81,6 +81,22 @@ int shim_raster_scan_mode(int variant, uint32_t samples, int overlay, uint32_t l
 void shim_scratch_layout(uint32_t n, uint64_t inst_cap, ScratchLayout* out) { *out = scratch_layout(n, inst_cap); }
 uint32_t shim_scratch_layout_size(void) { return (uint32_t)sizeof(ScratchLayout); }
 
+// where the words of a Control block lie (bgs_device.h), in 32-bit words: sizeof(Control), CONTROL_HEADER_WORDS, then the
+// offsets named in tests/helpers.py CONTROL_FIELDS, in that order; returns how many words `out` was given
+uint32_t shim_control_offsets(uint32_t* out) {
+    const uint32_t v[] = {(uint32_t)(sizeof(Control) / 4u), CONTROL_HEADER_WORDS,
+                          (uint32_t)(offsetof(Control, draw_count) / 4u), (uint32_t)(offsetof(Control, instance_count) / 4u),
+                          (uint32_t)(offsetof(Control, error) / 4u), (uint32_t)(offsetof(Control, visible_count) / 4u),
+                          (uint32_t)(offsetof(Control, splat_count) / 4u), (uint32_t)(offsetof(Control, sort_overflow) / 4u),
+                          (uint32_t)(offsetof(Control, bucket_max) / 4u), (uint32_t)(offsetof(Control, strip_tiles) / 4u),
+                          (uint32_t)(offsetof(Control, saturated_tiles_prev) / 4u), (uint32_t)(offsetof(Control, ticket) / 4u),
+                          (uint32_t)(offsetof(Control, color_max_bits) / 4u), (uint32_t)(offsetof(Control, hist_depth) / 4u),
+                          (uint32_t)(offsetof(Control, coarse_total) / 4u), (uint32_t)(offsetof(Control, splitters) / 4u),
+                          (uint32_t)(offsetof(Control, bucket_count) / 4u), BUCKET_MAX};
+    for (uint32_t i = 0; i < sizeof v / sizeof v[0]; ++i) out[i] = v[i];
+    return (uint32_t)(sizeof v / sizeof v[0]);
+}
+
 // ---- Buffer (device_buffer.h) over a memory policy that counts: live allocations and their peak, calls, the bytes of the
 // last request; fail_at = k makes the k-th alloc() from now fail
 struct CountingMem {
