@@ -31,7 +31,7 @@ STAGE_NAMES = ("keygen", "depth_sort", "project", "tile_sort", "ranges", "raster
 COMM_ID_BYTES = 128
 # what this binding was written against (include/bgs.h BGS_VERSION_*): load() hands it to bgs_abi_check together with
 # the sizes of its ctypes structs
-ABI_VERSION = (0 << 16) | 8
+ABI_VERSION = (0 << 16) | 9
 
 
 class BgsSortEntry(ctypes.Structure):
@@ -114,6 +114,9 @@ SELFTEST_RASTER_GUARD = 64   # BGS_SELFTEST_RASTER_GUARD (include/bgs_diag.h)
 HEAVY_CAP, HEAVY_LIST_OFFSET = 256, 128
 HEAVY_FLAGS_OFFSET = HEAVY_LIST_OFFSET + 2 * HEAVY_CAP
 SELFTEST_BUCKET_GUARD = 64   # BGS_SELFTEST_BUCKET_GUARD (include/bgs_diag.h)
+GRID_CAP_MAX = 4096   # BGS_GRID_CAP_MAX
+FRAME_GRIDS_WORDS = 16   # BGS_FRAME_GRIDS_WORDS
+GRID_KERNELS = ("front", "depth", "project", "bin", "tile_sort")   # enum bgs_grid_kernel, in order
 
 
 vp, u32, u64 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64
@@ -193,6 +196,8 @@ PROTOTYPES = (
     ("bgs_selftest_keygen_buckets", c_int, (vp, vp, view_p, settings_p, up, u32, u32, u32, u32, up, up, u64, up, u64, up)),
     ("bgs_selftest_raster", c_int, (vp, POINTER(BgsRasterSelftest), fp, fp, u64, vp, vp, u64, up)),
     ("bgs_debug_frame_leftovers", c_int, (vp, vp, u64, vp, u32, POINTER(BgsScratchLayout), POINTER(BgsFrameLeftoversInfo))),
+    ("bgs_set_grid_cap", c_int, (vp, u32)),
+    ("bgs_debug_frame_grids", c_int, (vp, up, u32)),
 )
 EXPORTED_SYMBOLS = tuple(name for name, _, _ in PROTOTYPES)
 

@@ -23,6 +23,7 @@
 #include "bgs_device.h"
 #include "adaptive_state.h"
 #include "device_buffer.h"
+#include "entries_math.h"
 #include "frame_params.h"
 #include "kernels.h"
 
@@ -116,6 +117,7 @@ struct FrameInputs {
     uint32_t debug_flags = 0;
     uint64_t kind = 0;                  // frame_kind() (0: a bgs_sort)
     bool force_passes = false;          // the digit passes, not the bucket sort: a re-run of a frame whose bucket sort gave up
+    uint32_t grid_cap = 0;              // bgs_set_grid_cap as it was when the frame was enqueued (0: off): a re-run keeps its grids
 };
 
 // Every choice of one frame (plan_frame, bgs_frame.hip): enqueue_frame allocates, binds and issues it, finish_lane reads
@@ -135,6 +137,9 @@ struct FramePlan {
     uint32_t edges[4] = {6, 8, 16, 32}, level = 1, sup_edge = 8, num_st = 0;   // supertiles
     bool large = false, wide_bin = false, want_srgb8 = false;
     int sort_blocks = 0, bin_blocks = 0, binning_blocks = 0;
+    // the grids plan_frame does not size by the draw hint: keygen's (ordered instantiations) and the compaction's, BINNING_SORT's
+    // project_emit and its two tile-id passes. All six are what bgs_set_grid_cap caps (FrameInputs::grid_cap)
+    int front_blocks = 0, emit_blocks = 0, tile_sort_blocks = 0;
     uint32_t out_format = 0, ntiles = 0;
     bool raster_cleans = false;     // the rasteriser zeroes the scratch region and reports the Control block (FrameCleanup)
     RasterInst raster{};            // the instantiation launch_raster_scan launches
@@ -260,6 +265,20 @@ struct Lane {
     // ... and, for bgs_debug_frame_leftovers, whether that frame was a graph replay and whether its rasteriser's grid had
     // the strip workgroups behind it
     bool last_replay = false, last_strips = false;
+    // What the lane's last enqueued frame — or a diag hook that launches persistent kernels of its own, on lane 0 —
+    // launched, for bgs_debug_frame_grids: per persistent kernel the workgroups, the items of one tile (0: not launched) and
+    // which count its tiles are made of when the report is read. The report is the lane's with the newest stamp.
+    struct Grids {
+        enum Kernel { FRONT, DEPTH, PROJECT, BIN, TILE_SORT, KERNELS };
+        enum Count : uint8_t { HOST_N, DRAW_COUNT, INSTANCE_COUNT };   // n below, or the completed frame's Control copy
+        uint32_t blocks[KERNELS] = {}, per_tile[KERNELS] = {};
+        Count count[KERNELS] = {HOST_N, DRAW_COUNT, DRAW_COUNT, DRAW_COUNT, INSTANCE_COUNT};
+        uint32_t n = 0;           // the items the host knows: the cloud's splats, a hook's pairs
+        uint32_t cap = 0;         // the grid cap the kernels were launched under
+        bool front_chainless = false;
+        bool tail = false;        // the front kernel wrote the culled / skipped entries to the lane's `culled`, n - draw_count of them
+        uint64_t stamp = 0;       // bgs_ctx::grid_stamps when it was written (0: never)
+    } grids;
 
     bgs_stats result{};      // counters of the last completed frame of this lane (no timings)
     bool has_result = false;
@@ -287,6 +306,8 @@ struct bgs_ctx {
 
     uint32_t binning = BINNING_SCAN;
     uint32_t debug_flags = 0;
+    uint32_t grid_cap = 0;          // bgs_set_grid_cap: 0 off, else the most workgroups of any persistent launch
+    uint64_t grid_stamps = 0;       // Lane::Grids written so far
     int profiling = 2;              // 0 = no events, 1 = frame start/end only, 2 = every stage
     uint32_t profiling_stride = 1;  // record events only on every Nth frame
     uint32_t frame_counter = 0;

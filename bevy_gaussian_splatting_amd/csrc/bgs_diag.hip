@@ -27,11 +27,23 @@ int bgs_radix_sort_pairs(bgs_ctx* ctx, bgs_sort_entry* entries, uint32_t n, uint
     HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)&ctl->splat_count, (int)n, 1, st));
     launch_histogram(st, L.entries[0].ptr, n, &ctl->hist_depth[0][0], passes);
     const bool large = n > (4u << 20);
+    // the frames' default grid, under the context's grid cap (bgs_set_grid_cap); what was launched: bgs_debug_frame_grids
+    const int max_blocks = grid_under_cap(ctx->num_cus * 4, ctx->grid_cap);
+    {
+        Lane::Grids g;
+        g.stamp = ++ctx->grid_stamps;
+        g.n = n;
+        g.cap = ctx->grid_cap;
+        g.per_tile[g.DEPTH] = sort_tile_size(large);
+        g.count[g.DEPTH] = g.HOST_N;
+        g.blocks[g.DEPTH] = capped_grid(n, g.per_tile[g.DEPTH], max_blocks);
+        L.grids = g;
+    }
     int cur = 0;
     for (uint32_t p = 0; p < passes; ++p) {
         launch_onesweep_pass(st, L.entries[cur].ptr, L.entries[cur ^ 1].ptr, &ctl->splat_count, n, ctl->hist_depth[p],
                              depth_status + (size_t)p * L.layout.pass_stride, &ctl->ticket[p][0], &ctl->error,
-                             p * RADIX_BITS, 0u, large, ctx->num_cus * 4);
+                             p * RADIX_BITS, 0u, large, max_blocks);
         cur ^= 1;
     }
     HIP_TRY(ctx, hipGetLastError());
@@ -561,7 +573,17 @@ int bgs_selftest_keygen_buckets(bgs_ctx* ctx, const bgs_cloud* cloud, const bgs_
     kg.split.sub = sub;
     kg.split.wide = wide_buckets;
     kg.wide = alone != 0u;
-    if (!kg.prepare(ctx->num_cus * 4)) return fail(ctx, BGS_EINTERNAL, "keygen self-test: nothing to launch");
+    if (!kg.prepare(grid_under_cap(ctx->num_cus * 4, ctx->grid_cap))) return fail(ctx, BGS_EINTERNAL, "keygen self-test: nothing to launch");
+    {   // (the culled list is the call's own: no tail to read back from the lane)
+        Lane::Grids g;
+        g.stamp = ++ctx->grid_stamps;
+        g.n = n;
+        g.cap = ctx->grid_cap;
+        g.per_tile[g.FRONT] = keygen_tile_splats(n);
+        g.blocks[g.FRONT] = kg.blocks;
+        g.front_chainless = !ordered;
+        ctx->lanes[0].grids = g;
+    }
     bool ok = hipMemsetAsync(ctl, 0, sizeof(Control), st) == hipSuccess &&
               hipMemsetAsync(status_buf.ptr, 0, status_words * sizeof(uint32_t), st) == hipSuccess &&
               hipMemsetAsync(slots_buf.ptr, 0xFF, (size_t)slot_words * sizeof(uint32_t), st) == hipSuccess &&

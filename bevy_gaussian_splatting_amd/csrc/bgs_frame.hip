@@ -590,6 +590,13 @@ FramePlan plan_frame(const bgs_ctx& ctx, const Lane& L, const FrameInputs& in) {
         p.bin_blocks = (int)std::min<uint64_t>((uint64_t)p.bin_blocks, std::max<uint64_t>((uint64_t)state.draw_hint / 256 + 8, 32));
         p.binning_blocks = (int)std::min<uint64_t>((uint64_t)p.binning_blocks, std::max<uint64_t>((uint64_t)state.draw_hint / 1024 + 4, 16));
     }
+    p.front_blocks = ctx.num_cus * 4;
+    p.emit_blocks = ctx.num_cus * 3;
+    p.tile_sort_blocks = ctx.num_cus * 4;
+    // bgs_set_grid_cap (test hook): every persistent launch with at most that many workgroups, so that they come back for
+    // further tiles. The grids are in GraphKey: a frame under another cap is captured anew.
+    for (int* blocks : {&p.sort_blocks, &p.bin_blocks, &p.binning_blocks, &p.front_blocks, &p.emit_blocks, &p.tile_sort_blocks})
+        *blocks = grid_under_cap(*blocks, in.grid_cap);
     p.want_srgb8 = in.render && (in.output_srgb8 || in.output_rgba16f || in.srgb8_target);
     p.out_format = !p.want_srgb8 ? 0u : ((in.output_rgba16f ? OUT_RGBA16F : OUT_SRGB8) |
                                          ((in.packed_only && p.scan) ? OUT_SKIP_F32 : 0u));
@@ -788,7 +795,7 @@ int enqueue_frame(bgs_ctx* ctx, Lane& L, const FrameInputs& in) {
         kg.split.wide = p.wide ? 1u : 0u;
     }
     kg.wide = p.wide_bin;
-    const bool have_keygen = !p.kept && kg.prepare(ctx->num_cus * 4);
+    const bool have_keygen = !p.kept && kg.prepare(p.front_blocks);
     // a kept order: the compaction in keygen's place, leaving what keygen leaves (entries_kernels.hip)
     EntriesLaunch ek;   // (filled for a kept order only: a sorting frame's enqueue does not touch it)
     bool have_compact = false;
@@ -802,7 +809,7 @@ int enqueue_frame(bgs_ctx* ctx, Lane& L, const FrameInputs& in) {
         ek.ticket_slot = kg.ticket_slot;
         ek.fp_out = L.d_fp.ptr;
         ek.zero_word = kg.zero_word;
-        have_compact = ek.prepare();
+        have_compact = ek.prepare(in.grid_cap);
     }
     FrameCleanup cl{};
     if (p.raster_cleans) {
@@ -883,12 +890,12 @@ int enqueue_frame(bgs_ctx* ctx, Lane& L, const FrameInputs& in) {
         } else if (render) {
             const uint32_t capacity = (uint32_t)std::min<uint64_t>(L.inst[0].capacity, MAX_INSTANCE_CAPACITY);
             launch_project_emit(st, fp, in.cloud->ptrs, draw_list, L.culled.ptr, ctl, scan_status, L.records.ptr, L.inst[0].ptr, capacity,
-                                /*ticket_slot=*/4, ctx->num_cus * 3);
+                                /*ticket_slot=*/4, p.emit_blocks);
             mark(3);
             for (uint32_t q = 0; q < 2; ++q)
                 launch_onesweep_pass(st, L.inst[q].ptr, L.inst[q ^ 1].ptr, &ctl->instance_count, capacity, ctl->hist_tile[q],
                                      tile_status + (size_t)q * lay.inst_tiles * RADIX_BASE, &ctl->ticket[5 + q][0],
-                                     &ctl->error, q * RADIX_BITS, 0u, true, ctx->num_cus * 4);
+                                     &ctl->error, q * RADIX_BITS, 0u, true, p.tile_sort_blocks);
             mark(4);
             launch_tile_ranges(st, L.inst[0].ptr, ctl, ranges);
             mark(5);
@@ -930,6 +937,37 @@ int enqueue_frame(bgs_ctx* ctx, Lane& L, const FrameInputs& in) {
     L.last_ctl = render ? ctl : nullptr;
     L.last_replay = ctx->graph_replays != replays_before;
     L.last_strips = render && scan && p.raster.mode != 0 && heavy_in != nullptr;   // (launch_raster_scan's grid)
+    {   // the persistent kernels' grids, as the launchers above made them (capped_grid, kernels.h)
+        Lane::Grids g;
+        g.stamp = ++ctx->grid_stamps;
+        g.tail = p.culled_tail && (have_keygen || have_compact);
+        g.n = n;
+        g.cap = in.grid_cap;
+        if (have_keygen) {
+            g.blocks[g.FRONT] = kg.blocks;
+            g.per_tile[g.FRONT] = keygen_tile_splats(n);
+            g.front_chainless = bucket && !p.culled_tail;
+        } else if (have_compact) {
+            g.blocks[g.FRONT] = ek.blocks;
+            g.per_tile[g.FRONT] = ENTRIES_TILE;
+        }
+        if (!bucket && places > 0 && n > 0) {
+            g.per_tile[g.DEPTH] = sort_tile_size(p.large);
+            g.blocks[g.DEPTH] = capped_grid(n, g.per_tile[g.DEPTH], p.sort_blocks);
+        }
+        if (render && n > 0) {
+            g.per_tile[g.PROJECT] = 256u;
+            g.blocks[g.PROJECT] = capped_grid(n, 256u, scan ? p.bin_blocks : p.emit_blocks);
+            if (scan) {
+                g.per_tile[g.BIN] = 1024u;
+                g.blocks[g.BIN] = capped_grid(n, 1024u, p.binning_blocks);
+            } else {
+                g.per_tile[g.TILE_SORT] = sort_tile_size(true);
+                g.blocks[g.TILE_SORT] = capped_grid(std::min<uint64_t>(L.inst[0].capacity, MAX_INSTANCE_CAPACITY), g.per_tile[g.TILE_SORT], p.tile_sort_blocks);
+            }
+        }
+        L.grids = g;
+    }
     L.fb_valid = !(p.out_format & OUT_SKIP_F32) || (flags & BGS_DEBUG_SEPARATE_ENCODE);
     L.fb8_is_f16 = (p.out_format & OUT_RGBA16F) != 0u;
     L.fb8_valid = p.want_srgb8;
@@ -954,7 +992,7 @@ int run(bgs_ctx* ctx, const bgs_cloud* cloud, const bgs_view* view, const bgs_se
     if (async && L.pending && (rc = finish_lane(ctx, L)) != BGS_OK) return rc;
     const FrameInputs in{cloud, *view, *s, render, /*allow_graph=*/async, render ? ctx->next_srgb8_target : nullptr,
                          ctx->output_srgb8, ctx->output_rgba16f, ctx->packed_only, ctx->debug_flags,
-                         render ? frame_kind(cloud->ptrs.n, cloud->ptrs.format, view, s) : 0ull, /*force_passes=*/false};
+                         render ? frame_kind(cloud->ptrs.n, cloud->ptrs.format, view, s) : 0ull, /*force_passes=*/false, ctx->grid_cap};
     if (!async) {
         ctx->recent = 0;
         ctx->regrow_count = 0;

@@ -136,10 +136,11 @@ __global__ __launch_bounds__(ENTRIES_THREADS) void entries_compact_kernel(FrameP
     }
 }
 
-bool EntriesLaunch::prepare() {
+bool EntriesLaunch::prepare(uint32_t max_blocks) {
     if (fp.n == 0) return false;
     func = tail ? reinterpret_cast<const void*>(&entries_compact_kernel<true>) : reinterpret_cast<const void*>(&entries_compact_kernel<false>);
     blocks = entries_blocks(fp.n);
+    if (max_blocks && blocks > max_blocks) blocks = max_blocks;
     threads = ENTRIES_THREADS;
     argv[0] = &fp; argv[1] = &entries; argv[2] = &draw_list; argv[3] = &tail; argv[4] = &ctl;
     argv[5] = &part_status; argv[6] = &ticket_slot; argv[7] = &fp_out; argv[8] = &zero_word;

@@ -66,6 +66,16 @@ struct FrameCleanup {
 
 // (the onesweep tile geometry, SORT_THREADS .. sort_tile_size, and KEYGEN_TILE: bgs_device.h)
 
+// The grid of a persistent launch: one workgroup per tile of `per_block` items, at most max_blocks of them — the rest of
+// the tiles are taken by ticket (or stride) by workgroups that come back. The launchers below and the grid report
+// (bgs_debug_frame_grids) share this one formula; grid_under_cap is where a grid cap (bgs_set_grid_cap, 0 = none) meets a
+// launch's own most workgroups (plan_frame and the two diag hooks that launch with the frames' default grid).
+inline int grid_under_cap(int max_blocks, uint32_t cap) { return cap && (int)cap < max_blocks ? (int)cap : max_blocks; }
+inline uint32_t capped_grid(uint64_t items, uint32_t per_block, int max_blocks) {
+    const uint64_t tiles = (items + per_block - 1u) / per_block, most = (uint64_t)(max_blocks > 0 ? max_blocks : 1);
+    return (uint32_t)(tiles < most ? tiles : most);
+}
+
 // keygen + fused global digit histograms (radix_sort_a, src/sort/radix.wgsl:71-107) + stable
 // partition: drawable entries -> `entries` (index order), culled-sentinel entries -> `culled`
 // (index order); ctl->draw_count = number of drawable entries. part_status: zeroed chain words,
@@ -132,7 +142,7 @@ struct EntriesLaunch {
     const void* func;
     uint32_t blocks, threads;
     void* argv[9];
-    bool prepare();  // false: nothing to launch (n == 0)
+    bool prepare(uint32_t max_blocks = 0u);  // false: nothing to launch (n == 0); max_blocks: a grid cap (bgs_set_grid_cap), 0 = none
     hipError_t launch(hipStream_t stream);
     hipError_t update_node(hipGraphExec_t exec, hipGraphNode_t node);  // same launch, as a graph node update
 };

@@ -351,8 +351,7 @@ void launch_project_emit(hipStream_t stream, const FrameParams& fp, const CloudP
                          void* records, uint2* instances, uint32_t capacity, uint32_t ticket_slot,
                          int max_blocks) {
     if (fp.n == 0) return;
-    uint32_t blocks = (fp.n + 255u) / 256u;
-    if (blocks > (uint32_t)max_blocks) blocks = (uint32_t)max_blocks;
+    const uint32_t blocks = capped_grid(fp.n, 256u, max_blocks);
     const bool surfel = fp.gaussian_mode == 0u && fp.aabb != 0u;
     float4* rec = (float4*)records;
     const bool any_mode = fp.rasterize_mode != RASTERIZE_COLOR || fp.draw_mode != 0u;
@@ -572,8 +571,7 @@ void launch_project_bin(hipStream_t stream, const FrameParams& fp, const FramePa
                         void* records, uint32_t* rects, uint32_t* coarse, uint32_t coarse_cap, uint32_t sup_edge,
                         uint32_t ticket_slot, int project_blocks, int bin_blocks, bool wide_bin) {
     if (fp.n == 0) return;
-    uint32_t blocks = (fp.n + 255u) / 256u;
-    if (blocks > (uint32_t)project_blocks) blocks = (uint32_t)project_blocks;
+    const uint32_t blocks = capped_grid(fp.n, 256u, project_blocks);
     const uint32_t sup = sup_edge, sup_mul = supertile_mul(sup_edge);
     const uint32_t sup_x = ((uint32_t)fp.tiles_x + sup - 1u) / sup, sup_y = ((uint32_t)fp.tiles_y + sup - 1u) / sup;
     const bool surfel = fp.gaussian_mode == 0u && fp.aabb != 0u;
@@ -593,8 +591,7 @@ void launch_project_bin(hipStream_t stream, const FrameParams& fp, const FramePa
     }
 #undef BGS_LAUNCH_PB2
 #undef BGS_LAUNCH_PB
-    uint32_t bblocks = (fp.n + BIN_RANKS - 1u) / BIN_RANKS;
-    if (bblocks > (uint32_t)bin_blocks) bblocks = (uint32_t)bin_blocks;
+    const uint32_t bblocks = capped_grid(fp.n, BIN_RANKS, bin_blocks);
     launch_bin(stream, rects, ctl, bin_status, coarse, coarse_cap, sup_mul, sup_x, sup_y, ticket_slot, bblocks, wide_bin);
 }
 

@@ -727,9 +727,7 @@ void launch_onesweep_pass(hipStream_t stream, const uint2* in, uint2* out, const
                           uint32_t* error_flag, uint32_t shift, uint32_t key_xor, bool large_tiles,
                           int max_blocks) {
     if (max_n == 0) return;
-    const uint32_t tile = sort_tile_size(large_tiles);
-    uint32_t blocks = (max_n + tile - 1u) / tile;
-    if (blocks > (uint32_t)max_blocks) blocks = (uint32_t)max_blocks;
+    const uint32_t blocks = capped_grid(max_n, sort_tile_size(large_tiles), max_blocks);
     if (large_tiles)
         hipLaunchKernelGGL(onesweep_kernel<SORT_KPT_LARGE>, dim3(blocks), dim3(256), 0, stream, in, out,
                            n_ptr, hist, status, ticket, error_flag, shift, key_xor);

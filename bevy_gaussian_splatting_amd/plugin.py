@@ -959,6 +959,22 @@ class GaussianSplattingPlugin:
         """Kernel-ablation switches for experiments only (non-zero => wrong images)."""
         self._check(self._lib.bgs_set_debug_flags(self._ctx, int(flags)))
 
+    def set_grid_cap(self, blocks: int) -> None:
+        """`bgs_set_grid_cap`: every persistent launch of the context with at most `blocks` workgroups (1 .. 4096), so that
+        a small frame walks the kernels' tile loops several times; 0 (default) = the grids as they are. Test hook."""
+        self._check(self._lib.bgs_set_grid_cap(self._ctx, int(blocks)))
+
+    def debug_frame_grids(self) -> dict:
+        """`bgs_debug_frame_grids`: per persistent kernel of the last completed frame (or of a `radix_sort_pairs` since)
+        `(workgroups launched, tiles of work)` under "front", "depth", "project", "bin", "tile_sort" — `(0, 0)` for a kernel
+        the frame did not launch —, the `cap` the launches ran under, `front_chainless` (the keygen that is never capped), and
+        `tail_ptr` / `tail_count`: the device list of culled / skipped entries the front kernel left (0, 0: none)."""
+        out = np.zeros(_native.FRAME_GRIDS_WORDS, np.uint32)
+        self._check(self._lib.bgs_debug_frame_grids(self._ctx, _uptr(out), out.size))
+        grids = {name: (int(out[2 * k]), int(out[2 * k + 1])) for k, name in enumerate(_native.GRID_KERNELS)}
+        grids.update(cap=int(out[10]), front_chainless=bool(out[11]), tail_ptr=int(out[12]) | (int(out[13]) << 32), tail_count=int(out[14]))
+        return grids
+
     def draw_list(self) -> np.ndarray:
         """The sorted entries the last call left on the device (`bgs_sorted_entries_device_ptr` + `bgs_download`): after
         `sort` all n entries, after `render` the drawable prefix (what reaches the vertex stage, back to front)."""

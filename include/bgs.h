@@ -43,7 +43,9 @@ extern "C" {
 #endif
 
 #define BGS_VERSION_MAJOR 0
-#define BGS_VERSION_MINOR 8 /* 0.8: the read-back of what a frame leaves for the next (bgs_diag.h: bgs_debug_frame_leftovers); the seam of this
+#define BGS_VERSION_MINOR 9 /* 0.9: the grid cap of the persistent kernels and the read-back of a frame's grids (bgs_diag.h: bgs_set_grid_cap,
+                               bgs_debug_frame_grids); the seam of this header, bgs_view, bgs_settings and bgs_stats as in 0.4.
+                               0.8: the read-back of what a frame leaves for the next (bgs_diag.h: bgs_debug_frame_leftovers); the seam of this
                                header, bgs_view, bgs_settings and bgs_stats as in 0.4.
                                0.7: the tile rasterisers' test hook (bgs_diag.h: bgs_selftest_raster); the seam of this header, bgs_view,
                                bgs_settings and bgs_stats as in 0.4.

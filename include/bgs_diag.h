@@ -70,7 +70,8 @@ int bgs_learning_counters(bgs_ctx* ctx, uint64_t* early_frames, uint64_t* kinds_
 /* Stable LSD radix sort of n (key,index) pairs on the device, `passes` 8-bit digit
  * places starting at bit 0 (the Onesweep kernel used for both the depth and the tile
  * sort). entries_inout is a HOST buffer; used by the parity tests to exercise the sort
- * kernel on arbitrary keys (ties, all-equal, ragged sizes). */
+ * kernel on arbitrary keys (ties, all-equal, ragged sizes). The passes run with the frames' default grid under the
+ * context's grid cap (bgs_set_grid_cap); bgs_debug_frame_grids reports it as BGS_GRID_DEPTH, tiles of n. */
 int bgs_radix_sort_pairs(bgs_ctx* ctx, bgs_sort_entry* entries_inout, uint32_t n,
                          uint32_t passes);
 
@@ -229,7 +230,8 @@ int bgs_selftest_bucket_sort(bgs_ctx* ctx, uint32_t sub, uint32_t wide, uint32_t
  *                  culled sentinel) in index order, then the fill; culled_capacity_words: the words it holds;
  *   info_out       5 words: Control::draw_count, Control::splat_count and Control::error (the look-back watchdog) — the
  *                  words keygen publishes; the chainless instantiation leaves draw_count to bucket_sort_kernel and
- *                  publishes splat_count only —, then the launch's threads per workgroup and its workgroups.
+ *                  publishes splat_count only —, then the launch's threads per workgroup and its workgroups (the frames' default grid under the
+ *                  context's grid cap, bgs_set_grid_cap, with ordered = 1; one workgroup per tile with ordered = 0).
  * BGS_EINVAL, naming the argument: NULL pointers, an empty cloud, sub outside 1 .. 16, a flag that is not 0 / 1, settings
  * bgs_sort would refuse (sort_mode, radix_depth_bits), a table that descends somewhere, a capacity that is too small
  * (nothing is launched then). Completes the frames in flight. Test hook (tests/test_bucket_stage_gpu.py). */
@@ -326,6 +328,53 @@ typedef struct bgs_frame_leftovers_info {
 } bgs_frame_leftovers_info;
 int bgs_debug_frame_leftovers(bgs_ctx* ctx, void* host_scratch, uint64_t scratch_capacity_bytes, void* host_control,
                               uint32_t control_capacity_bytes, bgs_scratch_layout* layout_out, bgs_frame_leftovers_info* info_out);
+
+/* A cap on the grid of every PERSISTENT launch of the context: the kernels whose workgroups take tiles of work by ticket
+ * (or by stride) until none is left. Their default grids (num_cus * 4 or * 3 workgroups, or what the draw-count hint asks
+ * for) cover every tile of a frame of a few thousand splats, so that each workgroup takes exactly one tile and never goes
+ * round its loop a second time; under a cap of a few workgroups the same small frame walks every loop several times
+ * (tests/test_grid_cap_gpu.py). blocks: 0 = off, the default; 1 .. BGS_GRID_CAP_MAX = every persistent launch uses
+ * min(its own grid, blocks) workgroups; anything else is BGS_EINVAL. Capped:
+ *   keygen_kernel        the ordered instantiations (the onesweep path's, and the bucket path's with the culled tail:
+ *                        bgs_sort). The CHAINLESS bucket keygen of rendered frames keeps one workgroup per tile: its tiles
+ *                        depend on nobody, its grid is not capped by design and it has no ticket loop to walk;
+ *   onesweep_kernel      the depth passes and BGS_BINNING_SORT's two tile-id passes;
+ *   project_kernel, bin_kernel (BGS_BINNING_SCAN), project_emit_kernel (BGS_BINNING_SORT);
+ *   the kept-order compaction (entries_compact_kernel);
+ *   the hooks bgs_radix_sort_pairs and bgs_selftest_keygen_buckets, which launch with the frames' default grid.
+ * Not capped: the kernels whose grid IS their data — bucket_sort_kernel (workgroup = bucket), the rasterisers (workgroup =
+ * four tiles), tile_order_kernel, the pack and encode kernels, the small libraries.
+ * Why a capped grid cannot deadlock the chained scans: a tile is handed out by an atomic ticket, in tile order, to a
+ * workgroup that is already running; so when a workgroup waits for the chain word of a predecessor tile, that tile has
+ * been taken before its own, by a workgroup that is running (or has finished) and that waits, in turn, only for tiles
+ * taken earlier still. The tile with the lowest unfinished ticket waits for nobody. With a cap of 1 the one workgroup
+ * walks the tiles in order and every predecessor is complete. (project_kernel strides and has no chain.)
+ * The cap travels with the frame like the debug flags: it is snapshotted when the frame is enqueued, a re-run of the frame
+ * uses the grids it was enqueued with, and since the grids are part of what a captured frame graph is keyed on, a frame
+ * under another cap is captured anew, never replayed with the old grids. Test hook. */
+#define BGS_GRID_CAP_MAX 4096u
+int bgs_set_grid_cap(bgs_ctx* ctx, uint32_t blocks);
+
+/* What the persistent kernels of the most recently enqueued frame (bgs_sort or bgs_render; of a re-run, the re-run) launched,
+ * once the frame is complete — or of a bgs_radix_sort_pairs / bgs_selftest_keygen_buckets since (whichever launched last). out[2 k] = workgroups launched, out[2 k + 1] = tiles of
+ * work, for kernel k (both 0 for a kernel the frame did not launch):
+ *   BGS_GRID_FRONT      keygen_kernel or the kept-order compaction: tiles of bgs_cloud_len splats;
+ *   BGS_GRID_DEPTH      the onesweep depth passes (each pass has this grid): tiles of the frame's draw_count;
+ *   BGS_GRID_PROJECT    project_kernel / project_emit_kernel: 256-rank tiles of draw_count;
+ *   BGS_GRID_BIN        bin_kernel: 1024-rank tiles of draw_count;
+ *   BGS_GRID_TILE_SORT  BGS_BINNING_SORT's tile-id passes: tiles of instance_count.
+ * The tiles are computed on the host from the kernel's tile size and from the count the kernel read: the cloud's length, or
+ * the completed frame's Control copy for the counts only the device knew. out[10] = the grid cap the launches ran under,
+ * out[11] = 1 when the front kernel was the chainless keygen (never capped); out[12], out[13] = the low and high word of the
+ * DEVICE address of the list the front kernel left behind the draw list — keygen's culled entries in index order, the
+ * compaction's skipped entries in list order with their parked index — and out[14] = its entries (bgs_cloud_len - draw_count),
+ * all 0 for a frame that wrote none (a render outside BGS_RASTERIZE_DEPTH, a hook); out[15] = 0. The list is the lane's
+ * and is valid until the context's next call that runs kernels (read it with bgs_download). capacity: the words out holds, at least
+ * BGS_FRAME_GRIDS_WORDS. BGS_EINVAL when nothing has run or frames are in flight. Launches nothing. Test hook: a test of a
+ * loop's second trip asserts blocks < tiles before it compares anything. */
+enum bgs_grid_kernel { BGS_GRID_FRONT = 0, BGS_GRID_DEPTH = 1, BGS_GRID_PROJECT = 2, BGS_GRID_BIN = 3, BGS_GRID_TILE_SORT = 4 };
+#define BGS_FRAME_GRIDS_WORDS 16u
+int bgs_debug_frame_grids(bgs_ctx* ctx, uint32_t* out, uint32_t capacity);
 
 #ifdef __cplusplus
 }

@@ -29,7 +29,8 @@ def test_the_seam_header_carries_no_diagnostics_and_the_diag_header_every_hook()
     counters and experiment switches live in include/bgs_diag.h, which declares exactly the set below (the packed
     outputs' conversion hook bgs_selftest_pack, the vertex stage's read-back bgs_debug_frame_records, the binning stage's
     bgs_selftest_bin / bgs_debug_frame_lists, the bucket sort path's bgs_selftest_bucket_sort / bgs_selftest_keygen_buckets
-    the tile rasterisers' bgs_selftest_raster and the frame's leftovers' bgs_debug_frame_leftovers included)."""
+    the tile rasterisers' bgs_selftest_raster, the frame's leftovers' bgs_debug_frame_leftovers and the persistent kernels'
+    bgs_set_grid_cap / bgs_debug_frame_grids included)."""
     seam, diag = set(_declared(("bgs.h",))), set(_declared(("bgs_diag.h",)))
     assert not seam & diag
     assert {"bgs_create", "bgs_cloud_upload_f32", "bgs_sort", "bgs_render", "bgs_pipeline_pop"} <= seam
@@ -37,7 +38,7 @@ def test_the_seam_header_carries_no_diagnostics_and_the_diag_header_every_hook()
             "bgs_set_queue_holders", "bgs_adaptive_counters", "bgs_graph_counters", "bgs_learning_counters",
             "bgs_tile_order_counters", "bgs_selftest_tile_order", "bgs_selftest_pack", "bgs_debug_frame_records",
             "bgs_selftest_bin", "bgs_debug_frame_lists", "bgs_selftest_bucket_sort", "bgs_selftest_keygen_buckets",
-            "bgs_selftest_raster", "bgs_debug_frame_leftovers"} == diag
+            "bgs_selftest_raster", "bgs_debug_frame_leftovers", "bgs_set_grid_cap", "bgs_debug_frame_grids"} == diag
     # the seam proper, plus the multi-GPU frame gather ("ncclGather ... behind the boundary")
     assert {n for n in seam if n.startswith("bgs_comm_")} == {"bgs_comm_unique_id", "bgs_comm_create", "bgs_comm_gather", "bgs_comm_gather_after",
                                                                "bgs_comm_wait", "bgs_comm_stream", "bgs_comm_destroy"}
@@ -51,7 +52,7 @@ def test_library_is_built_and_exports_every_declared_symbol():
     assert set(names) == set(_native.EXPORTED_SYMBOLS)
     for n in names:
         assert hasattr(lib, n), f"libbgs.so does not export {n}"
-    assert lib.bgs_version() == (0 << 16) | 8 == _native.ABI_VERSION
+    assert lib.bgs_version() == (0 << 16) | 9 == _native.ABI_VERSION
 
 
 def test_the_library_exports_the_c_abi_and_nothing_else():

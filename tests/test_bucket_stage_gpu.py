@@ -62,13 +62,14 @@ def _tables(oracle, n, mode):
     return cloud, view, settings, entries, kk, drawable, d, np.sort(kk[drawable]), np.sort(kk2[dr2])
 
 
-def _check_run(plugin, handle, scene, what, tab, sub, wide, ordered, alone):
+def _check_run(plugin, handle, scene, what, tab, sub, wide, ordered, alone, blocks=None):
+    """`blocks`: the workgroups the launch must have had (default: one per tile; tests/test_grid_cap_gpu.py runs it capped)."""
     cloud, view, settings, entries, kk, drawable, d = scene[:7]
     n = len(kk)
     out = plugin.selftest_keygen_buckets(handle, view, settings, tab, sub, wide, ordered, alone)
     assert out["error"] == 0, f"{what}: Control::error {out['error']}"
     threads, items = C.tile_shape(n, alone)
-    assert (out["threads"], out["blocks"]) == (threads, -(-n // (threads * items))), \
+    assert (out["threads"], out["blocks"]) == (threads, -(-n // (threads * items)) if blocks is None else blocks), \
         f"{what}: the launch ran {out['blocks']} workgroups of {out['threads']} threads, not one per {threads} x {items} tile"
     msgs = C.check_placement(what, out, kk, drawable, tab, C.cap_of(wide))
     assert out["splat_count"] == n, f"{what}: splat_count {out['splat_count']}"

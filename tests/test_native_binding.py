@@ -19,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "bevy_gaussian_splatting_amd")
 SMALL_LIB = os.path.join(PKG, "small_lib")
 # in build order: the binding, the headers it binds, the prefix of their functions and how many they declare
-BINDINGS = {"libbgs": (_native, ("bgs.h", "bgs_diag.h"), "bgs_", 67),
+BINDINGS = {"libbgs": (_native, ("bgs.h", "bgs_diag.h"), "bgs_", 69),
             "libbgs_query": (_native_query, ("bgs_query.h",), "bgsq_", 8),
             "libbgs_sparse": (_native_sparse, ("bgs_sparse.h",), "bgss_", 8),
             "libbgs_slice": (_native_slice, ("bgs_slice.h",), "bgst_", 3),

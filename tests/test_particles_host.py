@@ -66,7 +66,7 @@ def test_the_entry_point_is_declared_bound_and_documented():
     block = doc[doc.index('extern "C" {'):]
     assert f"pub fn {SYMBOL}(" in block[:block.index("\n}")]
     assert hasattr(_native.load(), SYMBOL)
-    assert _native.load().bgs_version() == (0 << 16) | 8   # purely additive: it did not move the version (0.5 .. 0.8 came with test hooks in bgs_diag.h)
+    assert _native.load().bgs_version() == (0 << 16) | 9   # purely additive: it did not move the version (0.5 .. 0.9 came with test hooks in bgs_diag.h)
 
 
 def test_record_layout_is_the_references_64_bytes(tool):
