@@ -278,6 +278,9 @@ struct Lane {
         bool front_chainless = false;
         bool tail = false;        // the front kernel wrote the culled / skipped entries to the lane's `culled`, n - draw_count of them
         uint64_t stamp = 0;       // bgs_ctx::grid_stamps when it was written (0: never)
+        Grids() = default;
+        Grids(uint64_t stamp_, uint32_t n_, uint32_t cap_) : n(n_), cap(cap_), stamp(stamp_) {}   // a report of its own stamp: ++ctx->grid_stamps
+        void launched(Kernel k, uint32_t items_per_tile, uint32_t workgroups) { per_tile[k] = items_per_tile; blocks[k] = workgroups; }
     } grids;
 
     bgs_stats result{};      // counters of the last completed frame of this lane (no timings)
@@ -334,6 +337,8 @@ struct bgs_ctx {
 namespace bgs_host {
 // (bgs_frame.hip)
 int fail(bgs_ctx* ctx, int status, const std::string& msg);   // records the message, returns the status
+int enter(bgs_ctx* ctx);                                       // what an entry point that talks to the device begins with: hipSetDevice
+int enter_drained(bgs_ctx* ctx);                               // ... and finish_all: no frame is in flight behind it
 int assign_streams(bgs_ctx* ctx);
 int lane_create(bgs_ctx* ctx, Lane& L);
 void lane_destroy(Lane& L);

@@ -1,7 +1,39 @@
-// bgs_diag.hip — libbgs: the test hooks and probes of include/bgs_diag.h that launch kernels of their own (the digit
-// passes on caller-supplied pairs, the HBM probe, the device self-tests). Counters and switches stay with the context
+// bgs_diag.hip — libbgs: the test hooks and probes of include/bgs_diag.h that touch the device. Those that launch kernels
+// of their own (the digit passes on caller-supplied pairs, the HBM probe, the device self-tests) issue their commands
+// through one checked stream (command_stream.h); the read-backs of the last frame (bgs_debug_frame_records / _lists /
+// _leftovers / _grids) launch nothing and share one guard, last_frame below. Counters and switches stay with the context
 // (bgs_api.hip / bgs_frame.hip).
 #include "bgs_context.h"
+#include "command_stream.h"
+
+namespace {
+
+int refuse_in_flight(bgs_ctx* ctx, const std::string& hook) {
+    for (const Lane& lane : ctx->lanes)
+        if (lane.pending) return fail(ctx, BGS_EINVAL, hook + ": frames are in flight");
+    return BGS_OK;
+}
+
+// What the read-backs of the last frame refuse in common, under the hook's name, in this order: a pipeline depth other than
+// 1 (LF_DEPTH_1), frames in flight, a lane (lane 0, or with LF_RECENT the one the last frame ran on) that holds no rendered
+// frame — or no scratch region, LF_SCRATCH —, and an async frame: always (LF_NO_ASYNC), or at a depth other than 1
+// (LF_NO_ASYNC_RING). Between the second and the third it sets the device and completes what finish_all completes.
+enum : uint32_t { LF_RECENT = 1u, LF_DEPTH_1 = 2u, LF_NO_ASYNC = 4u, LF_NO_ASYNC_RING = 8u, LF_SCRATCH = 16u };
+int last_frame(bgs_ctx* ctx, const std::string& hook, uint32_t flags, Lane** lane_out) {
+    if ((flags & LF_DEPTH_1) && ctx->depth != 1) return fail(ctx, BGS_EINVAL, hook + ": the pipeline depth must be 1");
+    int rc = refuse_in_flight(ctx, hook);
+    if (rc != BGS_OK || (rc = enter_drained(ctx)) != BGS_OK) return rc;
+    Lane& L = ctx->lanes[(flags & LF_RECENT) ? ctx->recent : 0];
+    if (!L.has_result || !L.plan.render || !L.last_ctl || !L.stream || ((flags & LF_SCRATCH) && !L.scratch.ptr))
+        return fail(ctx, BGS_EINVAL, hook + ": no frame has been rendered (or a bgs_sort / bgs_radix_sort_pairs ran since)");
+    if (L.in.allow_graph && (flags & LF_NO_ASYNC)) return fail(ctx, BGS_EINVAL, hook + ": the last frame was an async frame");
+    if (L.in.allow_graph && (flags & LF_NO_ASYNC_RING) && ctx->depth != 1)
+        return fail(ctx, BGS_EINVAL, hook + ": the last frame was an async frame at a pipeline depth other than 1");
+    *lane_out = &L;
+    return BGS_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -9,8 +41,7 @@ int bgs_radix_sort_pairs(bgs_ctx* ctx, bgs_sort_entry* entries, uint32_t n, uint
     if (!ctx) return fail(nullptr, BGS_EINVAL, "ctx is NULL");
     if (passes < 1 || passes > 4) return fail(ctx, BGS_EINVAL, "passes must be 1..4");
     if (n > MAX_SPLATS) return fail(ctx, BGS_EINVAL, "too many pairs");
-    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, BGS_EHIP, "hipSetDevice failed");
-    int rc = finish_all(ctx);
+    int rc = enter_drained(ctx);
     if (rc != BGS_OK) return rc;
     if (n == 0) return BGS_OK;
     if (!entries) return fail(ctx, BGS_EINVAL, "entries is NULL");
@@ -29,16 +60,9 @@ int bgs_radix_sort_pairs(bgs_ctx* ctx, bgs_sort_entry* entries, uint32_t n, uint
     const bool large = n > (4u << 20);
     // the frames' default grid, under the context's grid cap (bgs_set_grid_cap); what was launched: bgs_debug_frame_grids
     const int max_blocks = grid_under_cap(ctx->num_cus * 4, ctx->grid_cap);
-    {
-        Lane::Grids g;
-        g.stamp = ++ctx->grid_stamps;
-        g.n = n;
-        g.cap = ctx->grid_cap;
-        g.per_tile[g.DEPTH] = sort_tile_size(large);
-        g.count[g.DEPTH] = g.HOST_N;
-        g.blocks[g.DEPTH] = capped_grid(n, g.per_tile[g.DEPTH], max_blocks);
-        L.grids = g;
-    }
+    Lane::Grids& g = L.grids = Lane::Grids(++ctx->grid_stamps, n, ctx->grid_cap);
+    g.launched(g.DEPTH, sort_tile_size(large), capped_grid(n, sort_tile_size(large), max_blocks));
+    g.count[g.DEPTH] = g.HOST_N;
     int cur = 0;
     for (uint32_t p = 0; p < passes; ++p) {
         launch_onesweep_pass(st, L.entries[cur].ptr, L.entries[cur ^ 1].ptr, &ctl->splat_count, n, ctl->hist_depth[p],
@@ -58,20 +82,20 @@ int bgs_hbm_probe(bgs_ctx* ctx, uint64_t bytes, uint32_t iters, float* copy_gbs,
     if (!ctx) return fail(nullptr, BGS_EINVAL, "ctx is NULL");
     bytes &= ~(uint64_t)15;
     if (bytes < 4096 || iters == 0 || iters > 10000) return fail(ctx, BGS_EINVAL, "bytes >= 4096 and 1 <= iters <= 10000");
-    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, BGS_EHIP, "hipSetDevice failed");
-    int rc = finish_all(ctx);
-    if (rc != BGS_OK) return rc;
+    if (int rc = enter_drained(ctx); rc != BGS_OK) return rc;
     DeviceBuffer<char> probe;
     if (!probe.reserve((size_t)bytes * 3)) return fail(ctx, BGS_ENOMEM, "hipMalloc(probe buffers) failed");
     char* const buf = probe.ptr;
     hipStream_t st = ctx->lanes[0].stream;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     float ms_copy = 0.0f, ms_triad = 0.0f;
-    bool ok = hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
     float4 *a = (float4*)buf, *b = (float4*)(buf + bytes), *c = (float4*)(buf + 2 * bytes);
     const size_t n4 = (size_t)bytes / 16;
     const int blocks = ctx->num_cus * 16;
-    ok = ok && hipMemsetAsync(buf, 0, (size_t)bytes * 3, st) == hipSuccess;
+    CommandStream cs(st);   // the set-up only: the two timed sections are a measurement and issue their commands themselves
+    cs.check(hipEventCreate(&e0));
+    if (cs.ok) cs.check(hipEventCreate(&e1));
+    bool ok = cs.zero(buf, (size_t)bytes * 3);
     if (ok) {  // warm-up, then `iters` back-to-back repetitions between two events
         ok = hipMemcpyAsync(a, b, bytes, hipMemcpyDeviceToDevice, st) == hipSuccess;
         ok = ok && hipEventRecord(e0, st) == hipSuccess;
@@ -98,9 +122,7 @@ int bgs_hbm_probe(bgs_ctx* ctx, uint64_t bytes, uint32_t iters, float* copy_gbs,
 int bgs_selftest_ln_f32(bgs_ctx* ctx, uint32_t first_bits, uint32_t count, float* host_out, uint64_t* checksum_out) {
     if (!ctx) return fail(nullptr, BGS_EINVAL, "ctx is NULL");
     if (count == 0 || (!host_out && !checksum_out)) return fail(ctx, BGS_EINVAL, "count >= 1 and one of host_out / checksum_out");
-    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, BGS_EHIP, "hipSetDevice failed");
-    int rc = finish_all(ctx);
-    if (rc != BGS_OK) return rc;
+    if (int rc = enter_drained(ctx); rc != BGS_OK) return rc;
     DeviceBuffer<unsigned long long> sum_buf;
     DeviceBuffer<float> out_buf;
     if (!sum_buf.reserve(1)) return fail(ctx, BGS_ENOMEM, "hipMalloc(selftest) failed");
@@ -109,15 +131,14 @@ int bgs_selftest_ln_f32(bgs_ctx* ctx, uint32_t first_bits, uint32_t count, float
     float* const d_out = out_buf.ptr;   // (null without host_out)
     hipStream_t st = ctx->lanes[0].stream;
     unsigned long long sum = 0;
-    bool ok = hipMemsetAsync(d_sum, 0, sizeof sum, st) == hipSuccess;
-    if (ok) {
-        launch_selftest_ln(st, first_bits, count, d_out, d_sum, ctx->num_cus * 8);
-        ok = hipGetLastError() == hipSuccess &&
-             hipMemcpyAsync(&sum, d_sum, sizeof sum, hipMemcpyDeviceToHost, st) == hipSuccess;
-    }
-    if (ok && host_out) ok = hipMemcpyAsync(host_out, d_out, (size_t)count * sizeof(float), hipMemcpyDeviceToHost, st) == hipSuccess;
-    ok = ok && hipStreamSynchronize(st) == hipSuccess;
-    if (!ok) { (void)hipGetLastError(); return fail(ctx, BGS_EHIP, "ln self-test failed on the device"); }
+    CommandStream cs(st);
+    cs.zero(d_sum, sizeof sum);
+    if (cs.ok) launch_selftest_ln(st, first_bits, count, d_out, d_sum, ctx->num_cus * 8);
+    cs.launched();
+    cs.down(&sum, d_sum, sizeof sum);
+    if (host_out) cs.down(host_out, d_out, (size_t)count * sizeof(float));
+    cs.sync();
+    if (!cs.ok) return fail(ctx, BGS_EHIP, "ln self-test failed on the device");
     if (checksum_out) *checksum_out = (uint64_t)sum;
     return BGS_OK;
 }
@@ -132,21 +153,20 @@ int bgs_selftest_pack(bgs_ctx* ctx, uint32_t format, const void* device_in_rgba_
     if ((reinterpret_cast<uintptr_t>(device_in_rgba_f32) & 15u) || (reinterpret_cast<uintptr_t>(device_out) & (out_align - 1u)))
         return fail(ctx, BGS_EINVAL, "pack self-test: the input must be 16-byte aligned, the output 4- (sRGB8) or 8-byte "
                                      "(Rgba16Float) aligned");
-    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, BGS_EHIP, "hipSetDevice failed");
-    int rc = finish_all(ctx);
-    if (rc != BGS_OK) return rc;
+    if (int rc = enter_drained(ctx); rc != BGS_OK) return rc;
     // encode_srgb8_kernel takes its destination from FrameParams::srgb8_target: a zeroed one sends it to device_out
     DeviceBuffer<FrameParams> fp_buf;
     if (!fp_buf.reserve(1)) return fail(ctx, BGS_ENOMEM, "hipMalloc(pack self-test) failed");
     FrameParams* const d_fp = fp_buf.ptr;
     hipStream_t st = ctx->lanes[0].stream;
-    bool ok = hipMemsetAsync(d_fp, 0, sizeof(FrameParams), st) == hipSuccess;
-    if (ok) {
+    CommandStream cs(st);
+    cs.zero(d_fp, sizeof(FrameParams));
+    if (cs.ok)
         launch_encode_srgb8(st, static_cast<const float4*>(device_in_rgba_f32), static_cast<uint32_t*>(device_out), pixels,
                             d_fp, format == BGS_PACK_RGBA16F ? OUT_RGBA16F : OUT_SRGB8);
-        ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
-    }
-    if (!ok) { (void)hipGetLastError(); return fail(ctx, BGS_EHIP, "pack self-test failed on the device"); }
+    cs.launched();
+    cs.sync();
+    if (!cs.ok) return fail(ctx, BGS_EHIP, "pack self-test failed on the device");
     return BGS_OK;
 }
 
@@ -154,33 +174,28 @@ int bgs_selftest_tile_order(bgs_ctx* ctx, const uint16_t* host_cost, uint32_t nt
     if (!ctx) return fail(nullptr, BGS_EINVAL, "ctx is NULL");
     if (!host_cost || !host_order || ntiles == 0 || ntiles > 65535u || (runs != 1u && runs != 2u && runs != 4u))
         return fail(ctx, BGS_EINVAL, "tile-order self-test: 1 <= ntiles <= 65535, runs 1 / 2 / 4, both host buffers");
-    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, BGS_EHIP, "hipSetDevice failed");
-    int rc = finish_all(ctx);
-    if (rc != BGS_OK) return rc;
+    if (int rc = enter_drained(ctx); rc != BGS_OK) return rc;
     const uint32_t nblocks = (ntiles + 3u) / 4u;
     DeviceBuffer<uint16_t> cost_buf, order_buf;
     cost_buf.reserve(tile_cost_bytes(ntiles) / 2u);
     order_buf.reserve(tile_order_bytes(ntiles) / 2u);
     uint16_t* const d_cost = cost_buf.ptr;
     uint16_t* const d_order = order_buf.ptr;
-    hipStream_t st = ctx->lanes[0].stream;
     uint32_t pairs[16];
-    bool ok = d_cost && d_order &&
-              hipMemsetAsync(d_order, 0xFF, tile_order_bytes(ntiles), st) == hipSuccess &&
-              hipMemcpyAsync(d_cost, host_cost, (size_t)ntiles * 2u, hipMemcpyHostToDevice, st) == hipSuccess;
-    if (ok) {
-        launch_tile_order_runs(st, d_cost, d_order, ntiles, runs);
-        ok = hipGetLastError() == hipSuccess &&
-             hipMemcpyAsync(host_order, d_order, (size_t)nblocks * 2u, hipMemcpyDeviceToHost, st) == hipSuccess &&
-             hipMemcpyAsync(pairs, reinterpret_cast<const uint8_t*>(d_order) + tile_order_stats_offset(ntiles), sizeof pairs,
-                            hipMemcpyDeviceToHost, st) == hipSuccess &&
-             hipStreamSynchronize(st) == hipSuccess;
-    }
-    if (ok && host_sums) {
+    CommandStream cs(ctx->lanes[0].stream);
+    cs.ok = d_cost && d_order;   // (no memory: the hook's one refusal)
+    cs.fill(d_order, 0xFF, tile_order_bytes(ntiles));
+    cs.up(d_cost, host_cost, (size_t)ntiles * 2u);
+    if (cs.ok) launch_tile_order_runs(cs.st, d_cost, d_order, ntiles, runs);
+    cs.launched();
+    cs.down(host_order, d_order, (size_t)nblocks * 2u);
+    cs.down(pairs, reinterpret_cast<const uint8_t*>(d_order) + tile_order_stats_offset(ntiles), sizeof pairs);
+    cs.sync();
+    if (!cs.ok) return fail(ctx, BGS_EHIP, "tile-order self-test failed on the device");
+    if (host_sums) {
         host_sums[0] = host_sums[1] = 0u;
         for (uint32_t x = 0; x < 8u; ++x) { host_sums[0] += pairs[2u * x]; host_sums[1] += pairs[2u * x + 1u]; }
     }
-    if (!ok) { (void)hipGetLastError(); return fail(ctx, BGS_EHIP, "tile-order self-test failed on the device"); }
     return BGS_OK;
 }
 
@@ -210,9 +225,7 @@ int bgs_selftest_bin(bgs_ctx* ctx, const uint32_t* host_rects, uint32_t n, uint3
     if (lists_capacity_words < list_words)
         return fail(ctx, BGS_EINVAL, "bin self-test: host_lists holds " + std::to_string(lists_capacity_words) + " words, the lists and their guard are " +
                                          std::to_string(list_words));
-    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, BGS_EHIP, "hipSetDevice failed");
-    int rc = finish_all(ctx);
-    if (rc != BGS_OK) return rc;
+    if (int rc = enter_drained(ctx); rc != BGS_OK) return rc;
     const size_t status_words = ((size_t)(n + 255u) / 256u + 1u) * MAX_SUPERTILES;   // (as scratch_layout sizes the frames')
     DeviceBuffer<uint32_t> rects_buf, status_buf, lists_buf;
     DeviceBuffer<Control> ctl_buf;
@@ -220,21 +233,21 @@ int bgs_selftest_bin(bgs_ctx* ctx, const uint32_t* host_rects, uint32_t n, uint3
         return fail(ctx, BGS_ENOMEM, "hipMalloc(bin self-test) failed");
     Control* const ctl = ctl_buf.ptr;
     hipStream_t st = ctx->lanes[0].stream;
-    bool ok = hipMemsetAsync(ctl, 0, sizeof(Control), st) == hipSuccess &&
-              hipMemsetAsync(status_buf.ptr, 0, status_words * sizeof(uint32_t), st) == hipSuccess &&
-              hipMemsetAsync(lists_buf.ptr, 0xFF, (size_t)list_words * sizeof(uint32_t), st) == hipSuccess &&
-              hipMemcpyAsync(rects_buf.ptr, host_rects, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, st) == hipSuccess &&
-              hipMemsetD32Async((hipDeviceptr_t)&ctl->draw_count, (int)n, 1, st) == hipSuccess;
-    if (ok) {
+    CommandStream cs(st);
+    cs.zero(ctl, sizeof(Control));
+    cs.zero(status_buf.ptr, status_words * sizeof(uint32_t));
+    cs.fill(lists_buf.ptr, 0xFF, (size_t)list_words * sizeof(uint32_t));
+    cs.up(rects_buf.ptr, host_rects, (size_t)n * sizeof(uint32_t));
+    cs.word(&ctl->draw_count, n);
+    if (cs.ok)
         launch_bin(st, rects_buf.ptr, ctl, status_buf.ptr, lists_buf.ptr, coarse_cap, supertile_mul(sup_edge), sup_x, sup_y,
                    /*ticket_slot=*/4, blocks, wide != 0u);
-        ok = hipGetLastError() == hipSuccess &&
-             hipMemcpyAsync(host_lists, lists_buf.ptr, (size_t)list_words * sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
-             hipMemcpyAsync(host_totals, ctl->coarse_total, sizeof ctl->coarse_total, hipMemcpyDeviceToHost, st) == hipSuccess &&
-             hipMemcpyAsync(error_out, &ctl->error, sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
-             hipStreamSynchronize(st) == hipSuccess;
-    }
-    if (!ok) { (void)hipGetLastError(); return fail(ctx, BGS_EHIP, "bin self-test failed on the device"); }
+    cs.launched();
+    cs.down(host_lists, lists_buf.ptr, (size_t)list_words * sizeof(uint32_t));
+    cs.down(host_totals, ctl->coarse_total, sizeof ctl->coarse_total);
+    cs.down(error_out, &ctl->error, sizeof(uint32_t));
+    cs.sync();
+    if (!cs.ok) return fail(ctx, BGS_EHIP, "bin self-test failed on the device");
     return BGS_OK;
 }
 
@@ -254,16 +267,9 @@ int bgs_debug_frame_records(bgs_ctx* ctx, void* host_records, uint64_t records_c
                             uint32_t rects_capacity_words, bgs_frame_records_info* info_out) {
     if (!ctx) return fail(nullptr, BGS_EINVAL, "ctx is NULL");
     if (!info_out) return fail(ctx, BGS_EINVAL, "frame records: info_out is NULL");
-    if (ctx->depth != 1) return fail(ctx, BGS_EINVAL, "frame records: the pipeline depth must be 1");
-    for (const Lane& lane : ctx->lanes)
-        if (lane.pending) return fail(ctx, BGS_EINVAL, "frame records: frames are in flight");
-    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, BGS_EHIP, "hipSetDevice failed");
-    int rc = finish_all(ctx);
-    if (rc != BGS_OK) return rc;
-    Lane& L = ctx->lanes[0];
-    if (!L.has_result || !L.plan.render || !L.last_ctl || !L.stream)
-        return fail(ctx, BGS_EINVAL, "frame records: no frame has been rendered (or a bgs_sort / bgs_radix_sort_pairs ran since)");
-    if (L.in.allow_graph) return fail(ctx, BGS_EINVAL, "frame records: the last frame was an async frame");
+    Lane* lane = nullptr;
+    if (int rc = last_frame(ctx, "frame records", LF_DEPTH_1 | LF_NO_ASYNC, &lane); rc != BGS_OK) return rc;
+    Lane& L = *lane;
     hipStream_t st = L.stream;
     uint32_t head[CONTROL_HEADER_WORDS] = {};
     uint32_t cmax = 0u;
@@ -315,15 +321,9 @@ int bgs_debug_frame_lists(bgs_ctx* ctx, uint32_t* host_totals, uint32_t totals_c
                           bgs_frame_lists_info* info_out) {
     if (!ctx) return fail(nullptr, BGS_EINVAL, "ctx is NULL");
     if (!info_out) return fail(ctx, BGS_EINVAL, "frame lists: info_out is NULL");
-    for (const Lane& lane : ctx->lanes)
-        if (lane.pending) return fail(ctx, BGS_EINVAL, "frame lists: frames are in flight");
-    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, BGS_EHIP, "hipSetDevice failed");
-    int rc = finish_all(ctx);
-    if (rc != BGS_OK) return rc;
-    Lane& L = ctx->lanes[ctx->recent];
-    if (!L.has_result || !L.plan.render || !L.last_ctl || !L.stream)
-        return fail(ctx, BGS_EINVAL, "frame lists: no frame has been rendered (or a bgs_sort / bgs_radix_sort_pairs ran since)");
-    if (L.in.allow_graph) return fail(ctx, BGS_EINVAL, "frame lists: the last frame was an async frame");
+    Lane* lane = nullptr;
+    if (int rc = last_frame(ctx, "frame lists", LF_RECENT | LF_NO_ASYNC, &lane); rc != BGS_OK) return rc;
+    Lane& L = *lane;
     const FramePlan& p = L.plan;
     const Control& h = *L.h_ctl.ptr;
     hipStream_t st = L.stream;
@@ -396,16 +396,9 @@ int bgs_debug_frame_leftovers(bgs_ctx* ctx, void* host_scratch, uint64_t scratch
                   "bgs_scratch_layout is ScratchLayout, field by field");
     if (!ctx) return fail(nullptr, BGS_EINVAL, "ctx is NULL");
     if (!info_out || !layout_out) return fail(ctx, BGS_EINVAL, "frame leftovers: layout_out and info_out must be non-NULL");
-    for (const Lane& lane : ctx->lanes)
-        if (lane.pending) return fail(ctx, BGS_EINVAL, "frame leftovers: frames are in flight");
-    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, BGS_EHIP, "hipSetDevice failed");
-    int rc = finish_all(ctx);
-    if (rc != BGS_OK) return rc;
-    Lane& L = ctx->lanes[0];
-    if (!L.has_result || !L.plan.render || !L.last_ctl || !L.stream || !L.scratch.ptr)
-        return fail(ctx, BGS_EINVAL, "frame leftovers: no frame has been rendered (or a bgs_sort / bgs_radix_sort_pairs ran since)");
-    if (L.in.allow_graph && ctx->depth != 1)
-        return fail(ctx, BGS_EINVAL, "frame leftovers: the last frame was an async frame at a pipeline depth other than 1");
+    Lane* lane = nullptr;
+    if (int rc = last_frame(ctx, "frame leftovers", LF_NO_ASYNC_RING | LF_SCRATCH, &lane); rc != BGS_OK) return rc;
+    Lane& L = *lane;
     const FramePlan& p = L.plan;
     const ScratchLayout& lay = L.layout;
     const uint8_t* const own = reinterpret_cast<const uint8_t*>(L.last_ctl);
@@ -460,6 +453,39 @@ int bgs_debug_frame_leftovers(bgs_ctx* ctx, void* host_scratch, uint64_t scratch
     return BGS_OK;
 }
 
+// What the last frame's persistent kernels launched (Lane::Grids, filled by enqueue_frame with the launchers' own formula) and
+// the tiles of work they had: of n for the front kernel, of the completed frame's Control copy for the kernels whose count
+// only the device knew (draw_count, voided by sort_overflow as the kernels read it; instance_count).
+int bgs_debug_frame_grids(bgs_ctx* ctx, uint32_t* out, uint32_t capacity) {
+    if (!ctx) return fail(nullptr, BGS_EINVAL, "ctx is NULL");
+    if (!out) return fail(ctx, BGS_EINVAL, "frame grids: out is NULL");
+    if (capacity < BGS_FRAME_GRIDS_WORDS)
+        return fail(ctx, BGS_EINVAL, "frame grids: out holds " + std::to_string(capacity) + " words, the report is " + std::to_string(BGS_FRAME_GRIDS_WORDS));
+    if (int rc = refuse_in_flight(ctx, "frame grids"); rc != BGS_OK) return rc;
+    const Lane* newest = &ctx->lanes[0];
+    for (const Lane& lane : ctx->lanes)
+        if (lane.grids.stamp > newest->grids.stamp) newest = &lane;
+    const Lane& L = *newest;
+    const Lane::Grids& g = L.grids;
+    if (!g.stamp || !L.h_ctl.ptr) return fail(ctx, BGS_EINVAL, "frame grids: no frame has been run");
+    const Control& h = *L.h_ctl.ptr;
+    const uint64_t draw = h.sort_overflow ? 0u : h.draw_count;
+    const uint64_t items[3] = {g.n, draw, h.instance_count};   // (Lane::Grids::Count)
+    for (int k = 0; k < Lane::Grids::KERNELS; ++k) {
+        out[2 * k] = g.blocks[k];
+        out[2 * k + 1] = g.per_tile[k] ? (uint32_t)((items[g.count[k]] + g.per_tile[k] - 1u) / g.per_tile[k]) : 0u;
+    }
+    out[10] = g.cap;
+    out[11] = g.front_chainless ? 1u : 0u;
+    // the tail behind the draw list, where the front kernel left it (index order after keygen, list order after the compaction)
+    const uint64_t tail = (g.tail && L.culled.ptr && g.n >= h.draw_count) ? (uint64_t)(uintptr_t)L.culled.ptr : 0u;
+    out[12] = (uint32_t)tail;
+    out[13] = (uint32_t)(tail >> 32);
+    out[14] = tail ? g.n - h.draw_count : 0u;
+    out[15] = 0u;
+    return BGS_OK;
+}
+
 // bucket_sort_kernel alone, on the caller's bucket contents: a zeroed Control with the caller's counts, slot regions that
 // hold each bucket's pairs at their start and 0xFF bytes behind them, an output list of n + BGS_SELFTEST_BUCKET_GUARD entries
 // of 0xFF bytes. What the kernel indexes (sort_kernels.hip): bucket_count[i < nb], a region's first min(count, cap) slots
@@ -483,34 +509,31 @@ int bgs_selftest_bucket_sort(bgs_ctx* ctx, uint32_t sub, uint32_t wide, uint32_t
     if (out_capacity_words < out_words)
         return fail(ctx, BGS_EINVAL, "bucket self-test: host_out holds " + std::to_string(out_capacity_words) + " words, the list and its guard are " +
                                          std::to_string(out_words));
-    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, BGS_EHIP, "hipSetDevice failed");
-    int rc = finish_all(ctx);
-    if (rc != BGS_OK) return rc;
+    if (int rc = enter_drained(ctx); rc != BGS_OK) return rc;
     DeviceBuffer<uint2> slots_buf, out_buf;
     DeviceBuffer<Control> ctl_buf;
     if (!slots_buf.reserve((size_t)nb * cap) || !out_buf.reserve((size_t)(n + BGS_SELFTEST_BUCKET_GUARD)) || !ctl_buf.reserve(1))
         return fail(ctx, BGS_ENOMEM, "hipMalloc(bucket self-test) failed");
     Control* const ctl = ctl_buf.ptr;
     hipStream_t st = ctx->lanes[0].stream;
-    bool ok = hipMemsetAsync(ctl, 0, sizeof(Control), st) == hipSuccess &&
-              hipMemsetAsync(slots_buf.ptr, 0xFF, (size_t)nb * cap * sizeof(uint2), st) == hipSuccess &&
-              hipMemsetAsync(out_buf.ptr, 0xFF, (size_t)out_words * sizeof(uint32_t), st) == hipSuccess &&
-              hipMemcpyAsync(ctl->bucket_count, host_counts, (size_t)nb * sizeof(uint32_t), hipMemcpyHostToDevice, st) == hipSuccess;
+    CommandStream cs(st);
+    cs.zero(ctl, sizeof(Control));
+    cs.fill(slots_buf.ptr, 0xFF, (size_t)nb * cap * sizeof(uint2));
+    cs.fill(out_buf.ptr, 0xFF, (size_t)out_words * sizeof(uint32_t));
+    cs.up(ctl->bucket_count, host_counts, (size_t)nb * sizeof(uint32_t));
     uint64_t at = 0;
-    for (uint32_t b = 0; ok && b < nb; ++b) {
+    for (uint32_t b = 0; b < nb; ++b) {
         const uint32_t len = std::min(host_counts[b], cap);
-        if (len) ok = hipMemcpyAsync(slots_buf.ptr + (size_t)b * cap, host_pairs + at * 2u, (size_t)len * sizeof(uint2), hipMemcpyHostToDevice, st) == hipSuccess;
+        if (len) cs.up(slots_buf.ptr + (size_t)b * cap, host_pairs + at * 2u, (size_t)len * sizeof(uint2));
         at += len;
     }
-    if (ok) {
-        ok = launch_bucket_sort(st, slots_buf.ptr, out_buf.ptr, ctl, key_xor, nb, wide != 0u) == hipSuccess && hipGetLastError() == hipSuccess &&
-             hipMemcpyAsync(host_out, out_buf.ptr, (size_t)out_words * sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
-             hipMemcpyAsync(&info_out[0], &ctl->draw_count, sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
-             hipMemcpyAsync(&info_out[1], &ctl->sort_overflow, sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
-             hipMemcpyAsync(&info_out[2], &ctl->bucket_max, sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
-             hipStreamSynchronize(st) == hipSuccess;
-    }
-    if (!ok) { (void)hipGetLastError(); return fail(ctx, BGS_EHIP, "bucket self-test failed on the device"); }
+    if (cs.ok) cs.launched(launch_bucket_sort(st, slots_buf.ptr, out_buf.ptr, ctl, key_xor, nb, wide != 0u));
+    cs.down(host_out, out_buf.ptr, (size_t)out_words * sizeof(uint32_t));
+    cs.down(&info_out[0], &ctl->draw_count, sizeof(uint32_t));
+    cs.down(&info_out[1], &ctl->sort_overflow, sizeof(uint32_t));
+    cs.down(&info_out[2], &ctl->bucket_max, sizeof(uint32_t));
+    cs.sync();
+    if (!cs.ok) return fail(ctx, BGS_EHIP, "bucket self-test failed on the device");
     return BGS_OK;
 }
 
@@ -546,9 +569,7 @@ int bgs_selftest_keygen_buckets(bgs_ctx* ctx, const bgs_cloud* cloud, const bgs_
                                          std::to_string(slot_words));
     if (ordered && (!host_culled || culled_capacity_words < (uint64_t)n * 2u))
         return fail(ctx, BGS_EINVAL, "keygen self-test: host_culled must hold " + std::to_string((uint64_t)n * 2u) + " words with ordered = 1");
-    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, BGS_EHIP, "hipSetDevice failed");
-    int rc = finish_all(ctx);
-    if (rc != BGS_OK) return rc;
+    if (int rc = enter_drained(ctx); rc != BGS_OK) return rc;
     const size_t status_words = (size_t)(n + KEYGEN_TILE - 1u) / KEYGEN_TILE + 1u;
     DeviceBuffer<uint2> slots_buf, culled_buf;
     DeviceBuffer<uint32_t> status_buf, keys_buf;
@@ -574,33 +595,24 @@ int bgs_selftest_keygen_buckets(bgs_ctx* ctx, const bgs_cloud* cloud, const bgs_
     kg.split.wide = wide_buckets;
     kg.wide = alone != 0u;
     if (!kg.prepare(grid_under_cap(ctx->num_cus * 4, ctx->grid_cap))) return fail(ctx, BGS_EINTERNAL, "keygen self-test: nothing to launch");
-    {   // (the culled list is the call's own: no tail to read back from the lane)
-        Lane::Grids g;
-        g.stamp = ++ctx->grid_stamps;
-        g.n = n;
-        g.cap = ctx->grid_cap;
-        g.per_tile[g.FRONT] = keygen_tile_splats(n);
-        g.blocks[g.FRONT] = kg.blocks;
-        g.front_chainless = !ordered;
-        ctx->lanes[0].grids = g;
-    }
-    bool ok = hipMemsetAsync(ctl, 0, sizeof(Control), st) == hipSuccess &&
-              hipMemsetAsync(status_buf.ptr, 0, status_words * sizeof(uint32_t), st) == hipSuccess &&
-              hipMemsetAsync(slots_buf.ptr, 0xFF, (size_t)slot_words * sizeof(uint32_t), st) == hipSuccess &&
-              (!ordered || hipMemsetAsync(culled_buf.ptr, 0xFF, (size_t)n * sizeof(uint2), st) == hipSuccess) &&
-              (sub <= BUCKET_SUB_KERNARG ||
-               hipMemcpyAsync(keys_buf.ptr, host_splitters, (size_t)nkeys * sizeof(uint32_t), hipMemcpyHostToDevice, st) == hipSuccess);
-    if (ok) {
-        ok = kg.launch(st) == hipSuccess && hipGetLastError() == hipSuccess &&
-             hipMemcpyAsync(host_counts, ctl->bucket_count, (size_t)nb * sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
-             hipMemcpyAsync(host_slots, slots_buf.ptr, (size_t)slot_words * sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
-             (!ordered || hipMemcpyAsync(host_culled, culled_buf.ptr, (size_t)n * sizeof(uint2), hipMemcpyDeviceToHost, st) == hipSuccess) &&
-             hipMemcpyAsync(&info_out[0], &ctl->draw_count, sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
-             hipMemcpyAsync(&info_out[1], &ctl->splat_count, sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
-             hipMemcpyAsync(&info_out[2], &ctl->error, sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
-             hipStreamSynchronize(st) == hipSuccess;
-    }
-    if (!ok) { (void)hipGetLastError(); return fail(ctx, BGS_EHIP, "keygen self-test failed on the device"); }
+    Lane::Grids& g = ctx->lanes[0].grids = Lane::Grids(++ctx->grid_stamps, n, ctx->grid_cap);   // (the culled list is the call's own: no tail)
+    g.launched(g.FRONT, keygen_tile_splats(n), kg.blocks);
+    g.front_chainless = !ordered;
+    CommandStream cs(st);
+    cs.zero(ctl, sizeof(Control));
+    cs.zero(status_buf.ptr, status_words * sizeof(uint32_t));
+    cs.fill(slots_buf.ptr, 0xFF, (size_t)slot_words * sizeof(uint32_t));
+    if (ordered) cs.fill(culled_buf.ptr, 0xFF, (size_t)n * sizeof(uint2));
+    if (sub > BUCKET_SUB_KERNARG) cs.up(keys_buf.ptr, host_splitters, (size_t)nkeys * sizeof(uint32_t));
+    if (cs.ok) cs.launched(kg.launch(st));
+    cs.down(host_counts, ctl->bucket_count, (size_t)nb * sizeof(uint32_t));
+    cs.down(host_slots, slots_buf.ptr, (size_t)slot_words * sizeof(uint32_t));
+    if (ordered) cs.down(host_culled, culled_buf.ptr, (size_t)n * sizeof(uint2));
+    cs.down(&info_out[0], &ctl->draw_count, sizeof(uint32_t));
+    cs.down(&info_out[1], &ctl->splat_count, sizeof(uint32_t));
+    cs.down(&info_out[2], &ctl->error, sizeof(uint32_t));
+    cs.sync();
+    if (!cs.ok) return fail(ctx, BGS_EHIP, "keygen self-test failed on the device");
     info_out[3] = kg.threads;
     info_out[4] = kg.blocks;
     return BGS_OK;
@@ -707,9 +719,7 @@ int bgs_selftest_raster(bgs_ctx* ctx, const bgs_raster_selftest* in, float* host
             if (instances.size() > (1u << 24)) return fail(ctx, BGS_EINVAL, "raster self-test: the lists hold more than 2^24 tile instances");
             ranges[(ty << 8) | tx] = make_uint2(start, (uint32_t)instances.size());
         }
-    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, BGS_EHIP, "hipSetDevice failed");
-    int rc = finish_all(ctx);
-    if (rc != BGS_OK) return rc;
+    if (int rc = enter_drained(ctx); rc != BGS_OK) return rc;
     const size_t stride = in->variant == (uint32_t)RV_SURFEL ? sizeof(RecordSurfel) : sizeof(Record);
     const size_t list_words = (size_t)num_st * cap * 2u, depth_floats = (size_t)pixels * ms;
     DeviceBuffer<uint8_t> rec_buf, heavy_in_buf, heavy_out_buf;
@@ -743,38 +753,39 @@ int bgs_selftest_raster(bgs_ctx* ctx, const bgs_raster_selftest* in, float* host
     memcpy(fp.clear, in->clear, sizeof fp.clear);
     Control* const ctl = ctl_buf.ptr;
     hipStream_t st = ctx->lanes[0].stream;
-    bool ok = hipMemsetAsync(ctl, 0, sizeof(Control), st) == hipSuccess &&
-              hipMemsetAsync(scan_buf.ptr, 0xFF, (size_t)image_floats * sizeof(float), st) == hipSuccess &&
-              hipMemsetAsync(sort_buf.ptr, 0xFF, (size_t)image_floats * sizeof(float), st) == hipSuccess &&
-              hipMemsetAsync(cost_buf.ptr, 0xFF, tile_cost_bytes(ntiles), st) == hipSuccess &&
-              hipMemsetAsync(heavy_out_buf.ptr, 0, heavy_host.size(), st) == hipSuccess &&
-              hipMemcpyAsync(heavy_in_buf.ptr, heavy_host.data(), heavy_host.size(), hipMemcpyHostToDevice, st) == hipSuccess &&
-              hipMemcpyAsync(fp_buf.ptr, &fp, sizeof fp, hipMemcpyHostToDevice, st) == hipSuccess &&
-              hipMemcpyAsync(lists_buf.ptr, in->lists, list_words * sizeof(uint32_t), hipMemcpyHostToDevice, st) == hipSuccess &&
-              hipMemcpyAsync(ranges_buf.ptr, ranges.data(), ranges.size() * sizeof(uint2), hipMemcpyHostToDevice, st) == hipSuccess &&
-              hipMemcpyAsync(ctl->coarse_total, in->totals, (size_t)num_st * sizeof(uint32_t), hipMemcpyHostToDevice, st) == hipSuccess &&
-              hipMemcpyAsync(&ctl->color_max_bits, &in->color_max_bits, sizeof(uint32_t), hipMemcpyHostToDevice, st) == hipSuccess &&
-              hipMemcpyAsync(&ctl->draw_count, &in->record_count, sizeof(uint32_t), hipMemcpyHostToDevice, st) == hipSuccess;
-    if (ok && in->record_count) ok = hipMemcpyAsync(rec_buf.ptr, in->records, (size_t)in->record_count * stride, hipMemcpyHostToDevice, st) == hipSuccess;
-    if (ok && !instances.empty()) ok = hipMemcpyAsync(inst_buf.ptr, instances.data(), instances.size() * sizeof(uint2), hipMemcpyHostToDevice, st) == hipSuccess;
-    if (ok && in->depth) ok = hipMemcpyAsync(depth_buf.ptr, in->depth, depth_floats * sizeof(float), hipMemcpyHostToDevice, st) == hipSuccess;
-    if (ok && in->order) ok = hipMemcpyAsync(order_buf.ptr, in->order, (size_t)nblocks * sizeof(uint16_t), hipMemcpyHostToDevice, st) == hipSuccess;
-    if (ok) {
+    CommandStream cs(st);
+    cs.zero(ctl, sizeof(Control));
+    cs.fill(scan_buf.ptr, 0xFF, (size_t)image_floats * sizeof(float));
+    cs.fill(sort_buf.ptr, 0xFF, (size_t)image_floats * sizeof(float));
+    cs.fill(cost_buf.ptr, 0xFF, tile_cost_bytes(ntiles));
+    cs.zero(heavy_out_buf.ptr, heavy_host.size());
+    cs.up(heavy_in_buf.ptr, heavy_host.data(), heavy_host.size());
+    cs.up(fp_buf.ptr, &fp, sizeof fp);
+    cs.up(lists_buf.ptr, in->lists, list_words * sizeof(uint32_t));
+    cs.up(ranges_buf.ptr, ranges.data(), ranges.size() * sizeof(uint2));
+    cs.up(ctl->coarse_total, in->totals, (size_t)num_st * sizeof(uint32_t));
+    cs.up(&ctl->color_max_bits, &in->color_max_bits, sizeof(uint32_t));
+    cs.up(&ctl->draw_count, &in->record_count, sizeof(uint32_t));
+    if (in->record_count) cs.up(rec_buf.ptr, in->records, (size_t)in->record_count * stride);
+    if (!instances.empty()) cs.up(inst_buf.ptr, instances.data(), instances.size() * sizeof(uint2));
+    if (in->depth) cs.up(depth_buf.ptr, in->depth, depth_floats * sizeof(float));
+    if (in->order) cs.up(order_buf.ptr, in->order, (size_t)nblocks * sizeof(uint16_t));
+    if (cs.ok) {
         const bool exits = in->mode != 0u;
         launch_raster_scan(st, fp, fp_buf.ptr, rec_buf.ptr, lists_buf.ptr, cap, in->sup_edge, ctl, reinterpret_cast<float4*>(scan_buf.ptr),
                            /*srgb8_default=*/nullptr, /*out_format=*/0u, FrameCleanup{}, /*tile_trace=*/nullptr, (int)in->mode,
                            exits && in->heavy_count ? heavy_in_buf.ptr : nullptr, exits ? heavy_out_buf.ptr : nullptr,
                            in->order ? order_buf.ptr : nullptr, cost_buf.ptr);
         launch_raster(st, fp, rec_buf.ptr, inst_buf.ptr, ranges_buf.ptr, reinterpret_cast<float4*>(sort_buf.ptr), in->clear, ctl);
-        ok = hipGetLastError() == hipSuccess &&
-             hipMemcpyAsync(host_scan, scan_buf.ptr, (size_t)image_floats * sizeof(float), hipMemcpyDeviceToHost, st) == hipSuccess &&
-             hipMemcpyAsync(host_sort, sort_buf.ptr, (size_t)image_floats * sizeof(float), hipMemcpyDeviceToHost, st) == hipSuccess &&
-             hipMemcpyAsync(host_cost, cost_buf.ptr, (size_t)ntiles * sizeof(uint16_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
-             hipMemcpyAsync(host_heavy, heavy_out_buf.ptr, heavy_host.size(), hipMemcpyDeviceToHost, st) == hipSuccess &&
-             hipMemcpyAsync(error_out, &ctl->error, sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
-             hipStreamSynchronize(st) == hipSuccess;
     }
-    if (!ok) { (void)hipGetLastError(); return fail(ctx, BGS_EHIP, "raster self-test failed on the device"); }
+    cs.launched();
+    cs.down(host_scan, scan_buf.ptr, (size_t)image_floats * sizeof(float));
+    cs.down(host_sort, sort_buf.ptr, (size_t)image_floats * sizeof(float));
+    cs.down(host_cost, cost_buf.ptr, (size_t)ntiles * sizeof(uint16_t));
+    cs.down(host_heavy, heavy_out_buf.ptr, heavy_host.size());
+    cs.down(error_out, &ctl->error, sizeof(uint32_t));
+    cs.sync();
+    if (!cs.ok) return fail(ctx, BGS_EHIP, "raster self-test failed on the device");
     return BGS_OK;
 }
 

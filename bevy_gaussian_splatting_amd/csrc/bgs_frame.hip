@@ -24,6 +24,12 @@ int fail(bgs_ctx* ctx, int status, const std::string& msg) {
     return status;
 }
 
+int enter(bgs_ctx* ctx) { return hipSetDevice(ctx->device) == hipSuccess ? BGS_OK : fail(ctx, BGS_EHIP, "hipSetDevice failed"); }
+
+int enter_drained(bgs_ctx* ctx) {
+    const int rc = enter(ctx);
+    return rc != BGS_OK ? rc : finish_all(ctx);
+}
 
 // Lane i runs on stream i % S (S = bgs_set_pipeline_streams, default: the pipeline depth, i.e. a
 // stream per lane). With S < depth a stream holds the NEXT frame of a sibling lane while one executes,
@@ -938,33 +944,19 @@ int enqueue_frame(bgs_ctx* ctx, Lane& L, const FrameInputs& in) {
     L.last_replay = ctx->graph_replays != replays_before;
     L.last_strips = render && scan && p.raster.mode != 0 && heavy_in != nullptr;   // (launch_raster_scan's grid)
     {   // the persistent kernels' grids, as the launchers above made them (capped_grid, kernels.h)
-        Lane::Grids g;
-        g.stamp = ++ctx->grid_stamps;
+        Lane::Grids g(++ctx->grid_stamps, n, in.grid_cap);
         g.tail = p.culled_tail && (have_keygen || have_compact);
-        g.n = n;
-        g.cap = in.grid_cap;
         if (have_keygen) {
-            g.blocks[g.FRONT] = kg.blocks;
-            g.per_tile[g.FRONT] = keygen_tile_splats(n);
+            g.launched(g.FRONT, keygen_tile_splats(n), kg.blocks);
             g.front_chainless = bucket && !p.culled_tail;
         } else if (have_compact) {
-            g.blocks[g.FRONT] = ek.blocks;
-            g.per_tile[g.FRONT] = ENTRIES_TILE;
+            g.launched(g.FRONT, ENTRIES_TILE, ek.blocks);
         }
-        if (!bucket && places > 0 && n > 0) {
-            g.per_tile[g.DEPTH] = sort_tile_size(p.large);
-            g.blocks[g.DEPTH] = capped_grid(n, g.per_tile[g.DEPTH], p.sort_blocks);
-        }
+        if (!bucket && places > 0 && n > 0) g.launched(g.DEPTH, sort_tile_size(p.large), capped_grid(n, sort_tile_size(p.large), p.sort_blocks));
         if (render && n > 0) {
-            g.per_tile[g.PROJECT] = 256u;
-            g.blocks[g.PROJECT] = capped_grid(n, 256u, scan ? p.bin_blocks : p.emit_blocks);
-            if (scan) {
-                g.per_tile[g.BIN] = 1024u;
-                g.blocks[g.BIN] = capped_grid(n, 1024u, p.binning_blocks);
-            } else {
-                g.per_tile[g.TILE_SORT] = sort_tile_size(true);
-                g.blocks[g.TILE_SORT] = capped_grid(std::min<uint64_t>(L.inst[0].capacity, MAX_INSTANCE_CAPACITY), g.per_tile[g.TILE_SORT], p.tile_sort_blocks);
-            }
+            g.launched(g.PROJECT, 256u, capped_grid(n, 256u, scan ? p.bin_blocks : p.emit_blocks));
+            if (scan) g.launched(g.BIN, 1024u, capped_grid(n, 1024u, p.binning_blocks));
+            else g.launched(g.TILE_SORT, sort_tile_size(true), capped_grid(std::min<uint64_t>(L.inst[0].capacity, MAX_INSTANCE_CAPACITY), sort_tile_size(true), p.tile_sort_blocks));
         }
         L.grids = g;
     }
@@ -983,7 +975,7 @@ int enqueue_frame(bgs_ctx* ctx, Lane& L, const FrameInputs& in) {
 int run(bgs_ctx* ctx, const bgs_cloud* cloud, const bgs_view* view, const bgs_settings* s, bool render) {
     int rc = validate(ctx, cloud, view, s, render);
     if (rc != BGS_OK) return rc;
-    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, BGS_EHIP, "hipSetDevice failed");
+    if ((rc = enter(ctx)) != BGS_OK) return rc;
     const bool async = ctx->async_frames && render && ctx->binning == BINNING_SCAN;
     // a blocking call: complete whatever is queued first (surfaces its watchdog state), use lane 0;
     // an async frame: the next lane of the ring, completing its previous occupant first
@@ -1038,7 +1030,7 @@ int run(bgs_ctx* ctx, const bgs_cloud* cloud, const bgs_view* view, const bgs_se
 //     does not change; the positions are read when the graph runs, behind the event above.
 // So staleness is slow at worst, never wrong, and a small step (the usual case) keeps every hint useful.
 int apply_particle_step(bgs_ctx* ctx, bgs_cloud* cloud, void* behaviors, uint32_t count, float dt) {
-    if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, BGS_EHIP, "hipSetDevice failed");
+    if (int rc = enter(ctx); rc != BGS_OK) return rc;
     for (int i; (i = oldest_pending_lane(ctx)) >= 0;) {
         int rc = finish_lane(ctx, ctx->lanes[i]);
         if (rc != BGS_OK) return rc;

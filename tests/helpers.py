@@ -69,6 +69,14 @@ CONTROL_FIELDS = ("words", "header_words", "draw_count", "instance_count", "erro
                   "splitters", "bucket_count", "bucket_max_keys")
 
 
+def header_version() -> int:
+    """(BGS_VERSION_MAJOR << 16) | BGS_VERSION_MINOR as include/bgs.h defines them: what bgs_version() returns."""
+    import re
+    header = open(os.path.join(HERE, "..", "include", "bgs.h")).read()
+    major, minor = (int(re.search(rf"^#define\s+BGS_VERSION_{part}\s+(\d+)u?\b", header, re.M).group(1)) for part in ("MAJOR", "MINOR"))
+    return (major << 16) | minor
+
+
 def control_offsets() -> dict:
     """Word offsets of the fields of a Control block (csrc/bgs_device.h), from the host build of the header itself."""
     out = (ctypes.c_uint32 * 32)()

@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import helpers as H
 from bevy_gaussian_splatting_amd import (
     CloudSettings, DeviceEntriesChunk, DeviceSortedEntries, GaussianSplattingPlugin, SortConfig, SortTrigger, View, _native,
     update_sort_trigger)
@@ -37,7 +38,7 @@ def test_view_struct_keeps_its_size_and_offsets():
     assert fields == [name for name, _ in BgsView._fields_]
     assert "reserved_ptr" not in header
     lib = _native.load()
-    assert lib.bgs_version() == (0 << 16) | 9   # (0.5 .. 0.9: diagnostics added to bgs_diag.h; bgs_view as in 0.4)
+    assert lib.bgs_version() == H.header_version() == _native.ABI_VERSION
     # zero in both fields is what the helpers hand out
     v = View.headless(64, 64).to_native()
     assert v.entries_device_ptr == 0 and v.entry_count == 0

@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import helpers as H
 from bevy_gaussian_splatting_amd import (
     PARTICLE_BEHAVIOR_DTYPE, ParticleBehaviors, _native, random_particle_behaviors, step_reference)
 
@@ -66,7 +67,7 @@ def test_the_entry_point_is_declared_bound_and_documented():
     block = doc[doc.index('extern "C" {'):]
     assert f"pub fn {SYMBOL}(" in block[:block.index("\n}")]
     assert hasattr(_native.load(), SYMBOL)
-    assert _native.load().bgs_version() == (0 << 16) | 9   # purely additive: it did not move the version (0.5 .. 0.9 came with test hooks in bgs_diag.h)
+    assert _native.load().bgs_version() == H.header_version() == _native.ABI_VERSION
 
 
 def test_record_layout_is_the_references_64_bytes(tool):
