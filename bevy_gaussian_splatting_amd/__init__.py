@@ -5,7 +5,7 @@ Only the hot path is implemented: cloud upload, per-view d
 per-splat projection + SH colour, tile binning, tile rasterisation — all as hand-written
 HIP kernels for gfx950 in `csrc/`, reached through the C ABI in `include/bgs.h`.
 """
-from .camera import GaussianCamera, View, transform_from, rotation_y
+from .camera import GaussianCamera, View, transform_from, rotation_y, color_attachment_offset, composite_reference
 from .gaussian import (
     Gaussian3d,
     PlanarGaussian3d,
@@ -93,4 +93,5 @@ __all__ = [
     "PlanarGaussian4d", "random_gaussians_4d_seeded", "TimeSlicer", "slice_float64", "slice_reference",
     "GaussianInterpolator", "interpolate_reference", "interpolation_factor",
     "PlaybackMode", "playback_update", "MorphPair", "ResidentCloud4d",
+    "color_attachment_offset", "composite_reference",
 ]

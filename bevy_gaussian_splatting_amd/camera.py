@@ -40,6 +40,41 @@ class BgsView(ctypes.Structure):
     ]
 
 
+# values of `bgs_view.reserved[0]` (include/bgs.h BGS_VIEW_ATTACH_*): what depth_device_ptr names
+VIEW_ATTACH_DEPTH_ONLY = 0
+VIEW_ATTACH_COLOR = 1
+
+
+def color_attachment_offset(width: int, height: int, samples: int) -> int:
+    """Byte offset of the colour plane in a view's attachment pair: behind the width * height * samples floats of the depth
+    plane, at the next multiple of 16 (include/bgs.h; `bgs::color_attachment_offset` of include/bgs.hpp)."""
+    return (int(width) * int(height) * int(samples) * 4 + 15) // 16 * 16
+
+
+def composite_reference(C: np.ndarray, T: np.ndarray, dst: np.ndarray) -> np.ndarray:
+    """The numpy twin of a colour-attached frame's resolve (include/bgs.h), operation for operation in f32.
+    C [..., 4]: what the splats contribute to the pixel, alpha = 1 - mean_s(T_s); T [..., S]: the per-sample
+    transmittances; dst [..., S, 4]: the colour plane. acc = T_0 d_0, then acc = fma(T_s, d_s, acc) in sample order, then
+    out = fma(acc, 1/S, C): every line rounded once. A fused multiply-add is formed in f64, where the product of two f32 is
+    exact, and rounded to f32: exact FMA bits whenever the f64 sum is exact (always for T_s = 1 and terms within 2^29 of
+    each other: the pixels no fragment reaches), and otherwise off the true FMA only where the f64 sum falls within 2^-29
+    ulp of an f32 rounding boundary."""
+    C = np.asarray(C, dtype=np.float32)
+    T = np.asarray(T, dtype=np.float32)
+    dst = np.asarray(dst, dtype=np.float32)
+    S = T.shape[-1]
+    if dst.shape[-2:] != (S, 4) or C.shape[-1] != 4:
+        raise ValueError("shapes: C [..., 4], T [..., S], dst [..., S, 4]")
+
+    def fma(a, b, c):
+        return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(np.float32)
+
+    acc = (T[..., 0, None] * dst[..., 0, :]).astype(np.float32)
+    for s in range(1, S):
+        acc = fma(T[..., s, None], dst[..., s, :], acc)
+    return fma(acc, np.float32(1.0 / S), C)
+
+
 @dataclass
 class GaussianCamera:
     """src/camera.rs:6-9. `order` is Bevy's `Camera.order` = index of this camera's sorted
@@ -110,6 +145,11 @@ class View:
     # against with GreaterEqual (src/render/mod.rs:959-974), or 0: no scene depth. GaussianSplattingPlugin.upload_depth
     # puts a host array there.
     depth_device_ptr: int = 0
+    # depth_device_ptr names the view's attachment PAIR (`bgs_view.reserved[0]` = BGS_VIEW_ATTACH_COLOR): behind the depth
+    # plane, at `color_attachment_offset`, lie width * height * samples float4 of linear premultiplied RGBA, [y][x][sample],
+    # and the frame blends over them sample by sample instead of over `clear_color` (which is then ignored).
+    # GaussianSplattingPlugin.upload_attachments lays such a pair out.
+    color_attachment: bool = False
     # The camera's chunk of sorted entries kept on the device (`bgs_view.entries_device_ptr` / `entry_count`): anything with
     # `ptr` and `count` — a `DeviceEntriesChunk` from `DeviceSortedEntries.chunk(camera_index)` — or None. `sort` writes its
     # result there as well, `render` draws the chunk as it is instead of sorting (include/bgs.h).
@@ -173,6 +213,7 @@ class View:
         v.delta_time = float(self.delta_time)
         v.sample_count = int(self.msaa_samples)
         v.depth_device_ptr = int(self.depth_device_ptr)
+        v.reserved[0] = VIEW_ATTACH_COLOR if self.color_attachment else VIEW_ATTACH_DEPTH_ONLY
         if self.entries is not None:
             v.entries_device_ptr = int(self.entries.ptr)
             v.entry_count = int(self.entries.count)

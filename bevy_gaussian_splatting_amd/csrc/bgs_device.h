@@ -50,7 +50,12 @@ struct FrameParams {
     // MultisampleState.count of the pipeline = Msaa::samples() of the camera (src/render/mod.rs:357-424,975-979): 1, 2, 4 or 8
     uint32_t sample_count;
     // the view's depth attachment (Depth32Float, reverse-Z, [y][x][sample] floats) the quads are tested against with
-    // GreaterEqual (src/render/mod.rs:959-974), as a device address; 0 = none
+    // GreaterEqual (src/render/mod.rs:959-974), as a device address; 0 = none.
+    // Bit 0 (ATTACH_COLOR_TAG) says that the view's COLOUR attachment lies behind the depth plane (include/bgs.h,
+    // BGS_VIEW_ATTACH_COLOR). Every valid depth address is a multiple of 4 and such a pair's a multiple of 16, so the bit is
+    // free, and the flag travels wherever the address does (kernel arguments, captured graphs) in a struct whose layout
+    // the host shim's ctypes image pins. Kernels read the planes through attach_depth_address / attach_color_address only;
+    // `!= 0` keeps meaning "a depth attachment".
     uint64_t depth_ptr;
     // Per-frame constants the vertex stage used to re-derive per splat (each a few correctly rounded divisions / square
     // roots of uniform data: ~130 instructions per thread). Formed by fill_frame_params on the host with the same IEEE
@@ -60,6 +65,18 @@ struct FrameParams {
     uint32_t visualize_bbox;   // CloudSettings::visualize_bounding_box (src/render/gaussian.wgsl:486-495): the quads' frames
 };
 static_assert(sizeof(FrameParams) % 8 == 0 && sizeof(FrameParams) / 4 <= 256, "keygen copies it with one block");
+
+// The attachment pair behind FrameParams::depth_ptr (include/bgs.h, bgs_view.reserved[0]): w * h * S floats of depth, then,
+// at the next multiple of 16 bytes, w * h * S float4 of colour, both [y][x][sample].
+constexpr uint64_t ATTACH_COLOR_TAG = 1ull;
+constexpr uint64_t attach_color_offset(const uint64_t width, const uint64_t height, const uint64_t samples) {
+    return (width * height * samples * 4u + 15u) & ~15ull;
+}
+constexpr bool attach_has_color(const uint64_t depth_ptr) { return (depth_ptr & ATTACH_COLOR_TAG) != 0ull; }
+constexpr uint64_t attach_depth_address(const uint64_t depth_ptr) { return depth_ptr & ~ATTACH_COLOR_TAG; }
+constexpr uint64_t attach_color_address(const uint64_t depth_ptr, const uint64_t width, const uint64_t height, const uint64_t samples) {
+    return attach_depth_address(depth_ptr) + attach_color_offset(width, height, samples);
+}
 
 // rasterize_mode values (include/bgs.h)
 constexpr uint32_t RASTERIZE_CLASSIFICATION = 0, RASTERIZE_COLOR = 1, RASTERIZE_DEPTH = 2,

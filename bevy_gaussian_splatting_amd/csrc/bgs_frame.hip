@@ -258,6 +258,15 @@ int validate(bgs_ctx* ctx, const bgs_cloud* cloud, const bgs_view* view, const b
                                          "overlay or 2 / 8 samples per pixel: a frame would leave the trace buffer untouched");
         if (view->depth_device_ptr % (4u * samples) != 0u)
             return fail(ctx, BGS_EINVAL, "bgs_view.depth_device_ptr must be aligned to one pixel's samples (4 * sample_count bytes)");
+        // what depth_device_ptr names (bgs.h: BGS_VIEW_ATTACH_*): the depth plane alone, or the depth and colour planes
+        if (view->reserved[0] > BGS_VIEW_ATTACH_COLOR)
+            return fail(ctx, BGS_EINVAL, "bgs_view.reserved[0] must be BGS_VIEW_ATTACH_DEPTH_ONLY (0) or BGS_VIEW_ATTACH_COLOR (1); got " +
+                                             std::to_string(view->reserved[0]));
+        if (view->reserved[0] == BGS_VIEW_ATTACH_COLOR && view->depth_device_ptr == 0ull)
+            return fail(ctx, BGS_EINVAL, "bgs_view.reserved[0] is BGS_VIEW_ATTACH_COLOR but bgs_view.depth_device_ptr is 0: the colour plane lies "
+                                         "behind a depth plane (all 0.0 for a host without geometry)");
+        if (view->reserved[0] == BGS_VIEW_ATTACH_COLOR && view->depth_device_ptr % 16u != 0u)
+            return fail(ctx, BGS_EINVAL, "bgs_view.reserved[0] is BGS_VIEW_ATTACH_COLOR: bgs_view.depth_device_ptr must then be aligned to 16 bytes");
         const float w = view->viewport[2], h = view->viewport[3];
         if (!(w >= 1.0f) || !(h >= 1.0f) || w > 4096.0f || h > 4096.0f || w != std::floor(w) || h != std::floor(h))
             return fail(ctx, BGS_EINVAL, "viewport width/height must be integers in [1, 4096]");
@@ -384,6 +393,7 @@ void fill_stats(const bgs_ctx* ctx, Lane& L, const FrameTotals& t) {
             bytes += V * (B - 16) + V * R + V * 8 + V * 8 + I * 8 + I * 8 + P * 16;   // (+ the 4-byte tile rect per rank, written by project_kernel and read by bin_kernel)
         else
             bytes += V * (B - 16) + V * R + I * 8 + 2 * I * 16 + I * (4 + R) + P * 16;
+        if (attach_has_color(p.fp.depth_ptr)) bytes += P * p.fp.sample_count * 16;   // the colour attachment, read once by the epilogue
     }
     stt.algorithmic_bytes = bytes;
     L.has_result = true;

@@ -51,7 +51,10 @@ inline void fill_frame_params(uint32_t n, const bgs_view* view, const bgs_settin
     fp.srgb8_target = 0;
     fp.sort_path = 0;  // chosen per frame by the host (bgs_frame.hip)
     fp.sample_count = view->sample_count ? view->sample_count : 4u;   // 0 = not set = Msaa::default() = Sample4
-    fp.depth_ptr = view->depth_device_ptr;
+    // (bit 0: the colour attachment lies behind the depth plane, bgs_device.h ATTACH_COLOR_TAG; check_inputs has seen to it
+    // that the address of such a pair is set and 16-byte aligned)
+    fp.depth_ptr = view->depth_device_ptr |
+                   (view->depth_device_ptr != 0ull && view->reserved[0] == BGS_VIEW_ATTACH_COLOR ? ATTACH_COLOR_TAG : 0ull);
     // uniform parts of world_to_local_direction (gaussian.wgsl:166-176: normalize(basis[k]) = v / length(v),
     // length = sqrt(dot)) and of the bounding boxes (1.0 / viewport): IEEE binary32, the order of splat_math.h
     for (int k = 0; k < 3; ++k) {

@@ -1121,6 +1121,39 @@ template <int MSAA> __device__ __forceinline__ typename TransOf<MSAA>::type tran
 __device__ __forceinline__ float trans_mean(const float T) { return T; }
 __device__ __forceinline__ float trans_mean(const PxMs& T) { return T.S * T.rb; }
 template <int NS> __device__ __forceinline__ float trans_mean(const PxMsN<NS>& T) { return T.S * T.rb; }
+// sample k's transmittance T_k = S * r[k], one rounding (k is a constant after unrolling)
+__device__ __forceinline__ float trans_sample(const float T, const int) { return T; }
+__device__ __forceinline__ float trans_sample(const PxMs& T, const int k) { return T.S * (k == 0 ? T.r0 : k == 1 ? T.r1 : k == 2 ? T.r2 : T.r3); }
+template <int NS> __device__ __forceinline__ float trans_sample(const PxMsN<NS>& T, const int k) { return T.S * T.r[k]; }
+
+// ---------------------------------------------------------------------------------------
+// The view's COLOUR attachment (include/bgs.h BGS_VIEW_ATTACH_COLOR; the blend state src/render/mod.rs:944-948 applied to a
+// target that already holds the scene): every sample of the target blends as dst = src + dst (1 - src.a), so the resolved
+// pixel is C + mean_s(T_s d_s) — not C + mean_s(T_s) * clear, which is what it collapses to for a constant d. Only the
+// DEPTH instantiations have it (the attachments come as a pair), as a wave-uniform branch of their epilogue (FrameParams
+// sits in scalar registers): nothing of it is live across the record loops, and a depth-only frame takes the `clear`
+// arm with the bits it always had. Arithmetic, per channel, every line one rounding:
+//     T_s = S * r[s];  acc = T_0 * d_0;  acc = fma(T_s, d_s, acc), s = 1 .. S-1;  out = fma(acc, 1/S, C)
+// with alpha's C = 1 - mean_s(T_s) as the clear arm forms it. The S float4 of a pixel are read here and nowhere else, once
+// per frame: non-temporal loads, for the reason the target's stores are (raster_tile).
+// ---------------------------------------------------------------------------------------
+template <int MSAA, typename Trans>
+__device__ __forceinline__ float4 resolve_over_attachment(const FrameParams& fp, const size_t at, const Trans& T, const float cr,
+                                                          const float cg, const float cb, const float Tf) {
+    typedef float v4f __attribute__((ext_vector_type(4)));
+    const v4f* __restrict__ d = reinterpret_cast<const v4f*>(attach_color_address(fp.depth_ptr, (uint64_t)fp.width, (uint64_t)fp.height, MSAA)) + at * MSAA;
+    const float t0 = trans_sample(T, 0);
+    const v4f d0 = __builtin_nontemporal_load(d);
+    float ar = t0 * d0.x, ag = t0 * d0.y, ab = t0 * d0.z, aa = t0 * d0.w;
+#pragma unroll
+    for (int k = 1; k < MSAA; ++k) {
+        const float tk = trans_sample(T, k);
+        const v4f dk = __builtin_nontemporal_load(d + k);
+        ar = fmaf(tk, dk.x, ar); ag = fmaf(tk, dk.y, ag); ab = fmaf(tk, dk.z, ab); aa = fmaf(tk, dk.w, aa);
+    }
+    constexpr float INV = 1.0f / (float)MSAA;
+    return make_float4(fmaf(ar, INV, cr), fmaf(ag, INV, cg), fmaf(ab, INV, cb), fmaf(aa, INV, 1.0f - Tf));
+}
 
 // Rgba8UnormSrgb packing of one premultiplied linear pixel (shared by the rasteriser's fused output and
 // encode_srgb8_kernel, so both give the same bytes). Exact for every binary32 input (include/bgs.h "packed outputs"):
@@ -1418,7 +1451,7 @@ __global__ __launch_bounds__(256) void raster_kernel(FrameParams fp, const float
     if constexpr (DEPTH) {
         float lo = INFINITY, hi = -INFINITY;
         if (in_image) {
-            const float* dsrc = reinterpret_cast<const float*>(fp.depth_ptr) + ((size_t)py * (size_t)fp.width + (size_t)px) * MSAA;
+            const float* dsrc = reinterpret_cast<const float*>(attach_depth_address(fp.depth_ptr)) + ((size_t)py * (size_t)fp.width + (size_t)px) * MSAA;
             if constexpr (MSAA == 4) dpx = *reinterpret_cast<const float4*>(dsrc);
             else if constexpr (MSAA == 1) dpx.x = dpx.y = dpx.z = dpx.w = dsrc[0];
             if constexpr (MSAA == 1 || MSAA == 4) {
@@ -1485,9 +1518,13 @@ __global__ __launch_bounds__(256) void raster_kernel(FrameParams fp, const float
         // dst = src + dst*(1-src.a) unrolled over the whole list, target cleared to `clear`; multisampled: the mean
         // of the samples, C + clear * mean_s(T_s)
         const float Tf = trans_mean(tm);
-        fb[(size_t)py * (size_t)fp.width + (size_t)px] =
-            make_float4(fmaf(Tf, clear.x, crg.x), fmaf(Tf, clear.y, crg.y), fmaf(Tf, clear.z, cb),
-                        fmaf(Tf, clear.w, 1.0f - Tf));
+        const size_t at = (size_t)py * (size_t)fp.width + (size_t)px;
+        float4 c;
+        bool over_attachment = false;
+        if constexpr (DEPTH) over_attachment = attach_has_color(fp.depth_ptr);   // (uniform over the launch)
+        if (over_attachment) c = resolve_over_attachment<MSAA>(fp, at, tm, crg.x, crg.y, cb, Tf);
+        else c = make_float4(fmaf(Tf, clear.x, crg.x), fmaf(Tf, clear.y, crg.y), fmaf(Tf, clear.z, cb), fmaf(Tf, clear.w, 1.0f - Tf));
+        fb[at] = c;
     }
 }
 
@@ -1641,7 +1678,7 @@ __device__ __forceinline__ uint32_t raster_tile(const FrameParams& fp, const flo
             if constexpr (DEPTH && (MSAA == 1 || MSAA == 4)) {
                 float4 d = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
                 if (inside) {
-                    const float* dsrc = reinterpret_cast<const float*>(fp.depth_ptr) + ((size_t)py * (size_t)fp.width + (size_t)px) * MSAA;
+                    const float* dsrc = reinterpret_cast<const float*>(attach_depth_address(fp.depth_ptr)) + ((size_t)py * (size_t)fp.width + (size_t)px) * MSAA;
                     if constexpr (MSAA == 4) d = *reinterpret_cast<const float4*>(dsrc);
                     else d.x = d.y = d.z = d.w = dsrc[0];
                     lo = fminf(lo, fminf(fminf(d.x, d.y), fminf(d.z, d.w)));
@@ -1650,7 +1687,7 @@ __device__ __forceinline__ uint32_t raster_tile(const FrameParams& fp, const flo
                 if constexpr (MSAA == 4) s_depth[r * 64 + lane] = d;
                 else dpx[r] = d.x;
             } else if constexpr (DEPTH) {
-                const float* dsrc = reinterpret_cast<const float*>(fp.depth_ptr) + ((size_t)py * (size_t)fp.width + (size_t)px) * MSAA;
+                const float* dsrc = reinterpret_cast<const float*>(attach_depth_address(fp.depth_ptr)) + ((size_t)py * (size_t)fp.width + (size_t)px) * MSAA;
 #pragma unroll
                 for (int k = 0; k < MSAA; ++k) {
                     const float d = inside ? dsrc[k] : 0.0f;
@@ -1670,7 +1707,7 @@ __device__ __forceinline__ uint32_t raster_tile(const FrameParams& fp, const flo
                 for (int rr = 0; rr < 4; ++rr) {
                     const int pyt = (int)ty * TILE_PX + (lane >> 4) + 4 * rr;
                     if (px < fp.width && pyt < fp.height) {
-                        const float* dsrc = reinterpret_cast<const float*>(fp.depth_ptr) + ((size_t)pyt * (size_t)fp.width + (size_t)px) * MSAA;
+                        const float* dsrc = reinterpret_cast<const float*>(attach_depth_address(fp.depth_ptr)) + ((size_t)pyt * (size_t)fp.width + (size_t)px) * MSAA;
 #pragma unroll
                         for (int k = 0; k < MSAA; ++k) { const float d = dsrc[k]; lo = fminf(lo, d); hi = fmaxf(hi, d); }
                     }
@@ -1972,9 +2009,14 @@ __device__ __forceinline__ uint32_t raster_tile(const FrameParams& fp, const flo
             if (pxw < fp.width && py < fp.height) {
                 // (multisampled: the resolve — the mean of the samples is C + clear * mean_s(T_s))
                 const float Tf = trans_mean(T[r]);
-                const float4 c = make_float4(fmaf(Tf, fp.clear[0], crg[r].x), fmaf(Tf, fp.clear[1], crg[r].y),
-                                             fmaf(Tf, fp.clear[2], cb[r]), fmaf(Tf, fp.clear[3], 1.0f - Tf));
                 const size_t at = (size_t)py * (size_t)fp.width + (size_t)pxw;
+                // ... or, over the view's colour attachment, C + mean_s(T_s d_s) (resolve_over_attachment; wave-uniform)
+                float4 c;
+                bool over_attachment = false;
+                if constexpr (DEPTH) over_attachment = attach_has_color(fp.depth_ptr);
+                if (over_attachment) c = resolve_over_attachment<MSAA>(fp, at, T[r], crg[r].x, crg[r].y, cb[r], Tf);
+                else c = make_float4(fmaf(Tf, fp.clear[0], crg[r].x), fmaf(Tf, fp.clear[1], crg[r].y),
+                                     fmaf(Tf, fp.clear[2], cb[r]), fmaf(Tf, fp.clear[3], 1.0f - Tf));
                 // Streaming stores: a frame's 33 MB target is written once and read by nobody on this chip before
                 // the next frames have pushed it out anyway; kept out of the L2 / Infinity Cache allocation the
                 // cloud planes that keygen and project+bin read every frame stay resident (+1.5 % dense, +3 %

@@ -19,7 +19,7 @@ from typing import Optional, Union
 import numpy as np
 
 from . import _native
-from .camera import View
+from .camera import View, color_attachment_offset
 from .diag import DiagHooks, _fptr, _uptr
 from .gaussian import PlanarGaussian3d, PlanarGaussian3dF16, PlanarGaussian4d
 from .particles import PARTICLE_BEHAVIOR_DTYPE, ParticleBehaviors, ParticleBehaviorsHandle
@@ -748,6 +748,37 @@ class GaussianSplattingPlugin(DiagHooks):
         p = self.device_alloc(d.nbytes)
         self.upload_bytes(p, d)
         return p
+
+    def upload_attachments(self, depth: np.ndarray, color: Optional[np.ndarray] = None):
+        """Put a view's attachment pair on the device in ONE allocation (include/bgs.h BGS_VIEW_ATTACH_COLOR): `depth`
+        [height, width, samples] float32 as for `upload_depth`, and behind it, at `color_attachment_offset`, `color`
+        [height, width, samples, 4] float32 — linear, premultiplied, unclamped RGBA, what the engine's opaque passes left in
+        the colour attachment. Returns (address, holder): the address for `View.depth_device_ptr` (with
+        `View.color_attachment = True` when `color` was given), and the allocation to `device_free` once the frames that
+        use it are complete — the same value today; hold on to it rather than to the view's field. Without `color` this is
+        `upload_depth` in an allocation whose start is 16-byte aligned."""
+        d = np.ascontiguousarray(depth, dtype=np.float32)
+        if d.ndim != 3 or d.shape[2] not in (1, 2, 4, 8):
+            raise ValueError("depth must be [height, width, samples] with 1, 2, 4 or 8 samples")
+        if color is None:
+            p = self.device_alloc(d.nbytes)
+            self.upload_bytes(p, d)
+            return p, p
+        c = np.ascontiguousarray(color, dtype=np.float32)
+        if c.shape != d.shape + (4,):
+            raise ValueError(f"color must be [height, width, samples, 4] = {d.shape + (4,)}, got {c.shape}")
+        h, w, s = d.shape
+        off = color_attachment_offset(w, h, s)
+        p = self.device_alloc(off + c.nbytes)
+        try:
+            if p % 16:
+                raise RuntimeError("device_alloc returned memory that is not 16-byte aligned")
+            self.upload_bytes(p, d)
+            self.upload_bytes(p + off, c)
+        except Exception:
+            self.device_free(p)
+            raise
+        return p, p
 
     def build_id(self) -> str:
         """`bgs_build_id()`: SHA-256 of the kernel sources the loaded library was compiled from."""

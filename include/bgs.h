@@ -45,6 +45,9 @@ extern "C" {
 #define BGS_VERSION_MAJOR 0
 #define BGS_VERSION_MINOR 9 /* 0.9: the grid cap of the persistent kernels and the read-back of a frame's grids (bgs_diag.h: bgs_set_grid_cap,
                                bgs_debug_frame_grids); the seam of this header, bgs_view, bgs_settings and bgs_stats as in 0.4.
+                               Still 0.9 with the view's colour attachment: bgs_view.reserved[0] got two named values
+                               (BGS_VIEW_ATTACH_*; size, offsets and the field's name as they were); zero — what every earlier
+                               binding passes and what bgs_view_perspective sets — is the behaviour of before, bit for bit.
                                0.8: the read-back of what a frame leaves for the next (bgs_diag.h: bgs_debug_frame_leftovers); the seam of this
                                header, bgs_view, bgs_settings and bgs_stats as in 0.4.
                                0.7: the tile rasterisers' test hook (bgs_diag.h: bgs_selftest_raster); the seam of this header, bgs_view,
@@ -99,7 +102,35 @@ typedef struct bgs_view {
      * and renders with Msaa::default() = 4; anything else is BGS_EINVAL. bgs_view_perspective sets 4. */
     uint32_t sample_count;
     uint32_t entry_count;      /* records behind entries_device_ptr: bgs_cloud_len(cloud) when that is set, else 0 */
+    /* reserved[0]: WHAT depth_device_ptr NAMES, one of BGS_VIEW_ATTACH_* below. The word keeps the name bindings built against
+     * 0.4 know it by (they zero it: BGS_VIEW_ATTACH_DEPTH_ONLY, the behaviour of before, bit for bit; bgs_view_perspective
+     * sets 0 too); size and offsets are as they were.
+     *   BGS_VIEW_ATTACH_DEPTH_ONLY (0): the depth plane described at depth_device_ptr, or nothing (pointer 0). The target
+     *     starts from clear_color.
+     *   BGS_VIEW_ATTACH_COLOR (1): the view's ATTACHMENT PAIR in ONE caller-owned allocation, what the engine's opaque passes
+     *     left behind: the depth plane exactly as below (w * h * S floats, [y][x][sample], S = sample_count), and at byte offset
+     *     round_up(w * h * S * 4, 16) the colour plane, w * h * S float4 laid out [y][x][sample]: linear, premultiplied,
+     *     unclamped RGBA in f32. The splats are one Transparent3d draw into a target that already holds the scene: every
+     *     sample blends as dst = src + dst (1 - src.a) (src/render/mod.rs:944-948), and the image handed back is the resolve.
+     *     A host without geometry hands a depth plane of 0.0. clear_color is IGNORED for such a frame. A second cloud is
+     *     drawn over a first one this way (S = 1: the first frame's f32 image IS a colour plane).
+     *     Arithmetic, per pixel and channel c, with C and the per-sample transmittances T_s as the frame forms them
+     *     (T_s = S r_s, the product of the pixel's common and per-sample factors, rounded once), d_s the plane's sample:
+     *         acc   = T_0 * d_0.c
+     *         acc   = fma(T_s, d_s.c, acc)            s = 1 .. S-1, in sample order
+     *         out.c = fma(acc, 1/S, C.c)              alpha: C.a = 1 - mean_s(T_s) as in every frame
+     *     every line rounded once (the products contract into the fused multiply-adds written here and nowhere else; 1/S is
+     *     exact). A pixel no fragment reaches (C = 0, T_s = 1) is the left-to-right f32 sum of its samples times 1/S.
+     *     The packed outputs (sRGB8, Rgba16Float, packed-only) are conversions of that pixel, as ever.
+     *     Works wherever the depth attachment does (both binning modes, asynchronous lanes, kept-order frames, captured
+     *     graphs: flag and address travel with the frame, no new capture) and is refused where that is (the tile trace).
+     *     bgs_stats.algorithmic_bytes counts the w * h * S * 16 bytes read. The memory must stay valid and UNWRITTEN until
+     *     the frame has completed (the depth attachment's rule).
+     *   BGS_EINVAL, naming the field: reserved[0] > 1; BGS_VIEW_ATTACH_COLOR with depth_device_ptr == 0 or with a
+     *     depth_device_ptr that is not 16-byte aligned. */
     uint32_t reserved[1];
+#define BGS_VIEW_ATTACH_DEPTH_ONLY 0u
+#define BGS_VIEW_ATTACH_COLOR 1u
     /* The view's depth attachment the draw is tested against (src/render/mod.rs:959-974: Depth32Float,
      * CompareFunction::GreaterEqual — reverse-Z —, depth_write_enabled false): a DEVICE pointer to
      * viewport.w * viewport.h * sample_count floats laid out [y][x][sample] (sample order: the standard pattern's) (what Bevy's opaque passes left), or

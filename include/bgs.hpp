@@ -243,6 +243,12 @@ struct PlanarGaussian3d {
     }
 };
 
+// Byte offset of the colour plane in a view's attachment pair (bgs.h BGS_VIEW_ATTACH_COLOR): behind the width * height *
+// samples floats of the depth plane, at the next multiple of 16. The pair's allocation is this plus width * height * samples * 16.
+constexpr uint64_t color_attachment_offset(uint64_t width, uint64_t height, uint64_t samples) {
+    return (width * height * samples * 4u + 15u) / 16u * 16u;
+}
+
 // The View uniform the path reads, built the way Bevy builds it for `Camera3d::default()`.
 struct View {
     bgs_view native{};
@@ -270,6 +276,11 @@ struct View {
     void set_msaa_samples(uint32_t samples) { native.sample_count = samples; }
     // The view's depth attachment as device memory ([y][x][sample] floats, reverse-Z; src/render/mod.rs:959-974), 0 = none.
     void set_depth(const void* device_ptr) { native.depth_device_ptr = (uint64_t)(uintptr_t)device_ptr; }
+    // The view's attachment PAIR (bgs.h BGS_VIEW_ATTACH_COLOR): the depth plane and, color_attachment_offset behind its start in
+    // the same 16-byte aligned allocation, width * height * samples float4 of linear premultiplied RGBA the frame blends over,
+    // sample by sample, instead of over the clear colour. `false` = the pointer names the depth plane alone (the default).
+    void set_color_attachment(bool attached) { native.reserved[0] = attached ? BGS_VIEW_ATTACH_COLOR : BGS_VIEW_ATTACH_DEPTH_ONLY; }
+    bool color_attachment() const { return native.reserved[0] == BGS_VIEW_ATTACH_COLOR; }
     // The camera's chunk of sorted entries kept on the device (bgs_view.entries_device_ptr / entry_count; `count` = the
     // cloud's length): bgs_sort writes its result there too, bgs_render draws it as it is instead of sorting. nullptr = none.
     void set_entries(const void* device_ptr, uint32_t count) {
