@@ -78,7 +78,8 @@ constexpr int MAX_LANES = 8;
 struct GraphKey {
     const void* cloud[6];
     const void* bufs[11];
-    uint32_t n, format, places, sort_mode, gaussian_mode, aabb, any_mode, srgb8, debug_flags;
+    uint32_t n, places, sort_mode, srgb8, debug_flags;
+    uint32_t project, raster;   // the launched instantiations of the vertex stage and the rasteriser: ProjectInst::key(), RasterInst::key()
     int32_t width, height;
     int32_t sort_blocks, bin_blocks, front_blocks;
     uint32_t sup_edge;
@@ -93,7 +94,6 @@ struct GraphKey {
     const void* front_func;
     uint32_t front_threads;
     uint32_t wide_bin;         // bin_kernel<16> (1024 threads) or <4>: follows the pipeline depth, not the grid sizes
-    uint32_t raster_variant;   // the launched rasteriser instantiation: samples | depth << 8 | overlay << 9 | mode (graph_key)
     uint32_t split_sub;        // FrameCleanup::split_sub, a rasteriser argument: how many quantile keys the captured clean-up leaves
 };
 struct FrameGraph {
@@ -142,7 +142,8 @@ struct FramePlan {
     int front_blocks = 0, emit_blocks = 0, tile_sort_blocks = 0;
     uint32_t out_format = 0, ntiles = 0;
     bool raster_cleans = false;     // the rasteriser zeroes the scratch region and reports the Control block (FrameCleanup)
-    RasterInst raster{};            // the instantiation launch_raster_scan launches
+    RasterInst raster{};            // the instantiation launch_raster_scan launches (launch_raster: its variant, samples, depth, overlay)
+    ProjectInst project{};          // the instantiation of the vertex stage (launch_project_bin / launch_project_emit)
     // heavy-tile strips; leaves tile costs / draws in cost order / makes that order anew; the kind of the cost plane
     // behind its order, whose saturation counts the frame reports (0: none); may replay a captured graph
     bool heavy = false, cost = false, ordered = false, refresh = false, graph_ok = false;

@@ -78,6 +78,9 @@ constexpr uint64_t attach_color_address(const uint64_t depth_ptr, const uint64_t
     return attach_depth_address(depth_ptr) + attach_color_offset(width, height, samples);
 }
 
+// cloud formats (kernels.h CloudPtrs::format): f32 planes, f16 planes, f32 with precomputed covariance
+constexpr uint32_t CLOUD_F32 = 0, CLOUD_F16 = 1, CLOUD_COV3D = 2;
+
 // rasterize_mode values (include/bgs.h)
 constexpr uint32_t RASTERIZE_CLASSIFICATION = 0, RASTERIZE_COLOR = 1, RASTERIZE_DEPTH = 2,
                    RASTERIZE_NORMAL = 3, RASTERIZE_OPTICAL_FLOW = 4, RASTERIZE_POSITION = 5;

@@ -642,14 +642,10 @@ int bgs_selftest_raster(bgs_ctx* ctx, const bgs_raster_selftest* in, float* host
     if (in->variant > 2u) return fail(ctx, BGS_EINVAL, "raster self-test: variant must be 0 (OBB), 1 (AABB3D) or 2 (surfel), got " + num(in->variant));
     if (in->overlay > 1u) return fail(ctx, BGS_EINVAL, "raster self-test: overlay must be 0 or 1, got " + num(in->overlay));
     if (in->mode > 2u) return fail(ctx, BGS_EINVAL, "raster self-test: mode must be 0, 1 or 2, got " + num(in->mode));
-    if (in->mode != 0u) {
-        // what a frame can be given: raster_scan_mode at a low and a high supertile level, with the kind's say and frames in flight
-        const int lo = raster_scan_mode((int)in->variant, ms, in->overlay != 0u, 0u, true, 2, 0u);
-        const int hi = raster_scan_mode((int)in->variant, ms, in->overlay != 0u, 3u, true, 2, 0u);
-        if ((int)in->mode != lo && (int)in->mode != hi)
-            return fail(ctx, BGS_EINVAL, "raster self-test: mode " + num(in->mode) + " is never chosen for variant " + num(in->variant) + " at " + num(ms) +
-                                             " samples" + (in->overlay ? " with the overlay" : "") + " (raster_scan_mode)");
-    }
+    const RasterInst inst{(int)in->variant, ms, in->depth != nullptr, in->overlay != 0u, (int)in->mode};
+    if (!inst.exists())
+        return fail(ctx, BGS_EINVAL, "raster self-test: mode " + num(in->mode) + " is not built for variant " + num(in->variant) + " at " + num(ms) +
+                                         " samples" + (in->overlay ? " with the overlay" : "") + " (RasterInst::exists)");
     if (in->reserved != 0u) return fail(ctx, BGS_EINVAL, "raster self-test: reserved must be 0");
     if (!(in->viewport_w > 0.0f) || !(in->viewport_h > 0.0f)) return fail(ctx, BGS_EINVAL, "raster self-test: viewport_w and viewport_h must be > 0");
     const uint32_t tiles_x = (in->width + TILE_PX - 1u) / TILE_PX, tiles_y = (in->height + TILE_PX - 1u) / TILE_PX, ntiles = tiles_x * tiles_y;
@@ -772,11 +768,11 @@ int bgs_selftest_raster(bgs_ctx* ctx, const bgs_raster_selftest* in, float* host
     if (in->order) cs.up(order_buf.ptr, in->order, (size_t)nblocks * sizeof(uint16_t));
     if (cs.ok) {
         const bool exits = in->mode != 0u;
-        launch_raster_scan(st, fp, fp_buf.ptr, rec_buf.ptr, lists_buf.ptr, cap, in->sup_edge, ctl, reinterpret_cast<float4*>(scan_buf.ptr),
-                           /*srgb8_default=*/nullptr, /*out_format=*/0u, FrameCleanup{}, /*tile_trace=*/nullptr, (int)in->mode,
-                           exits && in->heavy_count ? heavy_in_buf.ptr : nullptr, exits ? heavy_out_buf.ptr : nullptr,
-                           in->order ? order_buf.ptr : nullptr, cost_buf.ptr);
-        launch_raster(st, fp, rec_buf.ptr, inst_buf.ptr, ranges_buf.ptr, reinterpret_cast<float4*>(sort_buf.ptr), in->clear, ctl);
+        if (cs.check(launch_raster_scan(st, fp, inst, fp_buf.ptr, rec_buf.ptr, lists_buf.ptr, cap, in->sup_edge, ctl, reinterpret_cast<float4*>(scan_buf.ptr),
+                                        /*srgb8_default=*/nullptr, /*out_format=*/0u, FrameCleanup{}, /*tile_trace=*/nullptr,
+                                        exits && in->heavy_count ? heavy_in_buf.ptr : nullptr, exits ? heavy_out_buf.ptr : nullptr,
+                                        in->order ? order_buf.ptr : nullptr, cost_buf.ptr)))
+            cs.check(launch_raster(st, fp, inst, rec_buf.ptr, inst_buf.ptr, ranges_buf.ptr, reinterpret_cast<float4*>(sort_buf.ptr), in->clear, ctl));
     }
     cs.launched();
     cs.down(host_scan, scan_buf.ptr, (size_t)image_floats * sizeof(float));

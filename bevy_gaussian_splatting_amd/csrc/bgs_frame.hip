@@ -532,9 +532,10 @@ FramePlan plan_frame(const bgs_ctx& ctx, const Lane& L, const FrameInputs& in) {
     p.kept = in.render && in.view.entries_device_ptr != 0u && fp.n > 0u;
     p.places = p.kept ? 0u : depth_places(s);
     p.scan = ctx.binning == BINNING_SCAN;
-    p.surfel = in.render && fp.gaussian_mode == 0u && fp.aabb != 0u;
-    p.rec_bytes = p.surfel ? sizeof(RecordSurfel) : sizeof(Record);
     p.cloud_format = in.cloud->ptrs.format;
+    p.project = project_instantiation(fp, p.cloud_format);
+    p.surfel = in.render && p.project.surfel;
+    p.rec_bytes = p.surfel ? sizeof(RecordSurfel) : sizeof(Record);
     // The culled tail (index order, 8 B per culled splat: 7 of the 24 MB keygen moves on the headline frame) has two
     // readers: bgs_sort's full list and RasterizeMode::Depth (sorted[N-1] of the full list, gaussian.wgsl:331-340).
     // Every other rendered frame skips the writes; bgs_sorted_entries_device_ptr after a render has always meant the
@@ -623,7 +624,7 @@ FramePlan plan_frame(const bgs_ctx& ctx, const Lane& L, const FrameInputs& in) {
     // chip its launch ends with its longest lists' serial chains, which do not saturate and only pay the checks (231 -> 272 us)
     p.raster_cleans = in.render && p.scan && fp.tiles_x > 0 && fp.tiles_y > 0 && !(flags & BGS_DEBUG_NO_RASTER_CLEANUP);
     const bool kind_midround = ctx.depth > 1 && state.midround(in.kind);
-    p.raster = raster_instantiation(fp, p.level, kind_midround, ctx.depth, flags);
+    p.raster = raster_instantiation(fp, p.level, kind_midround, ctx.depth, flags, ctx.tile_trace != nullptr);
     p.ntiles = (uint32_t)(fp.tiles_x * fp.tiles_y);
     // the feedback buffers alternate with every completed frame: not under frame graphs
     const bool feedback = p.raster_cleans && !(in.allow_graph && ctx.use_graphs) && p.ntiles <= 65535u;
@@ -632,14 +633,14 @@ FramePlan plan_frame(const bgs_ctx& ctx, const Lane& L, const FrameInputs& in) {
     // 1 M frame: raster 49.4 -> 45.3 us, the heaviest tiles' serial chains split four ways), but with several frames in
     // flight that tail is filled by the other lanes' kernels anyway and the extra workgroups and the flag load only cost
     // (20.6 -> 20.0 k frames/s with 8 lanes; profiles/r3_notes.md). Not with the tile trace.
-    p.heavy = feedback && p.raster.mode == 1 && p.level >= 2u && !ctx.tile_trace &&
+    p.heavy = feedback && p.raster.mode == 1 && p.level >= 2u && !p.raster.trace &&
               (ctx.depth == 1 || (flags & BGS_DEBUG_STRIPS_ANY_DEPTH)) && !(flags & BGS_DEBUG_NO_STRIPS);
     // Tile costs (kernels.h TileCost): every BINNING_SCAN frame leaves them, and a frame with more tile waves than the
     // chip holds at once draws its raster workgroups in the order made of a completed frame's costs; the tile trace shows
     // it. Unlike the heavy-tile strips it pays with frames in flight too, if little (+0.6 % dense, +0.9 % surfel
     // frames/s; alone on the chip 6-21 % of the rasteriser's time).
     p.cost = feedback && (ctx.depth == 1 || !(flags & BGS_DEBUG_NO_TILE_COST_PIPELINED)) && !(flags & BGS_DEBUG_NO_TILE_COST);
-    if (p.cost && p.ntiles > (uint32_t)(ctx.num_cus * 4 * raster_scan_waves_per_simd(fp))) {
+    if (p.cost && p.ntiles > (uint32_t)(ctx.num_cus * 4 * p.raster.waves_per_simd())) {
         // F.order holds a permutation of this grid's workgroups from the moment it was first made for the grid
         // (order_grid); it is made again from the newest completed costs every TILE_ORDER_REFRESH-th frame. (ensure_cost
         // keeps the lane's buffers, and what they hold, unless the grid outgrew them.)
@@ -661,7 +662,7 @@ FramePlan plan_frame(const bgs_ctx& ctx, const Lane& L, const FrameInputs& in) {
     // A kept-order frame is a graph of its own kind (Lane::graph): the compaction stands in keygen's place as the updated
     // node, and its arguments carry the caller's chunk as well. (It is never a bucket frame: p.bucket_sub stays 1.)
     p.graph_ok = in.allow_graph && ctx.use_graphs && p.raster_cleans && p.bucket_sub <= BUCKET_SUB_KERNARG &&
-                 !(flags & BGS_DEBUG_NO_GRAPHS) && !ctx.tile_trace;
+                 !(flags & BGS_DEBUG_NO_GRAPHS) && !p.raster.trace;
     return p;
 }
 
@@ -678,18 +679,14 @@ GraphKey graph_key(const FramePlan& p, const FrameInputs& in, const Lane& L, con
     const void* bufs[11] = {L.entries[0].ptr, L.entries[1].ptr, L.culled.ptr, L.records.ptr, L.coarse.ptr, L.fb.ptr, L.fb8.ptr,
                             L.scratch.ptr, L.d_fp.ptr, L.h_ctl_dev, L.bucket_slots.ptr};   // (L.rects lives and dies with L.entries: ensure_entries)
     std::memcpy(key.bufs, bufs, sizeof bufs);
-    key.n = p.n; key.format = p.cloud_format; key.places = p.places; key.sort_mode = in.settings.sort_mode;
-    key.gaussian_mode = fp.gaussian_mode; key.aabb = fp.aabb;
-    key.any_mode = (fp.rasterize_mode != RASTERIZE_COLOR || fp.draw_mode != 0u) ? 1u : 0u;
-    key.srgb8 = p.out_format;
+    key.n = p.n; key.places = p.places; key.sort_mode = in.settings.sort_mode;
+    key.project = p.project.key(); key.raster = p.raster.key(); key.srgb8 = p.out_format;
     key.debug_flags = in.debug_flags;
     key.width = fp.width; key.height = fp.height;
     key.sort_blocks = p.bucket ? 0 : p.sort_blocks;  // the bucket sort's grid is fixed
     key.bin_blocks = p.bin_blocks * 4096 + p.binning_blocks;   // (the bin kernel's shape follows the pipeline depth, as keygen's does: key.front_threads)
     key.front_blocks = (int32_t)front.blocks; key.front_func = front.func; key.front_threads = front.threads;   // (kept: entries_blocks(n) of the compaction)
     key.wide_bin = p.wide_bin ? 1u : 0u;
-    const RasterInst& r = p.raster;
-    key.raster_variant = r.samples | (r.depth ? 0x100u : 0u) | (r.overlay ? 0x200u : 0u) | (r.mode == 1 ? 0x400u : r.mode == 2 ? 0x800u : 0u);
     key.split_sub = p.split_sub_out;   // (round 5's advisor: a replay across a 524 k-pair step of the hint left a table of the captured sub under the new sub's label)
     key.sup_edge = p.sup_edge;
     key.scratch = L.layout;
@@ -867,7 +864,7 @@ int enqueue_frame(bgs_ctx* ctx, Lane& L, const FrameInputs& in) {
     // ---- 5. the launches of one frame, in stream order (issued directly, or once into a stream capture)
     auto issue = [&]() -> hipError_t {
         mark(0);
-        if (cost_in) launch_tile_order(st, cost_in, tile_order, p.ntiles, fp, p.raster.mode != 0);   // (counted with the frame's first stage)
+        if (cost_in) launch_tile_order(st, cost_in, tile_order, p.ntiles, p.raster);   // (counted with the frame's first stage)
         if (have_keygen) {
             if (bucket && p.bucket_sub > BUCKET_SUB_KERNARG) {
                 const hipError_t ce = hipMemcpyAsync(L.d_split_keys.ptr, L.h_split_keys.ptr, (BUCKET_COUNT * p.bucket_sub - 1u) * sizeof(uint32_t),
@@ -896,17 +893,19 @@ int enqueue_frame(bgs_ctx* ctx, Lane& L, const FrameInputs& in) {
         }
         mark(2);
         if (render && scan) {
-            launch_project_bin(st, fp, L.d_fp.ptr, in.cloud->ptrs, draw_list, L.culled.ptr, ctl, bin_status, L.records.ptr, L.rects.ptr, L.coarse.ptr,
-                               coarse_cap, p.sup_edge, /*ticket_slot=*/4, p.bin_blocks, p.binning_blocks, p.wide_bin);
+            hipError_t e = launch_project_bin(st, fp, p.project, L.d_fp.ptr, in.cloud->ptrs, draw_list, L.culled.ptr, ctl, bin_status, L.records.ptr,
+                                              L.rects.ptr, L.coarse.ptr, coarse_cap, p.sup_edge, /*ticket_slot=*/4, p.bin_blocks, p.binning_blocks, p.wide_bin);
+            if (e != hipSuccess) return e;
             mark(3);
-            launch_raster_scan(st, fp, L.d_fp.ptr, L.records.ptr, L.coarse.ptr, coarse_cap, p.sup_edge, ctl, L.fb.ptr, L.fb8.ptr,
-                               (flags & BGS_DEBUG_SEPARATE_ENCODE) ? 0u : p.out_format, cl, ctx->tile_trace,
-                               p.raster.mode, heavy_in, heavy_out, tile_order, cost_out);
+            e = launch_raster_scan(st, fp, p.raster, L.d_fp.ptr, L.records.ptr, L.coarse.ptr, coarse_cap, p.sup_edge, ctl, L.fb.ptr, L.fb8.ptr,
+                                   (flags & BGS_DEBUG_SEPARATE_ENCODE) ? 0u : p.out_format, cl, ctx->tile_trace, heavy_in, heavy_out, tile_order, cost_out);
+            if (e != hipSuccess) return e;
             mark(6);
         } else if (render) {
             const uint32_t capacity = (uint32_t)std::min<uint64_t>(L.inst[0].capacity, MAX_INSTANCE_CAPACITY);
-            launch_project_emit(st, fp, in.cloud->ptrs, draw_list, L.culled.ptr, ctl, scan_status, L.records.ptr, L.inst[0].ptr, capacity,
-                                /*ticket_slot=*/4, p.emit_blocks);
+            hipError_t e = launch_project_emit(st, fp, p.project, in.cloud->ptrs, draw_list, L.culled.ptr, ctl, scan_status, L.records.ptr, L.inst[0].ptr,
+                                               capacity, /*ticket_slot=*/4, p.emit_blocks);
+            if (e != hipSuccess) return e;
             mark(3);
             for (uint32_t q = 0; q < 2; ++q)
                 launch_onesweep_pass(st, L.inst[q].ptr, L.inst[q ^ 1].ptr, &ctl->instance_count, capacity, ctl->hist_tile[q],
@@ -915,7 +914,8 @@ int enqueue_frame(bgs_ctx* ctx, Lane& L, const FrameInputs& in) {
             mark(4);
             launch_tile_ranges(st, L.inst[0].ptr, ctl, ranges);
             mark(5);
-            launch_raster(st, fp, L.records.ptr, L.inst[0].ptr, ranges, L.fb.ptr, in.view.clear_color, ctl);
+            e = launch_raster(st, fp, p.raster, L.records.ptr, L.inst[0].ptr, ranges, L.fb.ptr, in.view.clear_color, ctl);
+            if (e != hipSuccess) return e;
             mark(6);
         }
         // BINNING_SCAN frames get their sRGB8 image from the rasteriser itself (BGS_DEBUG_SEPARATE_ENCODE: from the

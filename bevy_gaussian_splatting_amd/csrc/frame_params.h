@@ -139,27 +139,84 @@ inline uint32_t canonical_supertile_level(uint32_t level, const uint32_t edges[4
 // of a kind whose saturating tiles hold a good share of the work (KindState::midround) when several frames are in flight.
 // Only the OBB and AABB3D variants at 1 or 4 samples without the bounding-box overlay have the exit, and AABB3D has one
 // exit instantiation (1). Debug flags: BGS_DEBUG_NO_MIDROUND never, BGS_DEBUG_MIDROUND_ALWAYS at any level.
+// trace: the per-tile trace (bgs_set_tile_trace), which exists without a depth buffer, without the overlay, at 1 or 4 samples.
+// RasterInst is the ONE description of an instantiation: plan_frame chooses it (FramePlan::raster), graph_key stores key(),
+// the launchers look it up, and the kernel takes its __launch_bounds__ and RUNS from it with its template arguments.
+#ifndef BGS_MS_WAVES
+// multisampled ellipse variants: 6 since round 6. Round 5's kernel (92-96 VGPRs) spilled 10-25 registers INTO the record loop at
+// 80 and lost 10 %; with the tile id in scalar registers and the interior records in their own loop it is 83-86 and the 3-5
+// registers that spill at 80 are tile set-up values outside the loops: dense 1 M even, scene-like +1.9 %, trained-like +4.5 %
+// frames/s (profiles/r6_experiments/ms_waves_6_ab.txt)
+#define BGS_MS_WAVES 6
+#endif
+#ifndef BGS_DENSE_RUNS_MS
+#define BGS_DENSE_RUNS_MS 2u
+#endif
+#ifndef BGS_DENSE_RUNS
+#define BGS_DENSE_RUNS 1u
+#endif
 struct RasterInst {
     int variant = RV_OBB;
     uint32_t samples = 4;
     bool depth = false, overlay = false;
     int mode = 0;
+    bool trace = false;
+    // The instantiations of raster_scan_kernel that are compiled (72), and the only statement of them: the launchers
+    // (render_kernels.hip) instantiate what exists() admits and refuse everything else.
+    constexpr bool exists() const {
+        if (variant != RV_OBB && variant != RV_AABB3D && variant != RV_SURFEL) return false;
+        if (samples != 1u && samples != 2u && samples != 4u && samples != 8u) return false;
+        const bool plain = !overlay && (samples == 1u || samples == 4u);
+        if (trace && (depth || !plain)) return false;
+        return mode == 0 || (plain && ((mode == 1 && variant != RV_SURFEL) || (mode == 2 && variant == RV_OBB)));
+    }
+    // Runs per XCD of the rasteriser's work order (raster_scan_kernel: RUNS; tile_order_kernel deals out the same shares)
+    constexpr uint32_t runs() const {
+        return variant == RV_SURFEL ? 4u : (mode != 0 ? (samples == 4u ? BGS_DENSE_RUNS_MS : BGS_DENSE_RUNS) : 1u);
+    }
+    // Waves per SIMD (the kernel's __launch_bounds__): 8 for the single-sampled ellipse variants (<= 64 VGPRs), 6 for the surfel
+    // variant; the multisampled instantiations carry six transmittance words per pixel instead of one (5 / 4 waves).
+    constexpr int waves_per_simd() const {
+        const bool surfel = variant == RV_SURFEL;
+        return samples == 8u ? (surfel ? (depth ? 2 : 3) : (depth ? 3 : 4))   // ten transmittance words per pixel; 8 KB of depth samples per wave
+             : samples >= 2u ? (surfel ? (depth ? 3 : 4) : (depth ? 5 : BGS_MS_WAVES)) : (surfel ? (depth ? 5 : 6) : (depth ? 7 : 8));
+    }
+    // one word per instantiation (GraphKey)
+    constexpr uint32_t key() const {
+        return samples | (depth ? 0x100u : 0u) | (overlay ? 0x200u : 0u) | ((uint32_t)mode << 10) | ((uint32_t)variant << 12) | (trace ? 0x4000u : 0u);
+    }
 };
+inline int raster_variant(const FrameParams& fp) { return fp.aabb == 0u ? RV_OBB : (fp.gaussian_mode != 0u ? RV_AABB3D : RV_SURFEL); }
 inline int raster_scan_mode(int variant, uint32_t samples, bool overlay, uint32_t level, bool kind_midround, int pipeline_depth,
                             uint32_t debug_flags) {
     if (variant == RV_SURFEL || (samples != 1u && samples != 4u) || overlay || (debug_flags & BGS_DEBUG_NO_MIDROUND)) return 0;
     if (level < 2u && !(kind_midround && pipeline_depth > 1) && !(debug_flags & BGS_DEBUG_MIDROUND_ALWAYS)) return 0;
     return (level >= 2u || variant == RV_AABB3D) ? 1 : 2;
 }
+// (trace: validate, bgs_frame.hip, refuses it for the frames that have no traced instantiation, so what comes back exists())
 inline RasterInst raster_instantiation(const FrameParams& fp, uint32_t level, bool kind_midround, int pipeline_depth,
-                                       uint32_t debug_flags) {
+                                       uint32_t debug_flags, bool trace) {
     RasterInst r;
-    r.variant = fp.aabb == 0u ? RV_OBB : (fp.gaussian_mode != 0u ? RV_AABB3D : RV_SURFEL);
+    r.variant = raster_variant(fp);
     r.samples = fp.sample_count;
     r.depth = fp.depth_ptr != 0ull;
     r.overlay = fp.visualize_bbox != 0u;
     r.mode = raster_scan_mode(r.variant, r.samples, r.overlay, level, kind_midround, pipeline_depth, debug_flags);
+    r.trace = trace;
     return r;
+}
+
+// The instantiation of the vertex stage (project_kernel / project_emit_kernel, render_kernels.hip) a frame launches: the
+// cloud's format x surfel records x ANY_MODE (another RasterizeMode than Color, or a draw mode). A precomputed-covariance
+// cloud has no rotation and scale, hence no surfels (validate refuses the frame): 10 instantiations of each kernel.
+struct ProjectInst {
+    uint32_t format = CLOUD_F32;
+    bool surfel = false, any_mode = false;
+    constexpr bool exists() const { return format <= CLOUD_COV3D && !(format == CLOUD_COV3D && surfel); }
+    constexpr uint32_t key() const { return format | (surfel ? 0x100u : 0u) | (any_mode ? 0x200u : 0u); }
+};
+inline ProjectInst project_instantiation(const FrameParams& fp, uint32_t cloud_format) {
+    return {cloud_format, raster_variant(fp) == RV_SURFEL, fp.rasterize_mode != RASTERIZE_COLOR || fp.draw_mode != 0u};
 }
 
 // A lane's zeroed-every-frame scratch region for n splats and inst_cap tile instances, every part 256-byte aligned:

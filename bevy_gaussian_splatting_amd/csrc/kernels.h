@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "bgs_device.h"
+#include "frame_params.h"
 
 namespace bgs {
 
@@ -35,7 +36,7 @@ struct CloudPtrs {
 constexpr uint32_t PACK_ROT = 1u, PACK_SCALE_OPACITY = 2u, PACK_SH_F32 = 3u;   // f32
 constexpr uint32_t PACK_COV3D = 1u;                                            // cov3d (2 words), SH at PACK_SH_F32
 constexpr uint32_t PACK_RSO_F16 = 1u, PACK_SH_F16 = 2u;                        // f16
-constexpr uint32_t CLOUD_F32 = 0, CLOUD_F16 = 1, CLOUD_COV3D = 2;
+// (CLOUD_F32, CLOUD_F16, CLOUD_COV3D: bgs_device.h)
 
 // What the rasteriser of a BINNING_SCAN frame tidies up so that the NEXT frame of the same lane needs
 // neither a memset of the scratch region nor a device-to-host copy of the Control block (each a
@@ -173,23 +174,27 @@ hipError_t launch_bucket_sort(hipStream_t stream, const uint2* bucket_slots, uin
 // ctl->splitters = the 255 quantile keys of the sorted draw list (for frames without a cleaning rasteriser).
 void launch_splitters(hipStream_t stream, const uint2* sorted, Control* ctl, uint32_t key_xor, uint32_t sub = 1u);
 
+// The launchers of the templated kernels take the instantiation as the frame plan chose it (ProjectInst, RasterInst:
+// frame_params.h) and look it up; one that does not exist is hipErrorInvalidValue and no launch.
+
 // Vertex stage in front-to-back order + ordered tile-instance emission
-// (vs_points once per splat, src/render/gaussian.wgsl:184-436).
-void launch_project_emit(hipStream_t stream, const FrameParams& fp, const CloudPtrs& cloud,
-                         const uint2* draw_list, const uint2* culled, Control* ctl, unsigned long long* scan_status,
-                         void* records, uint2* instances, uint32_t capacity, uint32_t ticket_slot,
-                         int max_blocks);
+// (vs_points once per splat, src/render/gaussian.wgsl:184-436). inst: project_instantiation(fp, cloud.format).
+hipError_t launch_project_emit(hipStream_t stream, const FrameParams& fp, const ProjectInst& inst, const CloudPtrs& cloud,
+                               const uint2* draw_list, const uint2* culled, Control* ctl, unsigned long long* scan_status,
+                               void* records, uint2* instances, uint32_t capacity, uint32_t ticket_slot,
+                               int max_blocks);
 
 // BINNING_SCAN: the vertex stage in front-to-back order (project_kernel: rank -> record + packed tile rectangle, no
 // ordering between ranks) and the ORDERED coarse binning (bin_kernel: every rank is appended, in rank order, to the list
 // of each supertile (sup_edge x sup_edge tiles) its tile rectangle overlaps; one pass, no sort, no atomics on the data
 // path: the <= 256 supertiles are the "digits" of the same chained-scan look-back the radix sort uses), two launches.
-// d_fp: the device copy of `fp` the kernels read (written by this frame's keygen). rects: 4 bytes per rank.
+// inst: project_instantiation(fp, cloud.format). d_fp: the device copy of `fp` the kernels read (written by this frame's
+// keygen). rects: 4 bytes per rank.
 // wide_bin: the frame is alone on the chip (pipeline depth 1): bin_kernel as 1024-thread workgroups (else 256).
-void launch_project_bin(hipStream_t stream, const FrameParams& fp, const FrameParams* d_fp, const CloudPtrs& cloud,
-                        const uint2* draw_list, const uint2* culled, Control* ctl, uint32_t* bin_status, void* records,
-                        uint32_t* rects, uint32_t* coarse, uint32_t coarse_cap, uint32_t sup_edge,
-                        uint32_t ticket_slot, int project_blocks, int bin_blocks, bool wide_bin);
+hipError_t launch_project_bin(hipStream_t stream, const FrameParams& fp, const ProjectInst& inst, const FrameParams* d_fp,
+                              const CloudPtrs& cloud, const uint2* draw_list, const uint2* culled, Control* ctl, uint32_t* bin_status,
+                              void* records, uint32_t* rects, uint32_t* coarse, uint32_t coarse_cap, uint32_t sup_edge,
+                              uint32_t ticket_slot, int project_blocks, int bin_blocks, bool wide_bin);
 // bin_kernel alone, as launch_project_bin launches it behind project_kernel (and bgs_selftest_bin on rectangles of its
 // own): `blocks` workgroups of 1024 (wide_bin) or 256 threads; sup_mul = supertile_mul(edge), sup_x x sup_y supertiles.
 void launch_bin(hipStream_t stream, const uint32_t* rects, Control* ctl, uint32_t* bin_status, uint32_t* coarse,
@@ -200,13 +205,14 @@ void launch_bin(hipStream_t stream, const uint32_t* rects, Control* ctl, uint32_
 // rectangle contains this tile (order-preserving ballot compaction), stages their records in LDS
 // and composites front-to-back until the tile saturates. With want_srgb8 it also writes the frame as
 // Rgba8UnormSrgb (to d_fp->srgb8_target, else srgb8_default): no separate encode pass for this path.
-void launch_raster_scan(hipStream_t stream, const FrameParams& fp, const FrameParams* d_fp, const void* records,
-                        const uint32_t* coarse, uint32_t coarse_cap,
-                        uint32_t sup_edge, Control* ctl, float4* framebuffer, uint32_t* srgb8_default,
-                        uint32_t out_format, const FrameCleanup& cleanup, uint4* tile_trace = nullptr,
-                        int mode = 0 /* raster_scan_kernel's MODE: 0 plain, 1 dense + mid-round exit, 2 sparse + mid-round exit */,
-                        const uint8_t* heavy_in = nullptr, uint8_t* heavy_out = nullptr,
-                        const uint16_t* order = nullptr, uint16_t* cost_out = nullptr);
+// inst: the instantiation of raster_scan_kernel (raster_instantiation; its mode: 0 plain, 1 dense + mid-round exit, 2 sparse +
+// mid-round exit). tile_trace: what a traced instantiation fills (else unused). heavy_in / heavy_out, order, cost_out: the
+// tile feedback below, each may be null.
+hipError_t launch_raster_scan(hipStream_t stream, const FrameParams& fp, const RasterInst& inst, const FrameParams* d_fp,
+                              const void* records, const uint32_t* coarse, uint32_t coarse_cap,
+                              uint32_t sup_edge, Control* ctl, float4* framebuffer, uint32_t* srgb8_default,
+                              uint32_t out_format, const FrameCleanup& cleanup, uint4* tile_trace,
+                              const uint8_t* heavy_in, uint8_t* heavy_out, const uint16_t* order, uint16_t* cost_out);
 // TileCost: what every tile of a frame cost its wave — records blended, records staged, staging rounds and candidate
 // groups scanned, weighted into eighths of a blended record (render_kernels.hip WORK_*; u16 per tile) — left by the
 // rasteriser (cost_out) for the frames behind it, and the order made of it for a frame's raster workgroups
@@ -216,8 +222,8 @@ void launch_raster_scan(hipStream_t stream, const FrameParams& fp, const FramePa
 // looks heavier than it is). Frames with more tile waves than the chip holds at once (4x multisampling) end earlier
 // for it when they are alone on the chip: the rasteriser of the dense / scene-like 1 M frame 68.4 -> 61.0 / 128 ->
 // 116 us, of the 1 M-surfel frame 662 -> 522 us, of the scene-like 5 M frame 538 -> 504 us
-// (profiles/r4_experiments/tile_order.txt); with frames in flight it is worth under 1 %. `fp` and `midround_exit`
-// pick the share each XCD has in the frame's instantiation (raster_scan_kernel: RUNS). An order stays valid — a
+// (profiles/r4_experiments/tile_order.txt); with frames in flight it is worth under 1 %. `inst` is the frame's
+// instantiation: its runs() is the share each XCD has in it (raster_scan_kernel: RUNS). An order stays valid — a
 // permutation of the workgroups — for as long as the tile grid does, so it is made anew every TILE_ORDER_REFRESH-th
 // frame only (the kernel is a chain of ~40 barriers, ~7 us).
 constexpr uint32_t TILE_ORDER_REFRESH = 8u;
@@ -226,12 +232,9 @@ inline size_t tile_cost_bytes(uint32_t tiles) { return ((size_t)tiles + 4u) * 2u
 // the pair (work of all tiles, work of the tiles that ended saturated) at stats[2 x], stats[2 x + 1] (TileCost units)
 __host__ __device__ inline size_t tile_order_stats_offset(uint32_t tiles) { return (((((size_t)tiles + 3u) / 4u + 8u) * 2u + 63u) / 64u) * 64u; }
 inline size_t tile_order_bytes(uint32_t tiles) { return tile_order_stats_offset(tiles) + 16u * sizeof(uint32_t); }
-void launch_tile_order(hipStream_t stream, const uint16_t* cost, uint16_t* order, uint32_t ntiles, const FrameParams& fp,
-                       bool midround_exit);
+void launch_tile_order(hipStream_t stream, const uint16_t* cost, uint16_t* order, uint32_t ntiles, const RasterInst& inst);
 // the same with the runs per XCD given (1, 2 or 4; bgs_selftest_tile_order)
 void launch_tile_order_runs(hipStream_t stream, const uint16_t* cost, uint16_t* order, uint32_t ntiles, uint32_t runs);
-// tile waves of raster_scan_kernel a SIMD holds at once for this frame's instantiation (its __launch_bounds__)
-int raster_scan_waves_per_simd(const FrameParams& fp);
 // HeavyFeedback: what the rasteriser of a dense frame (midround_exit) leaves for the frames behind it — the tiles that
 // did not saturate inside their first staging round, as a list (for the strip workgroups) and as a flag per tile (for the
 // regular waves, which step aside). One buffer: [count (own 128-byte line) | list u16[HEAVY_CAP] | flag u8[tiles]].
@@ -248,10 +251,10 @@ constexpr uint32_t OUT_SKIP_F32 = 4u;  // do not write the f32 target (bgs_set_p
 void launch_tile_ranges(hipStream_t stream, const uint2* instances, const Control* ctl, uint2* ranges);
 
 // Per-16x16-tile front-to-back blend (fs_main + blend, src/render/gaussian.wgsl:438-505,
-// src/render/mod.rs:944-948).
-void launch_raster(hipStream_t stream, const FrameParams& fp, const void* records,
-                   const uint2* instances, const uint2* ranges, float4* framebuffer,
-                   const float clear_color[4], const Control* ctl);
+// src/render/mod.rs:944-948). Of `inst` its variant, samples, depth and overlay count: raster_kernel has no modes and no trace.
+hipError_t launch_raster(hipStream_t stream, const FrameParams& fp, const RasterInst& inst, const void* records,
+                         const uint2* instances, const uint2* ranges, float4* framebuffer,
+                         const float clear_color[4], const Control* ctl);
 
 // Rgba8UnormSrgb image of the f32 framebuffer (the reference's render-target format).
 // The destination is d_fp->srgb8_target when that is non-zero, else default_out.

@@ -103,6 +103,32 @@ struct ShF16 {
     }
 };
 
+// Runtime values, each from a fixed list, as compile-time constants: with_constants(f, Among<T, Vs...>{v}, ...) calls
+// f(std::integral_constant<T, V>{}, ...) with the V each v equals and returns what f returns; false, and no call, if a v
+// is not in its list. The launchers below look an instantiation (RasterInst, ProjectInst: frame_params.h) up with it and
+// guard the launch with `if constexpr (inst.exists())`: what exists() admits is what the compiler emits.
+template <class T, T... Vs> struct Among { T v; };
+template <class F> bool with_constants(F&& f) { return f(); }
+template <class F, class T, T... Vs, class... Rest>
+bool with_constants(F&& f, const Among<T, Vs...> a, const Rest... rest) {
+    return ((a.v == Vs && with_constants([&](auto... cs) { return f(std::integral_constant<T, Vs>{}, cs...); }, rest...)) || ...);
+}
+using AmongBool = Among<bool, false, true>;
+// f(FMT, SURFEL, ANY_MODE) / f(VARIANT, SAMPLES, DEPTH, OVERLAY, MODE, TRACE) for an instantiation that exists; false if not
+template <class F> bool with_project_inst(const ProjectInst& p, F&& f) {
+    return with_constants([&](auto FMT, auto SURFEL, auto ANY_MODE) {
+        if constexpr (ProjectInst{FMT, SURFEL, ANY_MODE}.exists()) f(FMT, SURFEL, ANY_MODE);
+        return ProjectInst{FMT, SURFEL, ANY_MODE}.exists();
+    }, Among<uint32_t, CLOUD_F32, CLOUD_F16, CLOUD_COV3D>{p.format}, AmongBool{p.surfel}, AmongBool{p.any_mode});
+}
+template <class F> bool with_raster_inst(const RasterInst& r, F&& f) {
+    return with_constants([&](auto VARIANT, auto SAMPLES, auto DEPTH, auto OVERLAY, auto MODE, auto TRACE) {
+        if constexpr (RasterInst{VARIANT, SAMPLES, DEPTH, OVERLAY, MODE, TRACE}.exists()) f(VARIANT, SAMPLES, DEPTH, OVERLAY, MODE, TRACE);
+        return RasterInst{VARIANT, SAMPLES, DEPTH, OVERLAY, MODE, TRACE}.exists();
+    }, Among<int, RV_OBB, RV_AABB3D, RV_SURFEL>{r.variant}, Among<uint32_t, 1u, 2u, 4u, 8u>{r.samples}, AmongBool{r.depth}, AmongBool{r.overlay},
+       Among<int, 0, 1, 2>{r.mode}, AmongBool{r.trace});
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------
@@ -345,31 +371,20 @@ __global__ __launch_bounds__(256) void project_emit_kernel(FrameParams fp, Cloud
     if (tid == 0) publish_color_max(ctl, fmaxf(fmaxf(s_cmag[0], s_cmag[1]), fmaxf(s_cmag[2], s_cmag[3])));
 }
 
-void launch_project_emit(hipStream_t stream, const FrameParams& fp, const CloudPtrs& cloud,
-                         const uint2* draw_list, const uint2* culled, Control* ctl,
-                         unsigned long long* scan_status,
-                         void* records, uint2* instances, uint32_t capacity, uint32_t ticket_slot,
-                         int max_blocks) {
-    if (fp.n == 0) return;
+hipError_t launch_project_emit(hipStream_t stream, const FrameParams& fp, const ProjectInst& inst, const CloudPtrs& cloud,
+                               const uint2* draw_list, const uint2* culled, Control* ctl,
+                               unsigned long long* scan_status,
+                               void* records, uint2* instances, uint32_t capacity, uint32_t ticket_slot,
+                               int max_blocks) {
+    if (fp.n == 0) return hipSuccess;
     const uint32_t blocks = capped_grid(fp.n, 256u, max_blocks);
-    const bool surfel = fp.gaussian_mode == 0u && fp.aabb != 0u;
     float4* rec = (float4*)records;
-    const bool any_mode = fp.rasterize_mode != RASTERIZE_COLOR || fp.draw_mode != 0u;
-#define BGS_LAUNCH_PE(F16, SURFEL, ANY)                                                             \
-    hipLaunchKernelGGL((project_emit_kernel<F16, SURFEL, ANY>), dim3(blocks), dim3(256), 0, stream, \
-                       fp, cloud, draw_list, culled, ctl, scan_status, rec, instances, capacity,    \
-                       ticket_slot)
-#define BGS_LAUNCH_PE2(F16, SURFEL) \
-    do { if (any_mode) BGS_LAUNCH_PE(F16, SURFEL, true); else BGS_LAUNCH_PE(F16, SURFEL, false); } while (0)
-    if (cloud.format == CLOUD_F16) {
-        if (surfel) BGS_LAUNCH_PE2(1, true); else BGS_LAUNCH_PE2(1, false);
-    } else if (cloud.format == CLOUD_COV3D) {
-        BGS_LAUNCH_PE2(2, false);  // 2DGS needs rotation and scale: refused for these clouds (validate)
-    } else {
-        if (surfel) BGS_LAUNCH_PE2(0, true); else BGS_LAUNCH_PE2(0, false);
-    }
-#undef BGS_LAUNCH_PE2
-#undef BGS_LAUNCH_PE
+    const bool found = with_project_inst(inst, [&](auto FMT, auto SURFEL, auto ANY_MODE) {
+        hipLaunchKernelGGL((project_emit_kernel<FMT, SURFEL, ANY_MODE>), dim3(blocks), dim3(256), 0, stream,
+                           fp, cloud, draw_list, culled, ctl, scan_status, rec, instances, capacity,
+                           ticket_slot);
+    });
+    return found ? hipSuccess : hipErrorInvalidValue;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -566,33 +581,23 @@ __global__ __launch_bounds__(64u * WAVES) void bin_kernel(const uint32_t* __rest
     }
 }
 
-void launch_project_bin(hipStream_t stream, const FrameParams& fp, const FrameParams* d_fp, const CloudPtrs& cloud,
-                        const uint2* draw_list, const uint2* culled, Control* ctl, uint32_t* bin_status,
-                        void* records, uint32_t* rects, uint32_t* coarse, uint32_t coarse_cap, uint32_t sup_edge,
-                        uint32_t ticket_slot, int project_blocks, int bin_blocks, bool wide_bin) {
-    if (fp.n == 0) return;
+hipError_t launch_project_bin(hipStream_t stream, const FrameParams& fp, const ProjectInst& inst, const FrameParams* d_fp,
+                              const CloudPtrs& cloud, const uint2* draw_list, const uint2* culled, Control* ctl, uint32_t* bin_status,
+                              void* records, uint32_t* rects, uint32_t* coarse, uint32_t coarse_cap, uint32_t sup_edge,
+                              uint32_t ticket_slot, int project_blocks, int bin_blocks, bool wide_bin) {
+    if (fp.n == 0) return hipSuccess;
     const uint32_t blocks = capped_grid(fp.n, 256u, project_blocks);
     const uint32_t sup = sup_edge, sup_mul = supertile_mul(sup_edge);
     const uint32_t sup_x = ((uint32_t)fp.tiles_x + sup - 1u) / sup, sup_y = ((uint32_t)fp.tiles_y + sup - 1u) / sup;
-    const bool surfel = fp.gaussian_mode == 0u && fp.aabb != 0u;
     float4* rec = (float4*)records;
-    const bool any_mode = fp.rasterize_mode != RASTERIZE_COLOR || fp.draw_mode != 0u;
-#define BGS_LAUNCH_PB(F16, SURFEL, ANY)                                                            \
-    hipLaunchKernelGGL((project_kernel<F16, SURFEL, ANY>), dim3(blocks), dim3(256), 0, stream,     \
-                       d_fp, cloud, draw_list, culled, ctl, rec, rects)
-#define BGS_LAUNCH_PB2(F16, SURFEL) \
-    do { if (any_mode) BGS_LAUNCH_PB(F16, SURFEL, true); else BGS_LAUNCH_PB(F16, SURFEL, false); } while (0)
-    if (cloud.format == CLOUD_F16) {
-        if (surfel) BGS_LAUNCH_PB2(1, true); else BGS_LAUNCH_PB2(1, false);
-    } else if (cloud.format == CLOUD_COV3D) {
-        BGS_LAUNCH_PB2(2, false);  // 2DGS needs rotation and scale: refused for these clouds (validate)
-    } else {
-        if (surfel) BGS_LAUNCH_PB2(0, true); else BGS_LAUNCH_PB2(0, false);
-    }
-#undef BGS_LAUNCH_PB2
-#undef BGS_LAUNCH_PB
+    const bool found = with_project_inst(inst, [&](auto FMT, auto SURFEL, auto ANY_MODE) {
+        hipLaunchKernelGGL((project_kernel<FMT, SURFEL, ANY_MODE>), dim3(blocks), dim3(256), 0, stream,
+                           d_fp, cloud, draw_list, culled, ctl, rec, rects);
+    });
+    if (!found) return hipErrorInvalidValue;
     const uint32_t bblocks = capped_grid(fp.n, BIN_RANKS, bin_blocks);
     launch_bin(stream, rects, ctl, bin_status, coarse, coarse_cap, sup_mul, sup_x, sup_y, ticket_slot, bblocks, wide_bin);
+    return hipSuccess;
 }
 
 void launch_bin(hipStream_t stream, const uint32_t* rects, Control* ctl, uint32_t* bin_status, uint32_t* coarse,
@@ -1573,16 +1578,6 @@ constexpr uint32_t WORK_BLENDED = 8u, WORK_STAGED = 1u, WORK_ROUND = 40u, WORK_G
 #else
 #define BGS_PHASE(i) do { } while (0)
 #endif
-#ifndef BGS_DENSE_RUNS_MS
-#define BGS_DENSE_RUNS_MS 2u
-#endif
-#ifndef BGS_DENSE_RUNS
-#define BGS_DENSE_RUNS 1u
-#endif
-// contiguous runs of workgroups per XCD (raster_scan_kernel: RUNS)
-constexpr uint32_t raster_runs(const int variant, const int msaa, const bool midround_exit) {
-    return variant == RV_SURFEL ? 4u : (midround_exit ? (msaa == 4 ? BGS_DENSE_RUNS_MS : BGS_DENSE_RUNS) : 1u);
-}
 // Which group of four tiles workgroup b of n draws when nothing is known about the frame (RUNS: see raster_scan_kernel)
 template <uint32_t RUNS>
 __device__ __forceinline__ uint32_t raster_block_item(const uint32_t b, const uint32_t n) {
@@ -2041,28 +2036,12 @@ __device__ __forceinline__ uint32_t raster_tile(const FrameParams& fp, const flo
     return rounds | (tile_saturated ? 0x80000000u : 0u);   // (bit 31: the tile ended saturated)
 }
 
-// Waves per SIMD: 8 for the single-sampled ellipse variants (<= 64 VGPRs), 6 for the surfel variant; the multisampled
-// instantiations carry six transmittance words per pixel instead of one (5 / 4 waves).
-#ifndef BGS_MS_WAVES
-// multisampled ellipse variants: 6 since round 6. Round 5's kernel (92-96 VGPRs) spilled 10-25 registers INTO the record loop at
-// 80 and lost 10 %; with the tile id in scalar registers and the interior records in their own loop it is 83-86 and the 3-5
-// registers that spill at 80 are tile set-up values outside the loops: dense 1 M even, scene-like +1.9 %, trained-like +4.5 %
-// frames/s (profiles/r6_experiments/ms_waves_6_ab.txt)
-#define BGS_MS_WAVES 6
-#endif
-constexpr int raster_waves_per_simd(const int variant, const int msaa, const bool depth) {
-    return msaa == 8 ? (variant == 2 ? (depth ? 2 : 3) : (depth ? 3 : 4))   // ten transmittance words per pixel; 8 KB of depth samples per wave
-         : msaa >= 2 ? (variant == 2 ? (depth ? 3 : 4) : (depth ? 5 : BGS_MS_WAVES)) : (variant == 2 ? (depth ? 5 : 6) : (depth ? 7 : 8));
-}
-int raster_scan_waves_per_simd(const FrameParams& fp) {
-    const int variant = fp.aabb == 0u ? RV_OBB : (fp.gaussian_mode != 0u ? RV_AABB3D : RV_SURFEL);
-    return raster_waves_per_simd(variant, (int)fp.sample_count, fp.depth_ptr != 0ull);
-}
+// (waves per SIMD and RUNS: RasterInst::waves_per_simd / runs, frame_params.h, of the instantiation the template arguments name)
 // MODE (round 6; a bool until then): 0 the plain instantiation; 1 mid-round exit for DENSE frames (supertile level >= 2: heavy-tile
 // strips, no strip reach masks, no staged sample offsets — each of them only costs there); 2 mid-round exit for frames of a kind
 // whose saturating tiles hold the work at a lower level (trained-like): the sparse frames' machinery plus the exit
 template <int VARIANT, bool TRACE = false, int MODE = 0, int MSAA = 1, bool DEPTH = false, bool BBOX = false>
-__global__ __launch_bounds__(256, raster_waves_per_simd(VARIANT, MSAA, DEPTH)) void raster_scan_kernel(const FrameParams* __restrict__ fpp, const float4* __restrict__ records,
+__global__ __launch_bounds__(256, (RasterInst{VARIANT, (uint32_t)MSAA, DEPTH, BBOX, MODE, TRACE}.waves_per_simd())) void raster_scan_kernel(const FrameParams* __restrict__ fpp, const float4* __restrict__ records,
                                                           const uint32_t* __restrict__ coarse,
                                                           uint32_t coarse_cap, uint32_t sup_mul,
                                                           uint32_t sup_x, Control* ctl,
@@ -2099,7 +2078,7 @@ __global__ __launch_bounds__(256, raster_waves_per_simd(VARIANT, MSAA, DEPTH)) v
     // 1 / 2 / 4: rasteriser alone 61.3 / 57.8 / 58.0 us, frames in flight 15.9 / 16.3 / 16.1 k frames/s (5 M dense: 49.8 /
     // 47.2 / 47.6 us, in flight the same); single-sampled 45.2 / 44.4 / 46.4 us and no change in flight: one band kept
     // (profiles/r4_experiments/tile_order.txt).
-    constexpr uint32_t RUNS = raster_runs(VARIANT, MSAA, MIDROUND_EXIT);
+    constexpr uint32_t RUNS = RasterInst{VARIANT, (uint32_t)MSAA, DEPTH, BBOX, MODE, TRACE}.runs();
     // `order` (tile_order_kernel): this frame's workgroups in the order of the work a completed frame found in them,
     // heaviest first inside every XCD's share — the same share xcd_remap / xcd_remap_runs deal out
     uint32_t tile = strip_block ? 0xFFFFFFFFu
@@ -2275,10 +2254,8 @@ __global__ __launch_bounds__(256) void tile_order_kernel(const uint16_t* __restr
         order[8u * i + x] = (uint16_t)raster_block_item<RUNS>(8u * (s_key[i] & 0xFFFFu) + x, nblocks);
 }
 
-void launch_tile_order(hipStream_t stream, const uint16_t* cost, uint16_t* order, uint32_t ntiles, const FrameParams& fp,
-                       bool midround_exit) {
-    const int variant = fp.aabb == 0u ? RV_OBB : (fp.gaussian_mode != 0u ? RV_AABB3D : RV_SURFEL);
-    launch_tile_order_runs(stream, cost, order, ntiles, raster_runs(variant, (int)fp.sample_count, midround_exit));
+void launch_tile_order(hipStream_t stream, const uint16_t* cost, uint16_t* order, uint32_t ntiles, const RasterInst& inst) {
+    launch_tile_order_runs(stream, cost, order, ntiles, inst.runs());
 }
 
 void launch_tile_order_runs(hipStream_t stream, const uint16_t* cost, uint16_t* order, uint32_t ntiles, uint32_t runs) {
@@ -2289,90 +2266,40 @@ void launch_tile_order_runs(hipStream_t stream, const uint16_t* cost, uint16_t* 
     else hipLaunchKernelGGL((tile_order_kernel<1u>), dim3(8), dim3(256), 0, stream, cost, order, nblocks, ntiles);
 }
 
-void launch_raster_scan(hipStream_t stream, const FrameParams& fp, const FrameParams* d_fp, const void* records,
-                        const uint32_t* coarse, uint32_t coarse_cap,
-                        uint32_t sup_edge, Control* ctl, float4* framebuffer, uint32_t* srgb8_default,
-                        uint32_t out_format, const FrameCleanup& cleanup, uint4* tile_trace, int mode,
-                        const uint8_t* heavy_in, uint8_t* heavy_out, const uint16_t* order, uint16_t* cost_out) {
+// The instantiation is the caller's choice (raster_instantiation, frame_params.h); one that does not exist (RasterInst::exists)
+// is refused, nothing launched. The strip workgroups behind the regular grid come with a mid-round-exit mode and heavy_in.
+hipError_t launch_raster_scan(hipStream_t stream, const FrameParams& fp, const RasterInst& inst, const FrameParams* d_fp,
+                              const void* records, const uint32_t* coarse, uint32_t coarse_cap,
+                              uint32_t sup_edge, Control* ctl, float4* framebuffer, uint32_t* srgb8_default,
+                              uint32_t out_format, const FrameCleanup& cleanup, uint4* tile_trace,
+                              const uint8_t* heavy_in, uint8_t* heavy_out, const uint16_t* order, uint16_t* cost_out) {
     const uint32_t ntiles = (uint32_t)(fp.tiles_x * fp.tiles_y);
-    if (ntiles == 0) return;
+    if (ntiles == 0) return hipSuccess;
     const float4* rec = (const float4*)records;
     const uint32_t sup = sup_edge, sup_mul = supertile_mul(sup_edge);
     const uint32_t sup_x = ((uint32_t)fp.tiles_x + sup - 1u) / sup;
-    // instantiations: variant x mid-round exit x samples per pixel; the per-tile trace exists for the variants without a
-    // depth buffer, the depth test for the untraced ones. Sample2 / Sample8 and the bounding-box overlay (debug features:
-    // nothing in the reference selects them by default) come untraced and without the mid-round exit only, surfels without
-    // the exit, AABB3D with one exit instantiation (mode 1): the caller (raster_instantiation, frame_params.h) asks for
-    // nothing else, and passes heavy-tile buffers with mode 1 only.
-    const bool depth = fp.depth_ptr != 0ull, bbox = fp.visualize_bbox != 0u;
-    const uint32_t ms = fp.sample_count;
-    const bool plain = (ms == 1u || ms == 4u) && !bbox;
-#define BGS_LAUNCH_RS4(V, X, TR, MS, DP, BB)                                                      \
-    hipLaunchKernelGGL((raster_scan_kernel<V, TR, X, MS, DP, BB>), dim3(grid), dim3(256), 0, stream, d_fp, rec, coarse,      \
-                       coarse_cap, sup_mul, sup_x, ctl, framebuffer, srgb8_default, out_format, cleanup, (TR) ? tile_trace : (uint4*)nullptr, heavy_in, heavy_out, order, cost_out)
-#define BGS_LAUNCH_RS(V, X)                                                                       \
-    do {                                                                                          \
-        const uint32_t grid = (ntiles + 3u) / 4u + ((X) && heavy_in ? HEAVY_CAP : 0u);            \
-        const bool msaa4 = ms == 4u;                                                              \
-        if (depth) { if (msaa4) BGS_LAUNCH_RS4(V, X, false, 4, true, false); else BGS_LAUNCH_RS4(V, X, false, 1, true, false); } \
-        else if (tile_trace) { if (msaa4) BGS_LAUNCH_RS4(V, X, true, 4, false, false); else BGS_LAUNCH_RS4(V, X, true, 1, false, false); } \
-        else { if (msaa4) BGS_LAUNCH_RS4(V, X, false, 4, false, false); else BGS_LAUNCH_RS4(V, X, false, 1, false, false); } \
-    } while (0)
-    // the rarely used instantiations: V x samples {1, 2, 4, 8} x depth x overlay, minus the plain ones above
-#define BGS_LAUNCH_RSX(V)                                                                         \
-    do {                                                                                          \
-        const uint32_t grid = (ntiles + 3u) / 4u;                                                 \
-        if (bbox) {                                                                               \
-            if (depth) { if (ms == 1u) BGS_LAUNCH_RS4(V, false, false, 1, true, true); else if (ms == 2u) BGS_LAUNCH_RS4(V, false, false, 2, true, true); \
-                         else if (ms == 4u) BGS_LAUNCH_RS4(V, false, false, 4, true, true); else BGS_LAUNCH_RS4(V, false, false, 8, true, true); } \
-            else { if (ms == 1u) BGS_LAUNCH_RS4(V, false, false, 1, false, true); else if (ms == 2u) BGS_LAUNCH_RS4(V, false, false, 2, false, true); \
-                   else if (ms == 4u) BGS_LAUNCH_RS4(V, false, false, 4, false, true); else BGS_LAUNCH_RS4(V, false, false, 8, false, true); } \
-        } else {                                                                                  \
-            if (depth) { if (ms == 2u) BGS_LAUNCH_RS4(V, false, false, 2, true, false); else BGS_LAUNCH_RS4(V, false, false, 8, true, false); } \
-            else { if (ms == 2u) BGS_LAUNCH_RS4(V, false, false, 2, false, false); else BGS_LAUNCH_RS4(V, false, false, 8, false, false); } \
-        }                                                                                         \
-    } while (0)
-    if (!plain) {
-        if (fp.aabb == 0u) BGS_LAUNCH_RSX(RV_OBB);
-        else if (fp.gaussian_mode != 0u) BGS_LAUNCH_RSX(RV_AABB3D);
-        else BGS_LAUNCH_RSX(RV_SURFEL);
-    }
-    else if (fp.aabb == 0u) { if (mode == 1) BGS_LAUNCH_RS(RV_OBB, 1); else if (mode == 2) BGS_LAUNCH_RS(RV_OBB, 2); else BGS_LAUNCH_RS(RV_OBB, 0); }
-    else if (fp.gaussian_mode != 0u) { if (mode == 1) BGS_LAUNCH_RS(RV_AABB3D, 1); else BGS_LAUNCH_RS(RV_AABB3D, 0); }   // (no interior path: one exit instantiation)
-    else BGS_LAUNCH_RS(RV_SURFEL, 0);
-#undef BGS_LAUNCH_RSX
-#undef BGS_LAUNCH_RS
-#undef BGS_LAUNCH_RS4
+    const uint32_t grid = (ntiles + 3u) / 4u + (inst.mode != 0 && heavy_in ? HEAVY_CAP : 0u);
+    const bool found = with_raster_inst(inst, [&](auto VARIANT, auto SAMPLES, auto DEPTH, auto OVERLAY, auto MODE, auto TRACE) {
+        hipLaunchKernelGGL((raster_scan_kernel<VARIANT, TRACE, MODE, SAMPLES, DEPTH, OVERLAY>), dim3(grid), dim3(256), 0, stream, d_fp, rec, coarse,
+                           coarse_cap, sup_mul, sup_x, ctl, framebuffer, srgb8_default, out_format, cleanup, TRACE ? tile_trace : (uint4*)nullptr,
+                           heavy_in, heavy_out, order, cost_out);
+    });
+    return found ? hipSuccess : hipErrorInvalidValue;
 }
 
-void launch_raster(hipStream_t stream, const FrameParams& fp, const void* records,
-                   const uint2* instances, const uint2* ranges, float4* framebuffer,
-                   const float clear_color[4], const Control* ctl) {
+// (the instantiations of raster_kernel: what exists of `inst` with mode 0 and no trace)
+hipError_t launch_raster(hipStream_t stream, const FrameParams& fp, const RasterInst& inst, const void* records,
+                         const uint2* instances, const uint2* ranges, float4* framebuffer,
+                         const float clear_color[4], const Control* ctl) {
     const uint32_t ntiles = (uint32_t)(fp.tiles_x * fp.tiles_y);
-    if (ntiles == 0) return;
+    if (ntiles == 0) return hipSuccess;
     const float4 clear = make_float4(clear_color[0], clear_color[1], clear_color[2], clear_color[3]);
     const float4* rec = (const float4*)records;
-    const bool depth = fp.depth_ptr != 0ull, bbox = fp.visualize_bbox != 0u;
-    const uint32_t ms = fp.sample_count;
-#define BGS_LAUNCH_R(V, MS, DP, BB)                                                                                     \
-    hipLaunchKernelGGL((raster_kernel<V, MS, DP, BB>), dim3(ntiles), dim3(256), 0, stream, fp, rec, instances, ranges, \
-                       framebuffer, clear, ctl)
-#define BGS_LAUNCH_R3(V, MS)                                                                      \
-    do {                                                                                          \
-        if (bbox) { if (depth) BGS_LAUNCH_R(V, MS, true, true); else BGS_LAUNCH_R(V, MS, false, true); }   \
-        else { if (depth) BGS_LAUNCH_R(V, MS, true, false); else BGS_LAUNCH_R(V, MS, false, false); }      \
-    } while (0)
-#define BGS_LAUNCH_R2(V)                                                                          \
-    do {                                                                                          \
-        if (ms == 4u) BGS_LAUNCH_R3(V, 4); else if (ms == 1u) BGS_LAUNCH_R3(V, 1);               \
-        else if (ms == 2u) BGS_LAUNCH_R3(V, 2); else BGS_LAUNCH_R3(V, 8);                        \
-    } while (0)
-    if (fp.aabb == 0u) BGS_LAUNCH_R2(RV_OBB);
-    else if (fp.gaussian_mode != 0u) BGS_LAUNCH_R2(RV_AABB3D);
-    else BGS_LAUNCH_R2(RV_SURFEL);
-#undef BGS_LAUNCH_R2
-#undef BGS_LAUNCH_R3
-#undef BGS_LAUNCH_R
+    const bool found = with_raster_inst({inst.variant, inst.samples, inst.depth, inst.overlay}, [&](auto VARIANT, auto SAMPLES, auto DEPTH, auto OVERLAY, auto, auto) {
+        hipLaunchKernelGGL((raster_kernel<VARIANT, SAMPLES, DEPTH, OVERLAY>), dim3(ntiles), dim3(256), 0, stream, fp, rec, instances, ranges,
+                           framebuffer, clear, ctl);
+    });
+    return found ? hipSuccess : hipErrorInvalidValue;
 }
 
 // ---------------------------------------------------------------------------------------

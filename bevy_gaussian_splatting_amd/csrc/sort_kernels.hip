@@ -391,7 +391,8 @@ __global__ __launch_bounds__(THREADS, (THREADS == 1024 && ORDERED) ? 8 : 1) void
                 if (tile > 0u) {
                     if (lane == 0) st_agent(my_status, STATUS_AGGREGATE | total);
                     // (a sort mode that draws every splat — Rayon / Std / None — has full tiles before this one: no chain to
-                    // walk, 12 of the 83 us of a 5 M-splat keygen; the status words are written all the same)
+                    // walk, 12 of the 83 us of a 5 M-splat keygen. Nothing reads the status words in this mode: the tiles that
+                    // get here write theirs, a bucket frame's full tiles, which take the short cut above, write none)
                     excl = all_draw ? tile * per_tile : lookback_wave(part_status, tile, lane, &ctl->error, 8u);
                 }
                 if (lane == 0) {

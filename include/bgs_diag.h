@@ -246,7 +246,7 @@ int bgs_selftest_keygen_buckets(bgs_ctx* ctx, const bgs_cloud* cloud, const bgs_
  *                      of them, 32 per axis);
  *   sample_count       1, 2, 4 or 8; variant 0 OBB, 1 AABB3D, 2 surfel; overlay 0 / 1 (the bounding-box overlay);
  *   mode               raster_scan_kernel's MODE: 0 plain, 1 dense + mid-round exit, 2 sparse + mid-round exit. Refused when
- *                      raster_scan_mode (csrc/frame_params.h) never gives it for the variant, samples and overlay;
+ *                      no such instantiation is built for the variant, samples and overlay (RasterInst::exists, csrc/frame_params.h);
  *   viewport_w / _h    FrameParams::viewport_w / _h (the surfel variant's aspect); clear[4]; color_max_bits: what
  *                      Control::color_max_bits holds (the bits of the frame's largest colour magnitude: the cut-off);
  *   records            record_count records of 48 bytes (OBB, AABB3D: Record) or 96 (surfel: RecordSurfel), csrc/bgs_device.h;

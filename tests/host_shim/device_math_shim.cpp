@@ -76,6 +76,36 @@ int shim_raster_scan_mode(int variant, uint32_t samples, int overlay, uint32_t l
                           uint32_t debug_flags) {
     return raster_scan_mode(variant, samples, overlay != 0, level, kind_midround != 0, pipeline_depth, debug_flags);
 }
+// RasterInst / ProjectInst (frame_params.h): the instantiations that are compiled, and what the kernel takes from one
+static RasterInst raster_inst(int variant, uint32_t samples, int depth, int overlay, int mode, int trace) {
+    return RasterInst{variant, samples, depth != 0, overlay != 0, mode, trace != 0};
+}
+int shim_raster_inst_exists(int variant, uint32_t samples, int depth, int overlay, int mode, int trace) {
+    return raster_inst(variant, samples, depth, overlay, mode, trace).exists() ? 1 : 0;
+}
+uint32_t shim_raster_inst_runs(int variant, uint32_t samples, int depth, int overlay, int mode, int trace) {
+    return raster_inst(variant, samples, depth, overlay, mode, trace).runs();
+}
+int shim_raster_inst_waves(int variant, uint32_t samples, int depth, int overlay, int mode, int trace) {
+    return raster_inst(variant, samples, depth, overlay, mode, trace).waves_per_simd();
+}
+uint32_t shim_raster_inst_key(int variant, uint32_t samples, int depth, int overlay, int mode, int trace) {
+    return raster_inst(variant, samples, depth, overlay, mode, trace).key();
+}
+int shim_project_inst_exists(uint32_t format, int surfel, int any_mode) { return ProjectInst{format, surfel != 0, any_mode != 0}.exists() ? 1 : 0; }
+// raster_instantiation for a frame of these settings: out = variant, samples, depth, overlay, mode, trace
+void shim_raster_instantiation(uint32_t aabb, uint32_t gaussian_mode, uint32_t samples, int depth, int overlay, uint32_t level, int kind_midround,
+                               int pipeline_depth, uint32_t debug_flags, int trace, int32_t out[6]) {
+    FrameParams fp{};
+    fp.aabb = aabb;
+    fp.gaussian_mode = gaussian_mode;
+    fp.sample_count = samples;
+    fp.depth_ptr = depth ? 16ull : 0ull;
+    fp.visualize_bbox = overlay ? 1u : 0u;
+    const RasterInst r = raster_instantiation(fp, level, kind_midround != 0, pipeline_depth, debug_flags, trace != 0);
+    const int32_t v[6] = {r.variant, (int32_t)r.samples, r.depth ? 1 : 0, r.overlay ? 1 : 0, r.mode, r.trace ? 1 : 0};
+    memcpy(out, v, sizeof v);
+}
 
 // the scratch layout of a lane (frame_params.h), as 11 x u64 + 2 x u32
 void shim_scratch_layout(uint32_t n, uint64_t inst_cap, ScratchLayout* out) { *out = scratch_layout(n, inst_cap); }

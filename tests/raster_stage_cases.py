@@ -833,8 +833,8 @@ def mixed_records(variant, n=200, seed=5, w=64, h=48):
 
 
 def instantiations():
-    """(variant, samples, depth, overlay, mode) of every instantiation launch_raster_scan dispatches, as far as raster_scan_mode
-    (csrc/frame_params.h) allows the mode: the exit instantiations exist for OBB (1, 2) and AABB3D (1) at 1 or 4 samples without overlay."""
+    """(variant, samples, depth, overlay, mode) of every untraced instantiation of raster_scan_kernel that RasterInst::exists
+    (csrc/frame_params.h) admits: the exit instantiations exist for OBB (1, 2) and AABB3D (1) at 1 or 4 samples without overlay."""
     out = []
     for variant in (OBB, AABB3D, SURFEL):
         for S in (1, 2, 4, 8):

@@ -224,6 +224,89 @@ def test_rasteriser_instantiation_choice():
     assert mode(OBB, level=0, flags=MIDROUND_ALWAYS) == 2 and mode(OBB, level=2, flags=MIDROUND_ALWAYS) == 1
 
 
+def test_the_compiled_instantiations_are_what_exists_says():
+    """frame_params.h RasterInst::exists / ProjectInst::exists, the set the launchers instantiate: 72 of raster_scan_kernel,
+    of which the 60 untraced ones are raster_stage_cases.instantiations() and the other 12 the traced ones; 10 of the vertex
+    stage, the inst_* cases of vertex_stage_cases. key() tells every one of them from the others."""
+    import helpers as H
+    import raster_stage_cases as C
+    import vertex_stage_cases as VC
+    sh = H.shim()
+    exist = [(v, s, d, o, m, t) for v in (0, 1, 2) for s in (1, 2, 4, 8) for d in (0, 1) for o in (0, 1) for t in (0, 1) for m in (0, 1, 2)
+             if sh.shim_raster_inst_exists(v, s, d, o, m, t)]
+    assert len(exist) == 72
+    untraced = {(v, s, bool(d), o, m) for v, s, d, o, m, t in exist if not t}
+    assert len(untraced) == 60 and untraced == set(C.instantiations())
+    traced = [(v, s, m) for v, s, d, o, m, t in exist if t]
+    assert len(traced) == 12 and all(not d and not o for v, s, d, o, m, t in exist if t)
+    assert sorted(traced) == sorted((v, s, m) for v, modes in ((0, (0, 1, 2)), (1, (0, 1)), (2, (0,))) for s in (1, 4) for m in modes)
+    for bad in ((3, 4, 0, 0, 0, 0), (-1, 4, 0, 0, 0, 0), (0, 3, 0, 0, 0, 0), (0, 16, 0, 0, 0, 0), (0, 0, 0, 0, 0, 0), (0, 4, 0, 0, 3, 0), (0, 4, 0, 0, -1, 0)):
+        assert not sh.shim_raster_inst_exists(*bad), bad
+    assert len({sh.shim_raster_inst_key(*i) for i in exist}) == 72
+    project = {(f, surfel, any_mode) for f in (0, 1, 2) for surfel in (0, 1) for any_mode in (0, 1) if sh.shim_project_inst_exists(f, surfel, any_mode)}
+    assert len(project) == 10 and not sh.shim_project_inst_exists(3, 0, 0)
+    named = {(("f32", "f16", "cov3d").index(fmt), int(shape == "surfel"), int(mode == "any"))
+             for fmt, shape, mode in (n[len("inst_"):].split("_") for n in VC.CASE_NAMES if n.startswith("inst_"))}
+    assert named == project
+
+
+def test_every_admitted_frame_gets_an_instantiation_that_exists():
+    """raster_instantiation over every input validate (bgs_frame.hip) admits — the per-tile trace only without a depth
+    buffer, without the overlay, at 1 or 4 samples — at every supertile level, either verdict of the kind, one frame or
+    several in flight and the debug flags that force the choice: what it returns exists(), so the launchers' refusal of an
+    instantiation that does not exist cannot be reached from a frame."""
+    import ctypes
+    import helpers as H
+    sh = H.shim()
+    NO_MIDROUND, MIDROUND_ALWAYS = 0x1000000, 0x20000
+    out = (ctypes.c_int32 * 6)()
+    seen = set()
+    for variant, (aabb, gaussian_mode) in ((0, (0, 1)), (0, (0, 0)), (1, (1, 1)), (2, (1, 0))):
+        for samples in (1, 2, 4, 8):
+            for depth in (0, 1):
+                for overlay in (0, 1):
+                    for trace in ((0, 1) if not depth and not overlay and samples in (1, 4) else (0,)):
+                        for level in range(4):
+                            for kind in (0, 1):
+                                for pipeline in (1, 4):
+                                    for flags in (0, NO_MIDROUND, MIDROUND_ALWAYS):
+                                        sh.shim_raster_instantiation(aabb, gaussian_mode, samples, depth, overlay, level, kind, pipeline, flags, trace, out)
+                                        assert list(out)[:4] == [variant, samples, depth, overlay] and out[5] == trace
+                                        assert out[4] == sh.shim_raster_scan_mode(variant, samples, overlay, level, kind, pipeline, flags)
+                                        assert sh.shim_raster_inst_exists(*out), list(out)
+                                        seen.add(tuple(out))
+    assert len(seen) == 72   # and every instantiation that is compiled is one a frame can ask for
+
+
+def test_rasteriser_waves_and_runs_per_instantiation():
+    """RasterInst::waves_per_simd (raster_scan_kernel's __launch_bounds__, and what plan_frame compares a frame's tile waves
+    with) and RasterInst::runs (the kernel's RUNS, and the share of an XCD launch_tile_order deals out), against the tables
+    of the default build (BGS_MS_WAVES 6, BGS_DENSE_RUNS 1, BGS_DENSE_RUNS_MS 2). Neither depends on overlay or trace."""
+    import helpers as H
+    sh = H.shim()
+    OBB, AABB3D, SURFEL = 0, 1, 2
+    #        samples:  1       2       4       8        (without, with a depth buffer)
+    waves = {OBB:    ((8, 7), (6, 5), (6, 5), (4, 3)),
+             AABB3D: ((8, 7), (6, 5), (6, 5), (4, 3)),
+             SURFEL: ((6, 5), (4, 3), (4, 3), (3, 2))}
+    for v in (OBB, AABB3D, SURFEL):
+        for si, s in enumerate((1, 2, 4, 8)):
+            for d in (0, 1):
+                assert {sh.shim_raster_inst_waves(v, s, d, o, 0, t) for o in (0, 1) for t in (0, 1)} == {waves[v][si][d]}, (v, s, d)
+                if v != SURFEL and s in (1, 4):
+                    assert sh.shim_raster_inst_waves(v, s, d, 0, 1, 0) == waves[v][si][d]
+    #       (samples, exit):  (1, no) (1, exit) (4, no) (4, exit)
+    runs = {OBB:    (1, 1, 1, 2),
+            AABB3D: (1, 1, 1, 2),
+            SURFEL: (4, 4, 4, 4)}
+    for v in (OBB, AABB3D, SURFEL):
+        got = tuple(sh.shim_raster_inst_runs(v, s, 0, 0, m, 0) for s in (1, 4) for m in (0, 1))
+        assert got == runs[v], (v, got)
+        for s in (1, 4):
+            assert sh.shim_raster_inst_runs(v, s, 0, 0, 2, 0) == sh.shim_raster_inst_runs(v, s, 0, 0, 1, 0)   # either exit mode
+            assert {sh.shim_raster_inst_runs(v, s, d, 0, 0, t) for d in (0, 1) for t in (0, 1)} == {runs[v][0 if s == 1 else 2]}
+
+
 def test_splitter_tables_are_only_accepted_when_ascending():
     """bucket(key) = number of splitters <= key orders the buckets only for an ascending table."""
     import ctypes
