@@ -36,6 +36,7 @@ from .settings import (
 from .io_ply import parse_ply_3d, write_ply_3d
 from .io_gcloud import decode_gcloud, encode_gcloud, read_gcloud, write_gcloud
 from .sort_policy import SortConfig, SortTrigger, update_sort_trigger
+from .bounds import bounds_reference
 from .particles import (
     PARTICLE_BEHAVIOR_DTYPE,
     ParticleBehaviors,
@@ -94,4 +95,5 @@ __all__ = [
     "GaussianInterpolator", "interpolate_reference", "interpolation_factor",
     "PlaybackMode", "playback_update", "MorphPair", "ResidentCloud4d",
     "color_attachment_offset", "composite_reference",
+    "bounds_reference",
 ]

@@ -60,6 +60,12 @@ struct bgs_cloud {
     CloudPtrs ptrs{};
     bgs_host::DeviceBuffer<uint8_t> positions, packed;   // what ptrs.position_visibility and ptrs.packed point at
     uint64_t bytes = 0;
+    // The cloud's own box (BGS_BOUNDS_CLOUD, bounds_math.h): the six device words the reduction merges into, and what the
+    // host read back and decoded from them. A cache of what the positions say, hence mutable: uploads leave it invalid and
+    // the first frame or sort that asks fills it (cloud_bounds, bgs_frame.hip); a particle step invalidates it again.
+    mutable bgs_host::DeviceBuffer<uint32_t> bounds_words;
+    mutable float bounds_min[3] = {0.0f, 0.0f, 0.0f}, bounds_max[3] = {0.0f, 0.0f, 0.0f};
+    mutable bool bounds_valid = false;
 };
 
 namespace bgs_host {
@@ -118,6 +124,10 @@ struct FrameInputs {
     uint64_t kind = 0;                  // frame_kind() (0: a bgs_sort)
     bool force_passes = false;          // the digit passes, not the bucket sort: a re-run of a frame whose bucket sort gave up
     uint32_t grid_cap = 0;              // bgs_set_grid_cap as it was when the frame was enqueued (0: off): a re-run keeps its grids
+    // BGS_BOUNDS_CLOUD (bgs_settings.reserved[0]) on a cloud that has splats: the cloud's own box as it was when the frame
+    // was enqueued, which plan_frame puts in the place of settings.position_min / _max (a re-run draws the same frame)
+    bool cloud_bounds = false;
+    float pos_min[3] = {0.0f, 0.0f, 0.0f}, pos_max[3] = {0.0f, 0.0f, 0.0f};
 };
 
 // Every choice of one frame (plan_frame, bgs_frame.hip): enqueue_frame allocates, binds and issues it, finish_lane reads
@@ -351,6 +361,7 @@ int enqueue_frame(bgs_ctx* ctx, Lane& L, const FrameInputs& in);
 int ensure_entries(bgs_ctx* ctx, Lane& L, uint32_t n);
 int run(bgs_ctx* ctx, const bgs_cloud* cloud, const bgs_view* view, const bgs_settings* s, bool render);   // bgs_sort / bgs_render
 int apply_particle_step(bgs_ctx* ctx, bgs_cloud* cloud, void* behaviors, uint32_t count, float dt);        // bgs_cloud_apply_particle_behaviors
+int cloud_bounds(bgs_ctx* ctx, const bgs_cloud* cloud);        // BGS_BOUNDS_CLOUD: the cloud's box is valid behind it (reduced on the device if it was not)
 extern int g_queue_holders_mode;           // bgs_set_queue_holders
 extern std::mutex g_queue_holders_mutex;
 }  // namespace bgs_host

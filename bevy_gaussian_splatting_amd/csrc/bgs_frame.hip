@@ -3,6 +3,7 @@
 // every rule that writes it, is AdaptiveState (adaptive_state.h): this file calls the rules and reads the state.
 // (The comment at the top of bgs_api.hip is the overview.)
 #include "bgs_context.h"
+#include "bounds_math.h"
 
 thread_local std::string bgs_host::g_error;
 
@@ -233,6 +234,10 @@ int validate(bgs_ctx* ctx, const bgs_cloud* cloud, const bgs_view* view, const b
     if (s->draw_mode > BGS_DRAW_HIGHLIGHT_SELECTED) return fail(ctx, BGS_EINVAL, "unknown draw_mode");
     if (s->rasterize_mode == BGS_RASTERIZE_CLASSIFICATION && s->num_classes == 0)
         return fail(ctx, BGS_EINVAL, "num_classes must be >= 1");
+    // whose CloudUniform.min / .max the frame gets (bgs.h: BGS_BOUNDS_*): the caller's, or the cloud's own box
+    if (s->reserved[0] > BGS_BOUNDS_CLOUD)
+        return fail(ctx, BGS_EINVAL, "bgs_settings.reserved[0] must be BGS_BOUNDS_CALLER (0) or BGS_BOUNDS_CLOUD (1); got " +
+                                         std::to_string(s->reserved[0]));
     // the camera's chunk of sorted entries on the device: bgs_sort's second output, bgs_render's draw order
     if (view->entries_device_ptr) {
         if (view->entries_device_ptr % sizeof(bgs_sort_entry) != 0u)
@@ -522,6 +527,10 @@ FramePlan plan_frame(const bgs_ctx& ctx, const Lane& L, const FrameInputs& in) {
     const bgs_settings* s = &in.settings;
     FrameParams& fp = p.fp;
     fill_frame_params(in.cloud->ptrs.n, &in.view, s, fp);
+    if (in.cloud_bounds) {   // BGS_BOUNDS_CLOUD: the caller's position_min / _max are ignored
+        std::memcpy(fp.pos_min, in.pos_min, sizeof fp.pos_min);
+        std::memcpy(fp.pos_max, in.pos_max, sizeof fp.pos_max);
+    }
     fp.debug = flags;
     fp.srgb8_target = (uint64_t)(uintptr_t)in.srgb8_target;
     const uint32_t n = p.n = fp.n;
@@ -992,9 +1001,18 @@ int run(bgs_ctx* ctx, const bgs_cloud* cloud, const bgs_view* view, const bgs_se
     Lane& L = ctx->lanes[async ? ctx->next : 0];
     if (!async && (rc = finish_all(ctx)) != BGS_OK) return rc;
     if (async && L.pending && (rc = finish_lane(ctx, L)) != BGS_OK) return rc;
-    const FrameInputs in{cloud, *view, *s, render, /*allow_graph=*/async, render ? ctx->next_srgb8_target : nullptr,
+    // BGS_BOUNDS_CLOUD: the cloud's box, reduced now if no call has asked since the positions last changed (an empty
+    // cloud has none: the caller's values stay, nothing is launched)
+    const bool own_bounds = s->reserved[0] == BGS_BOUNDS_CLOUD && cloud->ptrs.n > 0u;
+    if (own_bounds && (rc = cloud_bounds(ctx, cloud)) != BGS_OK) return rc;
+    FrameInputs in{cloud, *view, *s, render, /*allow_graph=*/async, render ? ctx->next_srgb8_target : nullptr,
                          ctx->output_srgb8, ctx->output_rgba16f, ctx->packed_only, ctx->debug_flags,
                          render ? frame_kind(cloud->ptrs.n, cloud->ptrs.format, view, s) : 0ull, /*force_passes=*/false, ctx->grid_cap};
+    if (own_bounds) {
+        in.cloud_bounds = true;
+        std::memcpy(in.pos_min, cloud->bounds_min, sizeof in.pos_min);
+        std::memcpy(in.pos_max, cloud->bounds_max, sizeof in.pos_max);
+    }
     if (!async) {
         ctx->recent = 0;
         ctx->regrow_count = 0;
@@ -1048,11 +1066,38 @@ int apply_particle_step(bgs_ctx* ctx, bgs_cloud* cloud, void* behaviors, uint32_
     }
     if (!ctx->step_done) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->step_done, hipEventDisableTiming));
     hipStream_t st = ctx->lanes[0].stream;
+    cloud->bounds_valid = false;   // (BGS_BOUNDS_CLOUD: the next frame or sort that asks reduces the stepped positions)
     launch_particle_step(st, behaviors, count, cloud->ptrs, dt);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(ctx->step_done, st));
     for (hipStream_t other : ctx->streams)
         if (other && other != st) HIP_TRY(ctx, hipStreamWaitEvent(other, ctx->step_done, 0));
+    return BGS_OK;
+}
+
+// The box of a resident cloud for BGS_BOUNDS_CLOUD frames (bounds_math.h), lazily: uploads and particle steps leave it
+// invalid, and the first bgs_sort / bgs_render that asks
+//   1. completes the frames in flight, as a particle step does (they stay in the ring for bgs_pipeline_pop);
+//   2. enqueues the two presets and the reduction on lane 0's stream: behind a particle step, which ran there, and behind
+//      nothing else that writes positions (an upload has synchronised before it returned);
+//   3. reads the six words back, 24 bytes, and WAITS for them: the one blocking read-back per change of the cloud;
+//   4. decodes them, applies the -+0.1f and keeps the result in the cloud.
+// Every frame, that one included, then carries the box in its FrameInputs.
+int cloud_bounds(bgs_ctx* ctx, const bgs_cloud* cloud) {
+    if (cloud->bounds_valid || cloud->ptrs.n == 0u) return BGS_OK;
+    for (int i; (i = oldest_pending_lane(ctx)) >= 0;) {
+        int rc = finish_lane(ctx, ctx->lanes[i]);
+        if (rc != BGS_OK) return rc;
+        ctx->lanes[i].ready = true;
+    }
+    if (!cloud->bounds_words.reserve(BOUNDS_WORDS)) return fail(ctx, BGS_ENOMEM, "hipMalloc(cloud bounds) failed");
+    hipStream_t st = ctx->lanes[0].stream;
+    uint32_t words[BOUNDS_WORDS];
+    HIP_TRY(ctx, launch_cloud_bounds(st, cloud->ptrs.position_visibility, cloud->ptrs.n, cloud->bounds_words.ptr, (uint32_t)ctx->num_cus, ctx->grid_cap));
+    HIP_TRY(ctx, hipMemcpyAsync(words, cloud->bounds_words.ptr, sizeof words, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    bounds_decode(words, cloud->bounds_min, cloud->bounds_max);
+    cloud->bounds_valid = true;
     return BGS_OK;
 }
 

@@ -273,6 +273,12 @@ void launch_pack_cloud(hipStream_t stream, const uint4* pos, const uint4* a, uin
 // the launch against every frame that reads it (bgs_cloud_apply_particle_behaviors).
 void launch_particle_step(hipStream_t stream, void* behaviors, uint32_t count, const CloudPtrs& cloud, float dt);
 
+// The box of a resident cloud (BGS_BOUNDS_CLOUD; bounds_kernels.hip, bounds_math.h): presets the six words (two memsets on
+// `stream`) and folds the n positions into them as order-preserving keys: words[0..2] the raw minima, words[3..5] the raw
+// maxima, for bounds_decode. The grid is bounds_grid(n, compute_units, grid_cap). n == 0: nothing is enqueued.
+hipError_t launch_cloud_bounds(hipStream_t stream, const float4* position_visibility, uint32_t n, uint32_t* words,
+                               uint32_t compute_units, uint32_t grid_cap);
+
 // STREAM-triad on float4: a = b + s * c (HBM ceiling probe, bgs_hbm_probe).
 void launch_triad(hipStream_t stream, float4* a, const float4* b, const float4* c, float s, size_t n4,
                   int blocks);

@@ -188,6 +188,9 @@ class CloudSettings:
     # RasterizeMode.Position. `compute_aabb(cloud)` gives what the reference would have attached.
     position_min: tuple = (0.0, 0.0, 0.0)
     position_max: tuple = (1.0, 1.0, 1.0)
+    # BGS_BOUNDS_CLOUD (include/bgs.h, bgs_settings.reserved[0]): the frame takes CloudUniform.min / .max from the resident
+    # cloud itself, reduced on the device (`bounds.bounds_reference` is its twin); position_min / position_max are ignored.
+    bounds_from_cloud: bool = False
 
     def to_native(self) -> BgsSettings:
         s = BgsSettings()
@@ -209,6 +212,7 @@ class CloudSettings:
         s.num_classes = int(self.num_classes)
         s.draw_mode = int(self.draw_mode)
         s.visualize_bounding_box = 1 if self.visualize_bounding_box else 0
+        s.reserved[0] = 1 if self.bounds_from_cloud else 0   # BGS_BOUNDS_CLOUD / BGS_BOUNDS_CALLER
         s.position_min[:] = [float(v) for v in self.position_min] + [1.0]
         s.position_max[:] = [float(v) for v in self.position_max] + [1.0]
         return s

@@ -48,6 +48,9 @@ extern "C" {
                                Still 0.9 with the view's colour attachment: bgs_view.reserved[0] got two named values
                                (BGS_VIEW_ATTACH_*; size, offsets and the field's name as they were); zero — what every earlier
                                binding passes and what bgs_view_perspective sets — is the behaviour of before, bit for bit.
+                               Still 0.9 with the cloud's own bounds: bgs_settings.reserved[0] got two named values (BGS_BOUNDS_*;
+                               size, offsets and the field's name as they were); zero — what every earlier binding passes and what
+                               bgs_settings_default sets — is the behaviour of before, bit for bit.
                                0.8: the read-back of what a frame leaves for the next (bgs_diag.h: bgs_debug_frame_leftovers); the seam of this
                                header, bgs_view, bgs_settings and bgs_stats as in 0.4.
                                0.7: the tile rasterisers' test hook (bgs_diag.h: bgs_selftest_raster); the seam of this header, bgs_view,
@@ -222,7 +225,32 @@ typedef struct bgs_settings {
     uint32_t visualize_bounding_box;  /* default 0: VISUALIZE_BOUNDING_BOX (settings.rs:95,117; key bit
                                          src/render/mod.rs:418,824; src/render/gaussian.wgsl:486-495): fragments in the
                                          outer 8 % of a quad's uv square are (0.3, 1, 0.1, 1) — the quads' frames  */
+    /* reserved[0]: WHOSE CloudUniform.min / .max the frame gets, one of BGS_BOUNDS_* below. The word keeps the name bindings
+     * built against 0.4 know it by (they zero it: BGS_BOUNDS_CALLER, the behaviour of before, bit for bit; bgs_settings_default
+     * sets 0 too); size and offsets are as they were.
+     *   BGS_BOUNDS_CALLER (0): position_min / position_max below, as given.
+     *   BGS_BOUNDS_CLOUD (1): the box of the RESIDENT cloud, taken on the device: CommonCloud::compute_aabb
+     *     (src/gaussian/interface.rs:22-63), which calculate_bounds (src/gaussian/cloud.rs:45-62) attaches to every cloud
+     *     entity. For hosts that never hold the positions: a cloud morphed or time-sliced on the device and uploaded from
+     *     device planes, a cloud moved by bgs_cloud_apply_particle_behaviors. position_min / position_max are IGNORED, by
+     *     every rasterize mode; only RasterizeMode::Position reads bounds at all (src/render/gaussian.wgsl:377), and every
+     *     other mode's frame is the bits of its BGS_BOUNDS_CALLER frame.
+     *     Arithmetic, per axis, over the UNTRANSFORMED position_visibility[i].xyz of all n splats, in f32, rounded once:
+     *         min = fold(+inf, f32::min) of (p - 0.1f)          max = fold(-inf, f32::max) of (p + 0.1f)
+     *     f32::min / max ignore a NaN operand (a NaN coordinate contributes nothing to its axis), +-inf propagate, an axis
+     *     with no contributor keeps +inf / -inf. The visibility lane is not read. The result does not depend on the order
+     *     of the splats (csrc/bounds_math.h says why), so it is a contract: bit for bit what a host computes that way.
+     *     The box is reduced LAZILY and kept in the bgs_cloud: uploads and particle steps leave it invalid, and the first
+     *     bgs_sort / bgs_render that says BGS_BOUNDS_CLOUD on such a cloud completes the frames in flight (as a particle
+     *     step does: they stay in the ring), runs one pass over the position plane (16 bytes a splat) and waits for 24
+     *     bytes to come back. Every later call finds the box in the cloud. Hosts that never ask pay nothing.
+     *     Works wherever the caller's bounds do: the box travels with the frame like position_min / position_max
+     *     (both binning modes, asynchronous lanes, kept-order frames, captured graphs: no new capture).
+     *     n == 0: the reference's compute_aabb is None; the caller's values are used and nothing is launched.
+     *   BGS_EINVAL from bgs_sort and bgs_render, naming the field: reserved[0] > 1. */
     uint32_t reserved[1];
+#define BGS_BOUNDS_CALLER 0u
+#define BGS_BOUNDS_CLOUD 1u
     float position_min[4];            /* CloudUniform.min/max = the cloud entity's Aabb   */
     float position_max[4];            /* (src/render/mod.rs:1070-1071); Position mode     */
 } bgs_settings;
@@ -369,7 +397,9 @@ typedef struct bgs_particle_behavior {
  * PRECONDITION: the indices of the active records are distinct. Two records that name one splat race in the reference;
  * here the result for that splat is then unspecified (the C++ and Python layers check it on the host before upload).
  * Works on every cloud format (position_visibility is f32 in all of them). position_min / position_max of bgs_settings
- * stay the caller's: no AABB is refreshed (the reference's TODO, src/gaussian/cloud.rs:43).
+ * stay the caller's under BGS_BOUNDS_CALLER: no AABB is refreshed (the reference's TODO, src/gaussian/cloud.rs:43). Under
+ * BGS_BOUNDS_CLOUD (bgs_settings.reserved[0]) the step invalidates the cloud's box, and the next bgs_sort / bgs_render that
+ * asks for it reduces the stepped positions.
  * ORDERING: the step is a pipeline barrier. Frames in flight are completed first (they — and a re-run of them — draw the
  * positions they were enqueued with; they stay in the ring for bgs_pipeline_pop); every bgs_sort / bgs_render after the
  * call sees the stepped cloud. The call only ENQUEUES the step and returns: the behaviours' memory must stay valid, and

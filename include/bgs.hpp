@@ -86,6 +86,13 @@ struct CloudSettings {
     Mat4 transform = identity();
     std::array<float, 3> position_min{0.0f, 0.0f, 0.0f};
     std::array<float, 3> position_max{1.0f, 1.0f, 1.0f};
+    uint32_t bounds_source = BGS_BOUNDS_CALLER;   // bgs_settings.reserved[0]: set_bounds_from_cloud
+
+    // CloudUniform.min / .max from the resident cloud itself (bgs.h BGS_BOUNDS_CLOUD): the box is taken on the device, the first
+    // time a frame or a sort asks after an upload or a particle step, and position_min / position_max are ignored. For clouds
+    // whose positions the host never held (morphed, time-sliced, moved by particle behaviours). `false` = the caller's (the default).
+    void set_bounds_from_cloud(bool from_cloud) { bounds_source = from_cloud ? BGS_BOUNDS_CLOUD : BGS_BOUNDS_CALLER; }
+    bool bounds_from_cloud() const { return bounds_source == BGS_BOUNDS_CLOUD; }
 
     bgs_settings to_native() const {
         bgs_settings s;
@@ -104,6 +111,7 @@ struct CloudSettings {
         s.num_classes = num_classes;
         s.draw_mode = static_cast<uint32_t>(draw_mode);
         s.visualize_bounding_box = visualize_bounding_box ? 1u : 0u;
+        s.reserved[0] = bounds_source;
         for (int i = 0; i < 3; ++i) {
             s.position_min[i] = position_min[i];
             s.position_max[i] = position_max[i];
