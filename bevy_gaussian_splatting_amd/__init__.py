@@ -68,16 +68,9 @@ from .interpolate import (
     interpolate_reference,
     interpolation_factor,
 )
-from .plugin import (
-    DeviceEntriesChunk,
-    DeviceSortedEntries,
-    GaussianSplattingPlugin,
-    MorphPair,
-    PlanarGaussian3dHandle,
-    ResidentCloud4d,
-    SortedEntries,
-    SORT_ENTRY_DTYPE,
-)
+from .entries import DeviceEntriesChunk, DeviceSortedEntries, SortedEntries, SORT_ENTRY_DTYPE
+from .resident import MorphPair, ResidentCloud4d
+from .plugin import GaussianSplattingPlugin, PlanarGaussian3dHandle
 
 __all__ = [
     "GaussianCamera", "View", "transform_from", "rotation_y",

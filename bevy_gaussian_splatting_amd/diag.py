@@ -10,6 +10,7 @@ import numpy as np
 
 from . import _native
 from .camera import View
+from .entries import SORT_ENTRY_DTYPE
 from .settings import CloudSettings
 
 
@@ -38,7 +39,6 @@ class DiagHooks:
     def radix_sort_pairs(self, keys: np.ndarray, passes: int = 4) -> np.ndarray:
         """Run the device Onesweep kernel on arbitrary (key, index=i) pairs (test hook)."""
         keys = np.ascontiguousarray(keys, dtype=np.uint32)
-        from .plugin import SORT_ENTRY_DTYPE
         e = np.empty(keys.shape[0], dtype=SORT_ENTRY_DTYPE)
         e["key"] = keys
         e["index"] = np.arange(keys.shape[0], dtype=np.uint32)

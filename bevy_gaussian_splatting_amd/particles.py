@@ -9,6 +9,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from .device_memory import DeviceBlock
+
 # ParticleBehavior (src/morph/particle.rs:349-358, #[repr(C)] Pod): 64 bytes, fields at 0 / 16 / 32 / 48.
 # `indicies` is the reference's spelling; [0] is the splat index, read as int32 (negative = inactive).
 PARTICLE_BEHAVIOR_DTYPE = np.dtype([
@@ -56,21 +58,16 @@ class ParticleBehaviors:
         return int(self.records.shape[0])
 
 
-class ParticleBehaviorsHandle:
-    """Behaviours resident in device memory the caller owns (`bgs_device_alloc`): address and record count."""
+class ParticleBehaviorsHandle(DeviceBlock):
+    """Behaviours resident in device memory the caller owns (`bgs_device_alloc`): a `DeviceBlock` (`ptr`, 0 once freed;
+    `free()`) of `count` records, never shorter than 64 bytes."""
 
     def __init__(self, plugin, ptr: int, count: int):
-        self._plugin = plugin
-        self.ptr = ptr
+        super().__init__(plugin, ptr, max(int(count) * PARTICLE_BEHAVIOR_DTYPE.itemsize, 64))
         self.count = int(count)
 
     def __len__(self) -> int:
         return self.count
-
-    def free(self) -> None:
-        if self.ptr and self._plugin._ctx is not None:
-            self._plugin.device_free(self.ptr)
-        self.ptr = 0
 
 
 def random_particle_behaviors(n: int, seed: int) -> ParticleBehaviors:

@@ -8,7 +8,8 @@ Reference call sites this stands behind:
   - draw: `DrawGaussianInstanced::render` (src/render/mod.rs:1513-1569)   -> `render`
 
 All compute happens in libbgs.so (hand-written HIP for gfx950). This module only marshals
-arguments; it has no CPU implementation of any stage.
+arguments; it has no CPU implementation of any stage. The sorted entries are `entries.py`, the owner of a
+`bgs_device_alloc` block is `device_memory.py`, `MorphPair` and `ResidentCloud4d` are `resident.py`; their names are exported here too.
 """
 from __future__ import annotations
 
@@ -20,120 +21,15 @@ import numpy as np
 
 from . import _native
 from .camera import View, color_attachment_offset
-from .diag import DiagHooks, _fptr, _uptr
+from .device_memory import DeviceBlock
+from .diag import DiagHooks, _fptr
+from .entries import SORT_ENTRY_DTYPE, DeviceEntriesChunk, DeviceSortedEntries, SortedEntries  # noqa: F401
 from .gaussian import PlanarGaussian3d, PlanarGaussian3dF16, PlanarGaussian4d
+from .interpolate import covariance_planes
 from .particles import PARTICLE_BEHAVIOR_DTYPE, ParticleBehaviors, ParticleBehaviorsHandle
+from .resident import MorphPair, ResidentCloud4d
 from .settings import CloudSettings
 from .sparse_select import SparseSelect, selected_indices
-
-SORT_ENTRY_DTYPE = np.dtype([("key", np.uint32), ("index", np.uint32)])
-
-
-@dataclass
-class SortedEntries:
-    """src/sort/mod.rs:331-393: `camera_count * entry_count` (key, index) pairs, where the creator
-    passes `entry_count = cloud.len_sqrt_ceil()**2` (src/sort/mod.rs:259-262). Camera `c` owns the
-    chunk `sorted[c * gaussians : (c + 1) * gaussians]` with `gaussians = cloud.len()` — the stride is
-    the CLOUD length, not entry_count, both where the sort writes (`chunks_mut(gaussians).nth(
-    camera_index)`, src/sort/rayon.rs:82-84) and where the draw binds (dynamic offset
-    `camera_index * 8 * cloud.len()`, src/render/mod.rs:1548-1554); the square-padding tail is unused."""
-
-    camera_count: int
-    entry_count: int
-    sorted: np.ndarray  # structured SORT_ENTRY_DTYPE
-
-    @staticmethod
-    def new(camera_count: int, entry_count: int) -> "SortedEntries":
-        s = np.empty(camera_count * entry_count, dtype=SORT_ENTRY_DTYPE)
-        s["key"] = 1  # src/sort/mod.rs:349-352
-        s["index"] = np.tile(np.arange(entry_count, dtype=np.uint32), camera_count)
-        return SortedEntries(camera_count, entry_count, s)
-
-    @staticmethod
-    def for_cloud(camera_count: int, cloud_len: int) -> "SortedEntries":
-        """`auto_insert_sorted_entries` (src/sort/mod.rs:218-268)."""
-        side = int(np.ceil(np.sqrt(np.float32(cloud_len))))
-        return SortedEntries.new(camera_count, side * side)
-
-    def chunk(self, camera_index: int, gaussians: Optional[int] = None) -> np.ndarray:
-        g = self.entry_count if gaussians is None else int(gaussians)
-        if camera_index < 0 or (camera_index + 1) * g > self.sorted.shape[0]:
-            raise IndexError("camera chunk out of range")  # `.nth(camera_index).unwrap()` panics
-        return self.sorted[camera_index * g : (camera_index + 1) * g]
-
-    def resized(self, camera_count: int) -> "SortedEntries":
-        """`update_sorted_entries_sizes` (src/sort/mod.rs:270-296): a camera-count change re-creates
-        the asset (all chunks back to key 1 / identity order)."""
-        return self if camera_count == self.camera_count else SortedEntries.new(camera_count, self.entry_count)
-
-
-@dataclass
-class DeviceEntriesChunk:
-    """One camera's chunk of a `DeviceSortedEntries`: `count` (key, index) records at the device address `ptr`
-    (`bgs_view.entries_device_ptr` / `entry_count`)."""
-
-    ptr: int
-    count: int
-
-
-class DeviceSortedEntries:
-    """`SortedEntries` resident on the device: `camera_count` chunks of `gaussians` = cloud.len() entries each in ONE
-    `bgs_device_alloc` block, camera `c` at byte offset `c * 8 * gaussians` — the dynamic offset the reference's draw binds
-    (src/render/mod.rs:1548-1554). `sort(..., into=chunk)` fills a chunk, `render(..., entries=chunk)` draws it as it is.
-    New chunks hold the asset's initial content, key 1 / index i (src/sort/mod.rs:347-354). The caller orders a sort into
-    a chunk against frames in flight that read it (`bgs_sort` completes the frames in flight first)."""
-
-    ENTRY_BYTES = 8
-
-    def __init__(self, plugin: "GaussianSplattingPlugin", camera_count: int, gaussians: int):
-        if camera_count < 1 or gaussians < 0:
-            raise ValueError("camera_count must be >= 1 and gaussians >= 0")
-        self._plugin = plugin
-        self.camera_count = int(camera_count)
-        self.gaussians = int(gaussians)
-        self.ptr = plugin.device_alloc(max(self.nbytes, self.ENTRY_BYTES))
-        if self.gaussians:
-            init = np.empty(self.camera_count * self.gaussians, dtype=SORT_ENTRY_DTYPE)
-            init["key"] = 1
-            init["index"] = np.tile(np.arange(self.gaussians, dtype=np.uint32), self.camera_count)
-            plugin.upload_bytes(self.ptr, init)
-
-    @staticmethod
-    def chunk_offset(camera_index: int, gaussians: int) -> int:
-        """Byte offset of camera `camera_index`'s chunk: `camera_index * 8 * gaussians` (always a multiple of 8)."""
-        return int(camera_index) * DeviceSortedEntries.ENTRY_BYTES * int(gaussians)
-
-    @property
-    def nbytes(self) -> int:
-        return self.chunk_offset(self.camera_count, self.gaussians)
-
-    def chunk(self, camera_index: int) -> DeviceEntriesChunk:
-        if self.ptr is None:
-            raise ValueError("the entries have been freed")
-        if camera_index < 0 or camera_index >= self.camera_count:
-            raise IndexError("camera chunk out of range")  # `.nth(camera_index).unwrap()` panics
-        return DeviceEntriesChunk(self.ptr + self.chunk_offset(camera_index, self.gaussians), self.gaussians)
-
-    def upload(self, camera_index: int, entries: np.ndarray) -> None:
-        """Overwrite a chunk with host entries (hand-built orders; blocking)."""
-        e = np.ascontiguousarray(entries, dtype=SORT_ENTRY_DTYPE)
-        if e.shape != (self.gaussians,):
-            raise ValueError("a chunk holds exactly cloud.len() entries")
-        if e.nbytes:
-            self._plugin.upload_bytes(self.chunk(camera_index).ptr, e)
-
-    def download(self, camera_index: int) -> np.ndarray:
-        """A chunk's entries (completes the frames in flight first; blocking)."""
-        out = np.empty(self.gaussians, dtype=SORT_ENTRY_DTYPE)
-        self._plugin.synchronize()
-        if out.nbytes:
-            self._plugin.download(self.chunk(camera_index).ptr, out)
-        return out
-
-    def free(self) -> None:
-        if self.ptr is not None and self._plugin._ctx is not None:
-            self._plugin.device_free(self.ptr)   # (completes the frames in flight first)
-        self.ptr = None
 
 
 def _with_entries(v, chunk):
@@ -176,141 +72,15 @@ class PlanarGaussian3dHandle:
         self._ptr = None
 
 
-class MorphPair:
-    """The two sides of a morph (`GaussianInterpolate { lhs, rhs }`) and the output's planes, kept in device memory
-    across calls; made by `GaussianSplattingPlugin.morph_pair`. `at(settings)` runs the blend on `bgs_stream`
-    (libbgs_morph.so) and hands the output's device planes to the cloud upload, which packs them where they lie
-    (include/bgs.h "DEVICE PLANES"): nothing crosses the host."""
-
-    def __init__(self, plugin: "GaussianSplattingPlugin", lhs: PlanarGaussian3d, rhs: PlanarGaussian3d,
-                 precompute_covariance_3d: bool = False, interpolator=None):
-        from .interpolate import COV3D_WIDTHS, F32_WIDTHS, GaussianInterpolator, covariance_planes, planes_of
-        if not isinstance(lhs, PlanarGaussian3d) or not isinstance(rhs, PlanarGaussian3d):
-            raise TypeError("lhs and rhs must be f32 PlanarGaussian3d")
-        if len(lhs) != len(rhs):
-            raise ValueError(f"lhs has {len(lhs)} splats, rhs {len(rhs)}: a morph needs two clouds of equal length")
-        self._plugin = plugin
-        self._interpolator = interpolator or GaussianInterpolator(plugin.device)
-        self.n = len(lhs)
-        self.precompute_covariance_3d = bool(precompute_covariance_3d)
-        self._widths = COV3D_WIDTHS if precompute_covariance_3d else F32_WIDTHS
-        sides = [planes_of(covariance_planes(c) if precompute_covariance_3d else c) for c in (lhs, rhs)]
-        self._ptrs = []                      # the lhs's planes, the rhs's, the output's
-        if self.n:
-            try:
-                for plane in sides[0] + sides[1]:
-                    self._ptrs.append(plugin.device_alloc(plane.nbytes))
-                    plugin.upload_bytes(self._ptrs[-1], plane)
-                for w in self._widths:
-                    self._ptrs.append(plugin.device_alloc(self.n * w * 4))
-            except BaseException:
-                self.free()
-                raise
-
-    def __len__(self) -> int:
-        return self.n
-
-    def at(self, settings: CloudSettings, return_planes: bool = False):
-        """The output cloud at `settings.time` (time_start and time_stop are read as well) as a resident handle, of
-        format "cov3d" for a pair made with `precompute_covariance_3d`. The blend is enqueued on `bgs_stream` and the
-        upload follows it with no synchronisation in between: the upload orders itself behind that stream and returns
-        once the cloud is complete, so the next `at` may overwrite the output planes. Free the handle before the next
-        time's replaces it. With `return_planes` also the output's planes, downloaded."""
-        plugin, k = self._plugin, len(self._widths)
-        outs = [np.zeros((self.n, w), np.float32) for w in self._widths] if return_planes else None
-        if self.n and not self._ptrs:
-            raise RuntimeError("this MorphPair was freed")
-        out_ptrs = self._ptrs[2 * k:] if self.n else [0] * k
-        if self.n:
-            self._interpolator.interpolate(plugin.stream_handle(), self.n, self._ptrs[:k], self._ptrs[k:2 * k], out_ptrs, settings)
-        handle = plugin.upload_device_planes("cov3d" if self.precompute_covariance_3d else "f32", self.n, out_ptrs)
-        if return_planes and self.n:
-            for ptr, plane in zip(out_ptrs, outs):     # (the upload has synchronised: the planes are complete)
-                plugin.download(ptr, plane)
-        return (handle, tuple(outs)) if return_planes else handle
-
-    def free(self) -> None:
-        ptrs, self._ptrs = self._ptrs, []
-        if self._plugin._ctx is not None:
-            for ptr in ptrs:
-                self._plugin.device_free(ptr)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.free()
-
-
-class ResidentCloud4d:
-    """A 4D cloud's five planes and the three planes of its slice, kept in device memory across calls; made by
-    `GaussianSplattingPlugin.resident_4d`. The analogue of `MorphPair` for a playing 4D asset: the planes go up once,
-    and `at(settings)` does only the slice (`bgst_slice` on `bgs_stream`, libbgs_slice.so) and the cloud upload from
-    the slice's device planes (include/bgs.h "DEVICE PLANES"): nothing crosses the host."""
-
-    WIDTHS = (4, 48, 8)
-
-    def __init__(self, plugin: "GaussianSplattingPlugin", cloud4d: PlanarGaussian4d, slicer=None):
-        from .time_slice import TimeSlicer
-        if not isinstance(cloud4d, PlanarGaussian4d):
-            raise TypeError("cloud4d must be a PlanarGaussian4d")
-        self._plugin = plugin
-        self._slicer = slicer or TimeSlicer(plugin.device)
-        self.n = len(cloud4d)
-        self._ptrs = []                      # the five planes of the 4D cloud, then the slice's three
-        if self.n:
-            try:
-                for plane in cloud4d.planes():
-                    self._ptrs.append(plugin.device_alloc(plane.nbytes))
-                    plugin.upload_bytes(self._ptrs[-1], plane)
-                for w in self.WIDTHS:
-                    self._ptrs.append(plugin.device_alloc(self.n * w * 4))
-            except BaseException:
-                self.free()
-                raise
-
-    def __len__(self) -> int:
-        return self.n
-
-    def at(self, settings: CloudSettings, return_planes: bool = False):
-        """The cloud at `settings.time` (global_scale, time_start and time_stop are read too) as a resident handle of
-        format "cov3d". The slice is enqueued on `bgs_stream` and the upload follows it with no synchronisation in
-        between: the upload orders itself behind that stream and returns once the cloud is complete, so the next `at`
-        may overwrite the slice's planes. Sort and render the handle with any settings of the precomputed-covariance
-        path, which reads neither `time` nor `global_scale`; free it before the next time's replaces it. With
-        `return_planes` also the slice's three planes, downloaded."""
-        plugin = self._plugin
-        outs = [np.zeros((self.n, w), np.float32) for w in self.WIDTHS] if return_planes else None
-        if self.n and not self._ptrs:
-            raise RuntimeError("this ResidentCloud4d was freed")
-        out_ptrs = self._ptrs[5:] if self.n else [0] * 3
-        if self.n:
-            self._slicer.slice(plugin.stream_handle(), self.n, self._ptrs[:5], out_ptrs, settings)
-        handle = plugin.upload_device_planes("cov3d", self.n, out_ptrs)
-        if return_planes and self.n:
-            for ptr, plane in zip(out_ptrs, outs):     # (the upload has synchronised: the planes are complete)
-                plugin.download(ptr, plane)
-        return (handle, tuple(outs)) if return_planes else handle
-
-    def free(self) -> None:
-        ptrs, self._ptrs = self._ptrs, []
-        if self._plugin._ctx is not None:
-            for ptr in ptrs:
-                self._plugin.device_free(ptr)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.free()
-
-
 # The three cloud uploads by format: the C entry point, its planes in the order of its arguments, and the bytes of a splat.
 DEVICE_PLANE_FORMATS = {
     "f32": ("bgs_cloud_upload_f32", ("position_visibility", "spherical_harmonic", "rotation", "scale_opacity"), 16 + 192 + 16 + 16),
     "f16": ("bgs_cloud_upload_f16", ("position_visibility", "spherical_harmonic_h2", "rotation_scale_opacity"), 16 + 96 + 16),
     "cov3d": ("bgs_cloud_upload_cov3d_f32", ("position_visibility", "spherical_harmonic", "covariance_3d_opacity"), 16 + 192 + 32),
 }
+# ... and the type of each plane's argument, by plane: float rows, but for the two planes of packed halves (uint32 words)
+PLANE_POINTER_TYPES = {name: ctypes.POINTER(ctypes.c_uint32 if name in ("spherical_harmonic_h2", "rotation_scale_opacity") else
+                                            ctypes.c_float) for _, names, _ in DEVICE_PLANE_FORMATS.values() for name in names}
 
 
 class GaussianSplattingPlugin(DiagHooks):
@@ -321,10 +91,7 @@ class GaussianSplattingPlugin(DiagHooks):
     def __init__(self, device: int = 0):
         self._lib = _native.load()
         ctx = ctypes.c_void_p()
-        st = self._lib.bgs_create(int(device), ctypes.byref(ctx))
-        if st != _native.BGS_OK:
-            msg = self._lib.bgs_last_error(None)
-            raise _native.BgsError(st, msg.decode("utf-8", "replace") if msg else "")
+        _native.check(self._lib, None, self._lib.bgs_create(int(device), ctypes.byref(ctx)))
         self._ctx = ctx
         self.device = device
 
@@ -350,54 +117,44 @@ class GaussianSplattingPlugin(DiagHooks):
         _native.check(self._lib, self._ctx, status)
 
     # -- cloud upload ----------------------------------------------------------------
-    def upload(self, cloud: Union[PlanarGaussian3d, PlanarGaussian3dF16],
-               precompute_covariance_3d: bool = False) -> PlanarGaussian3dHandle:
+    def upload(self, cloud: Union[PlanarGaussian3d, PlanarGaussian3dF16], precompute_covariance_3d: bool = False) -> PlanarGaussian3dHandle:
         """Make the cloud resident in HBM (the reference's asset upload). `precompute_covariance_3d`: store
         the `Covariance3dOpacity` plane (src/gaussian/f32.rs:218-251) instead of rotation and scale, as the
         reference's feature of that name does; the vertex stage then skips compute_cov3d."""
-        out = ctypes.c_void_p()
-        n = len(cloud)
         if precompute_covariance_3d:
             if not isinstance(cloud, PlanarGaussian3d):
                 raise TypeError("precompute_covariance_3d needs an f32 PlanarGaussian3d")
-            from .gaussian import covariance_3d_opacity
-            cov = np.ascontiguousarray(covariance_3d_opacity(cloud), np.float32)
-            self._check(
-                self._lib.bgs_cloud_upload_cov3d_f32(
-                    self._ctx, n, _fptr(cloud.position_visibility), _fptr(cloud.spherical_harmonic),
-                    _fptr(cov), ctypes.byref(out)))
-            return PlanarGaussian3dHandle(self, out, n, "cov3d", n * (16 + 192 + 32))
-        if isinstance(cloud, PlanarGaussian3dF16):
-            self._check(
-                self._lib.bgs_cloud_upload_f16(
-                    self._ctx, n, _fptr(cloud.position_visibility),
-                    _uptr(cloud.spherical_harmonic), _uptr(cloud.rotation_scale_opacity),
-                    ctypes.byref(out)))
-            fmt = "f16"
+            fmt, planes = "cov3d", covariance_planes(cloud)
+        elif isinstance(cloud, PlanarGaussian3dF16):
+            fmt, planes = "f16", (cloud.position_visibility, cloud.spherical_harmonic, cloud.rotation_scale_opacity)
         elif isinstance(cloud, PlanarGaussian3d):
-            self._check(
-                self._lib.bgs_cloud_upload_f32(
-                    self._ctx, n, _fptr(cloud.position_visibility),
-                    _fptr(cloud.spherical_harmonic), _fptr(cloud.rotation),
-                    _fptr(cloud.scale_opacity), ctypes.byref(out)))
-            fmt = "f32"
+            fmt, planes = "f32", (cloud.position_visibility, cloud.spherical_harmonic, cloud.rotation, cloud.scale_opacity)
         else:
             raise TypeError("cloud must be PlanarGaussian3d or PlanarGaussian3dF16")
-        return PlanarGaussian3dHandle(self, out, n, fmt, cloud.nbytes())
+        return self._upload_host_planes(fmt, len(cloud), planes)
+
+    def _upload_cloud(self, fmt: str, n: int, args) -> PlanarGaussian3dHandle:
+        """The one call of a cloud upload: `fmt`'s entry point over `args`, its planes as ctypes pointers in the order of
+        `DEVICE_PLANE_FORMATS`; the handle carries the format and the bytes of `n` splats in it."""
+        entry, _, splat_bytes = DEVICE_PLANE_FORMATS[fmt]
+        out = ctypes.c_void_p()
+        self._check(getattr(self._lib, entry)(self._ctx, n, *args, ctypes.byref(out)))
+        return PlanarGaussian3dHandle(self, out, n, fmt, n * splat_bytes)
+
+    def _upload_host_planes(self, fmt: str, n: int, planes) -> PlanarGaussian3dHandle:
+        """`_upload_cloud` of contiguous host arrays (`planes` keeps them alive across the call)."""
+        names = DEVICE_PLANE_FORMATS[fmt][1]
+        return self._upload_cloud(fmt, n, [a.ctypes.data_as(PLANE_POINTER_TYPES[name]) for a, name in zip(planes, names)])
 
     def upload_covariance_planes(self, position_visibility, spherical_harmonic, covariance_3d_opacity) -> PlanarGaussian3dHandle:
         """The sibling of `upload(..., precompute_covariance_3d=True)` for a covariance plane that is already made:
         [n, 4], [n, 48] and [n, 8] float32 (`Covariance3dOpacity`: xx, xy, xz, yy, yz, zz, opacity, pad) go up as they
         are (`bgs_cloud_upload_cov3d_f32`). Returns a handle of format "cov3d"."""
-        pv = np.ascontiguousarray(position_visibility, np.float32)
-        sh = np.ascontiguousarray(spherical_harmonic, np.float32)
-        cov = np.ascontiguousarray(covariance_3d_opacity, np.float32)
+        pv, sh, cov = (np.ascontiguousarray(a, np.float32) for a in (position_visibility, spherical_harmonic, covariance_3d_opacity))
         n = pv.shape[0]
         if pv.shape != (n, 4) or sh.shape != (n, 48) or cov.shape != (n, 8):
             raise ValueError("expected planes of shape [n, 4], [n, 48] and [n, 8]")
-        out = ctypes.c_void_p()
-        self._check(self._lib.bgs_cloud_upload_cov3d_f32(self._ctx, n, _fptr(pv), _fptr(sh), _fptr(cov), ctypes.byref(out)))
-        return PlanarGaussian3dHandle(self, out, n, "cov3d", n * (16 + 192 + 32))
+        return self._upload_host_planes("cov3d", n, (pv, sh, cov))
 
     def upload_device_planes(self, fmt: str, n: int, pointers) -> PlanarGaussian3dHandle:
         """A resident cloud of `n` splats from planes that are in device memory already (include/bgs.h "DEVICE PLANES"):
@@ -408,19 +165,14 @@ class GaussianSplattingPlugin(DiagHooks):
         entry points take host addresses as well, plane by plane, so the planes may be mixed."""
         if fmt not in DEVICE_PLANE_FORMATS:
             raise ValueError(f"fmt must be one of {sorted(DEVICE_PLANE_FORMATS)}, not {fmt!r}")
-        entry, names, splat_bytes = DEVICE_PLANE_FORMATS[fmt]
+        entry, names, _ = DEVICE_PLANE_FORMATS[fmt]
         pointers = [int(p or 0) for p in pointers]
         if len(pointers) != len(names):
             raise ValueError(f"{entry} takes {len(names)} planes ({', '.join(names)}), got {len(pointers)} pointers")
         n = int(n)
         if n < 0:
             raise ValueError("n must be >= 0")
-        ptype = {"f32": ctypes.POINTER(ctypes.c_float), "u32": ctypes.POINTER(ctypes.c_uint32)}
-        kinds = ("f32", "u32", "u32") if fmt == "f16" else ("f32",) * len(names)
-        args = [ctypes.cast(ctypes.c_void_p(p), ptype[k]) for p, k in zip(pointers, kinds)]
-        out = ctypes.c_void_p()
-        self._check(getattr(self._lib, entry)(self._ctx, n, *args, ctypes.byref(out)))
-        return PlanarGaussian3dHandle(self, out, n, fmt, n * splat_bytes)
+        return self._upload_cloud(fmt, n, [ctypes.cast(ctypes.c_void_p(p), PLANE_POINTER_TYPES[name]) for p, name in zip(pointers, names)])
 
     # -- 4D clouds (src/render/gaussian_4d.wgsl; libbgs_slice.so) ----------------------
     def resident_4d(self, cloud4d: PlanarGaussian4d, slicer=None) -> "ResidentCloud4d":
@@ -470,10 +222,7 @@ class GaussianSplattingPlugin(DiagHooks):
         rec = behaviors.records if isinstance(behaviors, ParticleBehaviors) else np.ascontiguousarray(behaviors)
         if rec.dtype != PARTICLE_BEHAVIOR_DTYPE or rec.ndim != 1:
             raise TypeError("behaviors must be ParticleBehaviors or a 1-D array of PARTICLE_BEHAVIOR_DTYPE")
-        ptr = self.device_alloc(max(rec.nbytes, 64))
-        if rec.nbytes:
-            self.upload_bytes(ptr, rec)
-        return ParticleBehaviorsHandle(self, ptr, rec.shape[0])
+        return ParticleBehaviorsHandle(self, self.device_block(max(rec.nbytes, 64), rec).release(), rec.shape[0])
 
     def apply_particle_behaviors(self, handle: PlanarGaussian3dHandle, behaviors: ParticleBehaviorsHandle, dt: float) -> None:
         """One step of the behaviours on the resident cloud (`bgs_cloud_apply_particle_behaviors`): positions (and
@@ -505,14 +254,11 @@ class GaussianSplattingPlugin(DiagHooks):
         self.synchronize()
         if n == 0 or chunk.count == 0:
             return
-        scratch = self.device_alloc(4 * n)
-        try:
+        with self.device_block(4 * n) as scratch:
             stream = self.stream_handle()
-            mesh.crossings(stream, points_ptr, n, matrix, scratch)
-            mesh.entries_keep(stream, chunk.ptr, chunk.count, scratch, n, outside=outside)
+            mesh.crossings(stream, points_ptr, n, matrix, scratch.ptr)
+            mesh.entries_keep(stream, chunk.ptr, chunk.count, scratch.ptr, n, outside=outside)
             self.synchronize()
-        finally:
-            self.device_free(scratch)
 
     # -- sparse-splat selection (src/query/sparse.rs; libbgs_sparse.so) ------------------
     def keep_sparse(self, chunk: DeviceEntriesChunk, points_ptr: int, grid, select: SparseSelect = SparseSelect(),
@@ -528,14 +274,11 @@ class GaussianSplattingPlugin(DiagHooks):
         self.synchronize()
         if n == 0 or chunk.count == 0:
             return
-        scratch = self.device_alloc(4 * n)
-        try:
+        with self.device_block(4 * n) as scratch:
             stream = self.stream_handle()
-            grid.neighbor_counts(stream, points_ptr, n, select.radius, scratch, cap=select.neighbor_threshold)
-            grid.entries_keep(stream, chunk.ptr, chunk.count, scratch, n, select.neighbor_threshold, dense=dense)
+            grid.neighbor_counts(stream, points_ptr, n, select.radius, scratch.ptr, cap=select.neighbor_threshold)
+            grid.entries_keep(stream, chunk.ptr, chunk.count, scratch.ptr, n, select.neighbor_threshold, dense=dense)
             self.synchronize()
-        finally:
-            self.device_free(scratch)
 
     def sparse_select(self, points_ptr: int, n: int, grid, select: SparseSelect = SparseSelect()) -> np.ndarray:
         """The ascending indices of the sparse splats among the `n` points at `points_ptr` (the reference's
@@ -544,13 +287,10 @@ class GaussianSplattingPlugin(DiagHooks):
         self.synchronize()
         if n == 0:
             return np.zeros(0, np.uint32)
-        scratch = self.device_alloc(4 * n)
-        try:
-            grid.neighbor_counts(self.stream_handle(), points_ptr, n, select.radius, scratch, cap=select.neighbor_threshold)
+        with self.device_block(4 * n) as scratch:
+            grid.neighbor_counts(self.stream_handle(), points_ptr, n, select.radius, scratch.ptr, cap=select.neighbor_threshold)
             self.synchronize()
-            counts = self.download(scratch, np.empty(n, np.uint32))
-        finally:
-            self.device_free(scratch)
+            counts = self.download(scratch.ptr, np.empty(n, np.uint32))
         return selected_indices(counts, select.neighbor_threshold)
 
     # -- hot path --------------------------------------------------------------------
@@ -587,11 +327,7 @@ class GaussianSplattingPlugin(DiagHooks):
             raise ValueError("sorted_entries has fewer camera chunks than the camera indices need")
         for view, ci in zip(views, idx):
             chunk = sorted_entries.chunk(ci, handle.n)
-            v, s = view.to_native(), settings.to_native()
-            tmp = np.empty(handle.n, dtype=SORT_ENTRY_DTYPE)
-            self._check(self._lib.bgs_sort(self._ctx, handle._ptr, ctypes.byref(v), ctypes.byref(s),
-                                           tmp.ctypes.data_as(ctypes.POINTER(_native.BgsSortEntry))))
-            chunk[:] = tmp
+            chunk[:] = self.sort(handle, view, settings)
         return sorted_entries
 
     def prepare(self, view: View, settings: CloudSettings) -> "PreparedView":
@@ -673,17 +409,20 @@ class GaussianSplattingPlugin(DiagHooks):
         """Frames that write a packed image (sRGB8 / Rgba16Float) skip the f32 target."""
         self._check(self._lib.bgs_set_packed_only(self._ctx, 1 if enabled else 0))
 
-    def framebuffer_rgba16f_device_ptr(self):
-        p = ctypes.c_void_p()
-        nbytes = ctypes.c_uint64()
-        self._check(self._lib.bgs_framebuffer_rgba16f_device_ptr(self._ctx, ctypes.byref(p), ctypes.byref(nbytes)))
+    def _framebuffer(self, getter):
+        """(address, bytes) of one of the last frame's images, from its `bgs_framebuffer_*device_ptr`."""
+        p, nbytes = ctypes.c_void_p(), ctypes.c_uint64()
+        self._check(getter(self._ctx, ctypes.byref(p), ctypes.byref(nbytes)))
         return p.value, nbytes.value
 
+    def framebuffer_device_ptr(self):
+        return self._framebuffer(self._lib.bgs_framebuffer_device_ptr)
+
+    def framebuffer_rgba16f_device_ptr(self):
+        return self._framebuffer(self._lib.bgs_framebuffer_rgba16f_device_ptr)
+
     def framebuffer_srgb8_device_ptr(self):
-        p = ctypes.c_void_p()
-        nbytes = ctypes.c_uint64()
-        self._check(self._lib.bgs_framebuffer_srgb8_device_ptr(self._ctx, ctypes.byref(p), ctypes.byref(nbytes)))
-        return p.value, nbytes.value
+        return self._framebuffer(self._lib.bgs_framebuffer_srgb8_device_ptr)
 
     def pipeline_pop(self):
         """Complete the oldest frame in flight; returns (f32 framebuffer ptr, srgb8 ptr or None)."""
@@ -710,7 +449,7 @@ class GaussianSplattingPlugin(DiagHooks):
         `sort` all n entries, after `render` the drawable prefix (what reaches the vertex stage, back to front)."""
         p, n = ctypes.c_void_p(), ctypes.c_uint32()
         self._check(self._lib.bgs_sorted_entries_device_ptr(self._ctx, ctypes.byref(p), ctypes.byref(n)))
-        out = np.empty(n.value, dtype=np.dtype([("key", np.uint32), ("index", np.uint32)]))
+        out = np.empty(n.value, dtype=SORT_ENTRY_DTYPE)
         if n.value:
             self._check(self._lib.bgs_download(self._ctx, p, out.ctypes.data_as(ctypes.c_void_p), out.nbytes))
         return out
@@ -724,6 +463,11 @@ class GaussianSplattingPlugin(DiagHooks):
 
     def device_free(self, device_ptr: int) -> None:
         self._check(self._lib.bgs_device_free(self._ctx, ctypes.c_void_p(device_ptr)))
+
+    def device_block(self, nbytes: int, init: Optional[np.ndarray] = None) -> DeviceBlock:
+        """`device_alloc` with an owner (`device_memory.DeviceBlock`: `free()` once, or `with`), holding `init` if one is
+        given and it is not empty. If that upload raises, the block is freed."""
+        return DeviceBlock.allocate(self, nbytes, init)
 
     def upload_bytes(self, device_ptr: int, host: np.ndarray) -> None:
         """`bgs_upload`: blocking host-to-device copy of a contiguous array."""
@@ -742,12 +486,7 @@ class GaussianSplattingPlugin(DiagHooks):
         """Put a view's scene depth on the device: `depth` is [height, width, samples] float32 (reverse-Z, what Bevy's
         opaque passes left in the view's Depth32Float attachment; src/render/mod.rs:959-974). Returns the device
         address for `View.depth_device_ptr`; release it with `device_free` once the frames that use it are complete."""
-        d = np.ascontiguousarray(depth, dtype=np.float32)
-        if d.ndim != 3 or d.shape[2] not in (1, 2, 4, 8):
-            raise ValueError("depth must be [height, width, samples] with 1, 2, 4 or 8 samples")
-        p = self.device_alloc(d.nbytes)
-        self.upload_bytes(p, d)
-        return p
+        return self.upload_attachments(depth)[0]
 
     def upload_attachments(self, depth: np.ndarray, color: Optional[np.ndarray] = None):
         """Put a view's attachment pair on the device in ONE allocation (include/bgs.h BGS_VIEW_ATTACH_COLOR): `depth`
@@ -761,23 +500,18 @@ class GaussianSplattingPlugin(DiagHooks):
         if d.ndim != 3 or d.shape[2] not in (1, 2, 4, 8):
             raise ValueError("depth must be [height, width, samples] with 1, 2, 4 or 8 samples")
         if color is None:
-            p = self.device_alloc(d.nbytes)
-            self.upload_bytes(p, d)
-            return p, p
+            return (self.device_block(d.nbytes, d).release(),) * 2
         c = np.ascontiguousarray(color, dtype=np.float32)
         if c.shape != d.shape + (4,):
             raise ValueError(f"color must be [height, width, samples, 4] = {d.shape + (4,)}, got {c.shape}")
         h, w, s = d.shape
         off = color_attachment_offset(w, h, s)
-        p = self.device_alloc(off + c.nbytes)
-        try:
-            if p % 16:
+        with self.device_block(off + c.nbytes) as block:        # (the caller's once both halves are up)
+            if block.ptr % 16:
                 raise RuntimeError("device_alloc returned memory that is not 16-byte aligned")
-            self.upload_bytes(p, d)
-            self.upload_bytes(p + off, c)
-        except Exception:
-            self.device_free(p)
-            raise
+            self.upload_bytes(block.ptr, d)
+            self.upload_bytes(block.ptr + off, c)
+            p = block.release()
         return p, p
 
     def build_id(self) -> str:
@@ -830,12 +564,6 @@ class GaussianSplattingPlugin(DiagHooks):
         supertile rule): the next frames behave like the first frames of a fresh context."""
         self._check(self._lib.bgs_reset_adaptive_state(self._ctx))
 
-    def framebuffer_device_ptr(self):
-        p = ctypes.c_void_p()
-        nbytes = ctypes.c_uint64()
-        self._check(self._lib.bgs_framebuffer_device_ptr(self._ctx, ctypes.byref(p), ctypes.byref(nbytes)))
-        return p.value, nbytes.value
-
     def stream_handle(self) -> int:
         p = ctypes.c_void_p()
         self._check(self._lib.bgs_stream(self._ctx, ctypes.byref(p)))
@@ -844,7 +572,7 @@ class GaussianSplattingPlugin(DiagHooks):
     def stats(self) -> dict:
         st = _native.BgsStats()
         self._check(self._lib.bgs_get_stats(self._ctx, ctypes.byref(st)))
-        d = {
+        return {
             "total_ms": float(st.total_ms),
             "splat_count": int(st.splat_count),
             "visible_count": int(st.visible_count),
@@ -866,4 +594,3 @@ class GaussianSplattingPlugin(DiagHooks):
             "frames_averaged": int(st.frames_averaged),
             "stage_ms": {n: float(st.stage_ms[i]) for i, n in enumerate(_native.STAGE_NAMES)},
         }
-        return d

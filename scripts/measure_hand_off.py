@@ -124,12 +124,10 @@ def main():
                 return pair.at(CloudSettings(time=time_of(k, count)))
             row["morph_f32"] = series(torch, plugin, morph_step, args.warmup, args.steps, args.repeats)
             if args.route == "resident":
-                w = len(pair._widths)
                 row["morph_f32"]["split"] = split(
                     torch, plugin,
-                    lambda k: pair._interpolator.interpolate(plugin.stream_handle(), n, pair._ptrs[:w], pair._ptrs[w:2 * w], pair._ptrs[2 * w:],
-                                                             CloudSettings(time=time_of(k, count))),
-                    lambda: plugin.upload_device_planes("f32", n, pair._ptrs[2 * w:]), n, args.warmup, args.steps)
+                    lambda k: pair.enqueue(plugin.stream_handle(), CloudSettings(time=time_of(k, count))),
+                    lambda: plugin.upload_device_planes("f32", n, pair.out_ptrs), n, args.warmup, args.steps)
         if args.route == "api":
             def slice_step(k, previous):
                 free(previous)
@@ -143,9 +141,8 @@ def main():
                 row["slice"] = series(torch, plugin, slice_step, args.warmup, args.steps, args.repeats)
                 row["slice"]["split"] = split(
                     torch, plugin,
-                    lambda k: resident._slicer.slice(plugin.stream_handle(), n, resident._ptrs[:5], resident._ptrs[5:],
-                                                     CloudSettings(time=time_of(k, count))),
-                    lambda: plugin.upload_device_planes("cov3d", n, resident._ptrs[5:]), n, args.warmup, args.steps)
+                    lambda k: resident.enqueue(plugin.stream_handle(), CloudSettings(time=time_of(k, count))),
+                    lambda: plugin.upload_device_planes("cov3d", n, resident.out_ptrs), n, args.warmup, args.steps)
             # the one-shot wrapper in this tree, for the record: it still puts the five planes up on every call
             def one_shot_step(k, previous):
                 free(previous)
