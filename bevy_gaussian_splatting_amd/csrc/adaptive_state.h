@@ -38,6 +38,20 @@ inline uint64_t frame_kind(uint32_t n, uint32_t format, const bgs_view* view, co
     return hsh ? hsh : 1ull;
 }
 
+// ---- tile instances (BINNING_SORT) ---------------------------------------------------------------------------------------
+constexpr uint64_t MIN_INSTANCE_CAPACITY = 1ull << 22;  // 4M instances (32 MB per buffer)
+constexpr uint64_t MAX_INSTANCE_CAPACITY = 1ull << 30;  // look-back words carry 30-bit values
+// The host's answer to a BINNING_SORT frame that needed `need` tile instances and overflowed its buffer: refused past the
+// limit, else the next power of two that holds the need with 25 % head-room, within [MIN, MAX]. Not learnt state: each
+// lane's buffers grow by it on their own (check_capacities), and nothing shrinks.
+struct InstanceVerdict { bool refuse; uint64_t capacity; };
+inline InstanceVerdict instance_capacity_for(uint64_t need) {
+    if (need > MAX_INSTANCE_CAPACITY) return {true, 0};
+    uint64_t cap = MIN_INSTANCE_CAPACITY;
+    while (cap < need + need / 4) cap <<= 1;
+    return {false, std::min(cap, MAX_INSTANCE_CAPACITY)};
+}
+
 // Whose sorted list a splitter table describes: the cloud (by identity and size), the camera and the settings.
 struct SortedView {
     const void* cloud;

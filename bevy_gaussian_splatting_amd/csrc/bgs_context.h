@@ -72,8 +72,7 @@ namespace bgs_host {
 
 extern thread_local std::string g_error;   // (bgs_frame.hip) the message of the calling thread's last failure: bgs_last_error(NULL)
 
-constexpr uint64_t MIN_INSTANCE_CAPACITY = 1ull << 22;  // 4M instances (32 MB per buffer)
-constexpr uint64_t MAX_INSTANCE_CAPACITY = 1ull << 30;  // look-back words carry 30-bit values
+// (MIN_INSTANCE_CAPACITY / MAX_INSTANCE_CAPACITY: adaptive_state.h, with the growth rule)
 constexpr uint32_t MAX_SPLATS = (1u << 30) - 1u;
 constexpr int EV_COUNT = BGS_STAGE_COUNT + 1;
 constexpr int EV_RING = 64;   // per-stage timings are averaged over up to this many frames per lane

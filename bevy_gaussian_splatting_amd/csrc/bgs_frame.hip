@@ -322,14 +322,12 @@ int check_capacities(bgs_ctx* ctx, Lane& L, const FrameTotals& t, int attempt, b
         *rerun = true;
     }
     if (p.render && !p.scan && h.overflow) {
-        // BINNING_SORT overflow: grow to the next power of two with 25 % headroom
-        if (t.instances > MAX_INSTANCE_CAPACITY)
+        // BINNING_SORT overflow: grow to the next power of two with 25 % headroom (instance_capacity_for, adaptive_state.h)
+        const InstanceVerdict grown = instance_capacity_for(t.instances);
+        if (grown.refuse)
             return fail(ctx, BGS_ECAPACITY,
                         "frame needs " + std::to_string(t.instances) + " tile instances, above the 2^30 limit");
-        uint64_t cap = MIN_INSTANCE_CAPACITY;
-        while (cap < t.instances + t.instances / 4) cap <<= 1;
-        cap = std::min(cap, MAX_INSTANCE_CAPACITY);
-        int rc = ensure_instances(ctx, L, cap);
+        int rc = ensure_instances(ctx, L, grown.capacity);
         if (rc != BGS_OK) return rc;
         ctx->reruns_instances += 1;
         *rerun = true;

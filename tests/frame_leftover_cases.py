@@ -102,6 +102,9 @@ class Case:
     expect: dict = field(default_factory=dict)   # plan fields the frame must report, else the case tests another path
     regions: tuple = ("part", "depth", "bin")    # the chain regions its twin must find words in
     reruns: str = ""           # adaptive counter that must have risen
+    budget: str = ""           # the cloud is this case's of tests/instance_budget_cases.py (n: its splats) instead of the seeded rows
+    sort_frames: int = 0       # BINNING_SORT frames of the same cloud and view drawn first, on the same lane: the frame read back
+                               # starts on what they left (a scratch region rebuilt for grown instance buffers, not cleaned)
 
     def settings(self) -> CloudSettings:
         extra = {"obb": {}, "aabb3d": {"aabb": True}, "surfel": {"aabb": True, "gaussian_mode": GaussianMode.Gaussian2d}}[self.shape]
@@ -117,6 +120,10 @@ _BASE = {}
 
 def cloud_of(case: Case) -> PlanarGaussian3d:
     """n splats: the rows of one 8192-splat seeded cloud repeated; all but the first `drawable` behind the camera."""
+    if case.budget:
+        import instance_budget_cases as I
+        assert len(I.built(case.budget)["cloud"]) == case.n and I.by_name(case.budget).size == case.size
+        return I.built(case.budget)["cloud"]
     if "base" not in _BASE:
         _BASE["base"] = random_gaussians_3d_seeded(8192, 77)
     b, n = _BASE["base"], case.n
@@ -155,6 +162,10 @@ CASES = (
     Case("bucket_overflow_rerun", 200000, flags=GUESSED_SPLITTERS, expect=ONESWEEP, reruns="reruns_sort"),
     Case("small_lists_rerun", 12000, size=(250, 130), flags=SMALL_LISTS | NO_BUCKET_SORT, expect=ONESWEEP, reruns="reruns_lists"),
     Case("rerun_every_frame", 12000, flags=RERUN_EVERY_FRAME | NO_BUCKET_SORT, expect=ONESWEEP),
+    # behind a BINNING_SORT frame of 2^22 + 1 tile instances (instance_budget_cases' one_over) that overflowed, grew the lane's
+    # instance buffers and its scratch region, and was re-run: the scan frame on that lane finds nothing clean and leaves it clean
+    Case("instances_overflow_rerun", 16385, size=(256, 256), flags=NO_BUCKET_SORT, budget="one_over", sort_frames=2, expect=ONESWEEP,
+         reruns="reruns_instances"),
     # kept order: the compaction's chain, no passes
     Case("kept_order", 9000, kept=True, expect={"kept": 1, "bucket": 0, "places": 0}, regions=("part", "bin")),
     # everything behind the camera: D = 0

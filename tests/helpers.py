@@ -180,6 +180,7 @@ def shim() -> ctypes.CDLL:
     viewp, setp = ctypes.POINTER(BgsView), ctypes.POINTER(BgsSettings)
     for name, args, res in (("shim_state_new", [], vp), ("shim_state_delete", [vp], None),
                             ("shim_frame_kind", [u32, u32, viewp, setp], u64),
+                            ("shim_instance_capacity_for", [u64, u64p], u64),
                             ("shim_state_switch_kind", [vp, u64], None), ("shim_state_settle", [vp, u64, u32], None),
                             ("shim_state_completed_early", [vp, u64], None), ("shim_state_learn_saturation", [vp, u64, u32], None),
                             ("shim_state_learn_draw_count", [vp, u32], None),

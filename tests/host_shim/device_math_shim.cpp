@@ -194,6 +194,13 @@ uint32_t shim_state_list_capacity(void* st, uint32_t n, int small_lists) { retur
 int shim_state_learn_list_capacity(void* st, uint32_t longest, uint32_t level, uint32_t capacity) {
     return ((AdaptiveState*)st)->learn_list_capacity(longest, level, capacity) ? 1 : 0;
 }
+// BINNING_SORT's growth rule: the capacity a frame that needs `need` tile instances is re-run with, 0: refused; limits[0..1]:
+// MIN_INSTANCE_CAPACITY, MAX_INSTANCE_CAPACITY
+uint64_t shim_instance_capacity_for(uint64_t need, uint64_t* limits) {
+    if (limits) { limits[0] = MIN_INSTANCE_CAPACITY; limits[1] = MAX_INSTANCE_CAPACITY; }
+    const InstanceVerdict v = instance_capacity_for(need);
+    return v.refuse ? 0ull : v.capacity;
+}
 // returns moved | changed << 1
 int shim_state_learn_level(void* st, uint64_t kind, uint32_t lv, const uint32_t* edges, uint64_t instances, uint32_t visible, uint32_t longest) {
     const AdaptiveState::LevelVerdict v = ((AdaptiveState*)st)->learn_level(kind, lv, edges, instances, visible, longest);

@@ -189,6 +189,60 @@ def test_first_list_capacity_is_a_guess_from_the_cloud_size():
     assert small.list_capacity(1_000_000, 1) == 64 and small.get()["coarse_cap_hint"] == 64
 
 
+# ---- tile-instance capacity (BINNING_SORT) ---------------------------------------------------------------------------------
+
+MIN_INSTANCES, MAX_INSTANCES = 1 << 22, 1 << 30
+
+
+def instance_want(need: int):
+    """The growth rule as check_capacities documents it: refused (None) past 2^30, else the next power of two from 2^22
+    that holds the need and a quarter of it (integer division), never more than 2^30."""
+    if need > MAX_INSTANCES:
+        return None
+    return min(next(1 << k for k in range(22, 64) if (1 << k) >= need + need // 4), MAX_INSTANCES)
+
+
+def instance_capacity_for(need: int):
+    limits = (ctypes.c_uint64 * 2)()
+    cap = int(helpers.shim().shim_instance_capacity_for(need, limits))
+    assert (int(limits[0]), int(limits[1])) == (MIN_INSTANCES, MAX_INSTANCES)
+    return cap or None
+
+
+def test_instance_capacity_grows_to_a_power_of_two_with_a_quarter_of_head_room_and_refuses_past_2_pow_30():
+    def fits(k):   # the largest need a capacity of 2^k serves: need + need // 4 <= 2^k, 2^k / 1.25 rounded as the rule rounds
+        need = (1 << k) * 4 // 5
+        while need + 1 + (need + 1) // 4 <= 1 << k:
+            need += 1
+        assert need + need // 4 <= 1 << k < need + 1 + (need + 1) // 4 and abs(need - (1 << k) / 1.25) <= 1
+        return need
+    fits_22, fits_23, fits_30 = fits(22), fits(23), fits(30)
+    expected = {
+        0: 1 << 22, 1: 1 << 22,
+        fits_22: 1 << 22, fits_22 + 1: 1 << 23,                 # 1.25 x need across 2^22, both ways
+        (1 << 22) - 1: 1 << 23, 1 << 22: 1 << 23, (1 << 22) + 1: 1 << 23,
+        (1 << 22) * 5 // 4: 1 << 23,                                     # a need of 1.25 x 2^22
+        fits_23: 1 << 23, fits_23 + 1: 1 << 24,                          # 1.25 x need across 2^23, both ways
+        (1 << 23) + 1: 1 << 24, (1 << 23) * 5 // 4: 1 << 24, (1 << 23) * 5 // 4 + 1: 1 << 24,
+        fits_30 - 1: 1 << 30, fits_30: 1 << 30,
+        fits_30 + 1: 1 << 30,                                            # 2^31 by the rule, held to the limit: the need still fits
+        (1 << 30) - 1: 1 << 30, 1 << 30: 1 << 30,
+        (1 << 30) + 1: None, (1 << 30) + 65536: None, (1 << 32) + 65536: None, (1 << 64) - 1: None,
+    }
+    for need, want in expected.items():
+        assert instance_want(need) == want, need          # the transcription says what the table says
+        assert instance_capacity_for(need) == want, f"need {need}: {instance_capacity_for(need)}, expected {want}"
+    # the head-room is there: without it these needs would keep the smaller power of two
+    for need in (fits_22 + 1, fits_23 + 1, 1 << 23):
+        assert instance_capacity_for(need) >= 2 * next(1 << k for k in range(22, 31) if (1 << k) >= need)
+    rng = np.random.default_rng(22)
+    for need in (int(v) for v in rng.integers(0, (1 << 30) + (1 << 20), 2000)):
+        cap = instance_capacity_for(need)
+        assert cap == instance_want(need), need
+        if cap is not None:
+            assert cap >= need and cap & (cap - 1) == 0 and MIN_INSTANCES <= cap <= MAX_INSTANCES
+
+
 # ---- bucket back-off -------------------------------------------------------------------------------------------------------
 
 def test_bucket_overflow_backs_off_by_tables_that_failed_in_a_row():

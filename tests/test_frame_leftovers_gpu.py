@@ -34,7 +34,7 @@ def ctx():
 
 
 def _handle(p, case):
-    key = (case.n, case.drawable)
+    key = (case.n, case.drawable, case.budget)
     if key not in p.handles:
         p.handles[key] = p.upload(L.cloud_of(case))
     return p.handles[key]
@@ -75,6 +75,10 @@ def run_case(p, case, extra_flags=0, handle=None, reset=True):
             # what it taught the context is forgotten, so that the frames below start where the clean-up run's did
             p.render(h, v, s, download=False, entries=chunk)
             p.reset_adaptive_state()
+        for f in range(case.sort_frames):
+            p.set_binning("sort")
+            p.render(h, v, s, download=False, entries=chunk)
+            p.set_binning("scan")
         for f in range(case.warm + 1):
             if case.graphs:
                 p.set_profiling(0)
