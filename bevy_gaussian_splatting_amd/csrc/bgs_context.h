@@ -74,7 +74,11 @@ extern thread_local std::string g_error;   // (bgs_frame.hip) the message of the
 
 // (MIN_INSTANCE_CAPACITY / MAX_INSTANCE_CAPACITY: adaptive_state.h, with the growth rule)
 constexpr uint32_t MAX_SPLATS = (1u << 30) - 1u;
-constexpr int EV_COUNT = BGS_STAGE_COUNT + 1;
+// The stage events of a timed frame, each recorded behind the stage it is named for (issue_frame marks, collect_stats
+// reads): a sort-only frame ends at MARK_SORT, a BINNING_SCAN render has no MARK_TILE_SORT / MARK_RANGES.
+enum StageMark : int { MARK_BEGIN, MARK_FRONT, MARK_SORT, MARK_PROJECT, MARK_TILE_SORT, MARK_RANGES, MARK_RASTER, EV_COUNT };
+static_assert(EV_COUNT == BGS_STAGE_COUNT + 1, "one event per stage boundary");
+inline StageMark last_mark(bool render) { return render ? MARK_RASTER : MARK_SORT; }
 constexpr int EV_RING = 64;   // per-stage timings are averaged over up to this many frames per lane
 constexpr int MAX_LANES = 8;
 
@@ -129,8 +133,8 @@ struct FrameInputs {
     float pos_min[3] = {0.0f, 0.0f, 0.0f}, pos_max[3] = {0.0f, 0.0f, 0.0f};
 };
 
-// Every choice of one frame (plan_frame, bgs_frame.hip): enqueue_frame allocates, binds and issues it, finish_lane reads
-// it back when the frame is complete.
+// Every choice of one frame (plan_frame, bgs_frame.hip): enqueue_frame allocates, binds (FrameBindings) and issues it,
+// finish_lane reads it back when the frame is complete.
 struct FramePlan {
     FrameParams fp{};               // what keygen hands the frame's kernels (debug flags, sRGB8 target, sort path included)
     bool render = false, scan = false, surfel = false, culled_tail = true;   // (culled_tail: keygen writes the culled tail)
@@ -152,7 +156,7 @@ struct FramePlan {
     uint32_t out_format = 0, ntiles = 0;
     bool raster_cleans = false;     // the rasteriser zeroes the scratch region and reports the Control block (FrameCleanup)
     RasterInst raster{};            // the instantiation launch_raster_scan launches (launch_raster: its variant, samples, depth, overlay)
-    ProjectInst project{};          // the instantiation of the vertex stage (launch_project_bin / launch_project_emit)
+    ProjectInst project{};          // the instantiation of the vertex stage (ProjectLaunch / ProjectEmitLaunch)
     // heavy-tile strips; leaves tile costs / draws in cost order / makes that order anew; the kind of the cost plane
     // behind its order, whose saturation counts the frame reports (0: none); may replay a captured graph
     bool heavy = false, cost = false, ordered = false, refresh = false, graph_ok = false;
@@ -162,6 +166,37 @@ struct FramePlan {
     uint8_t ev_kind() const { return (uint8_t)(!render ? 1 : (scan ? 2 : 3) + (kept ? 2 : 0)); }
     struct EvKind { bool render, scan, kept; };
     static EvKind decode_ev_kind(uint8_t kind) { return {kind != 1, kind == 2 || kind == 4, kind >= 4}; }
+};
+
+// A frame's device memory: which pointer of the lane (and of its scratch region, ScratchLayout) each kernel argument is,
+// and the frame's stage launches filled from them and prepared. bind_frame (bgs_frame.hip) makes it from the lane, the
+// plan and the inputs, without a HIP call or a change of state; issue_frame launches from it, graph_key and the lane's
+// bookkeeping read it. Of the stage launches only those of the frame's path are filled (the others launch nothing).
+struct FrameBindings {
+    Control* ctl = nullptr;          // this frame's Control block, by the lane's parity (the other one: raster_scan.cleanup)
+    uint32_t* part_status = nullptr;   // the front kernel's chain
+    uint32_t* depth_status = nullptr;  // the depth passes' look-back words
+    uint2* ranges = nullptr;         // BINNING_SORT: [start, end) per tile
+    uint2* draw_list = nullptr;      // the sorted draw list: entries[places & 1], the passes ping-pong from entries[0]
+    uint32_t final_xor = 0;          // SortMode::Rayon / Std sort ascending on the inverted key; the last step of either path un-inverts it
+    // the tile feedback (TileFeedback): the cost plane the frame makes its order of (only a frame that makes it anew) and the
+    // order; what the rasteriser reads and leaves is in raster_scan (heavy_in: only a completed buffer of the same grid
+    // that is not the one being written)
+    const uint16_t* cost_in = nullptr;
+    uint16_t* tile_order = nullptr;
+    // the lane's buffers that the short launchers and the front launch take
+    uint2* bucket_slots = nullptr;
+    uint32_t* split_keys = nullptr;          // a long splitter table as keygen reads it, and the pinned staging it is copied from
+    uint32_t* split_keys_staging = nullptr;
+    FrameParams* d_fp = nullptr;
+    float4* fb = nullptr;
+    uint32_t* fb8 = nullptr;
+    OnesweepLaunch depth, tile_sort;     // the digit passes of the depth keys; BINNING_SORT: of the tile ids
+    ProjectLaunch project;               // BINNING_SCAN
+    BinLaunch bin;
+    RasterScanLaunch raster_scan;        // (its cleanup: the frame's FrameCleanup)
+    ProjectEmitLaunch project_emit;      // BINNING_SORT
+    RasterLaunch raster;
 };
 
 // The tile feedback a lane's BINNING_SCAN frames leave for its next ones: balance only, every tile is drawn exactly once
@@ -290,7 +325,8 @@ struct Lane {
         uint64_t stamp = 0;       // bgs_ctx::grid_stamps when it was written (0: never)
         Grids() = default;
         Grids(uint64_t stamp_, uint32_t n_, uint32_t cap_) : n(n_), cap(cap_), stamp(stamp_) {}   // a report of its own stamp: ++ctx->grid_stamps
-        void launched(Kernel k, uint32_t items_per_tile, uint32_t workgroups) { per_tile[k] = items_per_tile; blocks[k] = workgroups; }
+        // what a prepared launch struct (kernels.h) launches, or would: a captured frame's replay runs what was prepared
+        template <class Launch> void launched(Kernel k, const Launch& l) { if (l.blocks) { per_tile[k] = l.per_tile; blocks[k] = l.blocks; } }
     } grids;
 
     bgs_stats result{};      // counters of the last completed frame of this lane (no timings)

@@ -57,21 +57,19 @@ int bgs_radix_sort_pairs(bgs_ctx* ctx, bgs_sort_entry* entries, uint32_t n, uint
     HIP_TRY(ctx, hipMemcpyAsync(L.entries[0].ptr, entries, (size_t)n * sizeof(uint2), hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)&ctl->splat_count, (int)n, 1, st));
     launch_histogram(st, L.entries[0].ptr, n, &ctl->hist_depth[0][0], passes);
-    const bool large = n > (4u << 20);
+    OnesweepLaunch sort;
+    sort.lists[0] = L.entries[0].ptr; sort.lists[1] = L.entries[1].ptr;
+    sort.n_ptr = &ctl->splat_count; sort.max_n = n;
+    sort.hist = ctl->hist_depth; sort.status = depth_status; sort.status_stride = L.layout.pass_stride;
+    sort.ctl = ctl; sort.first_ticket = TICKET_DEPTH; sort.passes = passes; sort.large_tiles = n > (4u << 20);
     // the frames' default grid, under the context's grid cap (bgs_set_grid_cap); what was launched: bgs_debug_frame_grids
-    const int max_blocks = grid_under_cap(ctx->num_cus * 4, ctx->grid_cap);
+    sort.prepare(grid_under_cap(ctx->num_cus * 4, ctx->grid_cap));
     Lane::Grids& g = L.grids = Lane::Grids(++ctx->grid_stamps, n, ctx->grid_cap);
-    g.launched(g.DEPTH, sort_tile_size(large), capped_grid(n, sort_tile_size(large), max_blocks));
+    g.launched(g.DEPTH, sort);
     g.count[g.DEPTH] = g.HOST_N;
-    int cur = 0;
-    for (uint32_t p = 0; p < passes; ++p) {
-        launch_onesweep_pass(st, L.entries[cur].ptr, L.entries[cur ^ 1].ptr, &ctl->splat_count, n, ctl->hist_depth[p],
-                             depth_status + (size_t)p * L.layout.pass_stride, &ctl->ticket[p][0], &ctl->error,
-                             p * RADIX_BITS, 0u, large, max_blocks);
-        cur ^= 1;
-    }
+    sort.launch(st);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(entries, L.entries[cur].ptr, (size_t)n * sizeof(uint2), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(entries, L.entries[passes & 1u].ptr, (size_t)n * sizeof(uint2), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipMemcpyAsync(L.h_ctl.ptr, ctl, sizeof(Control), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     if (L.h_ctl.ptr->error) return fail(ctx, BGS_EINTERNAL, "device watchdog tripped in radix sort");
@@ -239,9 +237,11 @@ int bgs_selftest_bin(bgs_ctx* ctx, const uint32_t* host_rects, uint32_t n, uint3
     cs.fill(lists_buf.ptr, 0xFF, (size_t)list_words * sizeof(uint32_t));
     cs.up(rects_buf.ptr, host_rects, (size_t)n * sizeof(uint32_t));
     cs.word(&ctl->draw_count, n);
-    if (cs.ok)
-        launch_bin(st, rects_buf.ptr, ctl, status_buf.ptr, lists_buf.ptr, coarse_cap, supertile_mul(sup_edge), sup_x, sup_y,
-                   /*ticket_slot=*/4, blocks, wide != 0u);
+    BinLaunch bin;
+    bin.rects = rects_buf.ptr; bin.ctl = ctl; bin.bin_status = status_buf.ptr; bin.coarse = lists_buf.ptr;
+    bin.coarse_cap = coarse_cap; bin.sup_edge = sup_edge; bin.tiles_x = tiles_x; bin.tiles_y = tiles_y;
+    bin.wide = wide != 0u; bin.blocks = blocks;   // (the caller's grid)
+    if (cs.ok) bin.launch(st);
     cs.launched();
     cs.down(host_lists, lists_buf.ptr, (size_t)list_words * sizeof(uint32_t));
     cs.down(host_totals, ctl->coarse_total, sizeof ctl->coarse_total);
@@ -453,7 +453,7 @@ int bgs_debug_frame_leftovers(bgs_ctx* ctx, void* host_scratch, uint64_t scratch
     return BGS_OK;
 }
 
-// What the last frame's persistent kernels launched (Lane::Grids, filled by enqueue_frame with the launchers' own formula) and
+// What the last frame's persistent kernels launched (Lane::Grids, filled by enqueue_frame from the frame's launch structs) and
 // the tiles of work they had: of n for the front kernel, of the completed frame's Control copy for the kernels whose count
 // only the device knew (draw_count, voided by sort_overflow as the kernels read it; instance_count).
 int bgs_debug_frame_grids(bgs_ctx* ctx, uint32_t* out, uint32_t capacity) {
@@ -587,7 +587,7 @@ int bgs_selftest_keygen_buckets(bgs_ctx* ctx, const bgs_cloud* cloud, const bgs_
     kg.ctl = ctl;
     kg.part_status = status_buf.ptr;
     kg.places = 4u;
-    kg.ticket_slot = 7u;
+    kg.ticket_slot = TICKET_FRONT;
     kg.bucket_slots = slots_buf.ptr;
     if (sub <= BUCKET_SUB_KERNARG) std::memcpy(kg.split.key, host_splitters, (size_t)nkeys * sizeof(uint32_t));
     kg.split.device_keys = keys_buf.ptr;
@@ -596,7 +596,7 @@ int bgs_selftest_keygen_buckets(bgs_ctx* ctx, const bgs_cloud* cloud, const bgs_
     kg.wide = alone != 0u;
     if (!kg.prepare(grid_under_cap(ctx->num_cus * 4, ctx->grid_cap))) return fail(ctx, BGS_EINTERNAL, "keygen self-test: nothing to launch");
     Lane::Grids& g = ctx->lanes[0].grids = Lane::Grids(++ctx->grid_stamps, n, ctx->grid_cap);   // (the culled list is the call's own: no tail)
-    g.launched(g.FRONT, keygen_tile_splats(n), kg.blocks);
+    g.launched(g.FRONT, kg);
     g.front_chainless = !ordered;
     CommandStream cs(st);
     cs.zero(ctl, sizeof(Control));
@@ -766,14 +766,19 @@ int bgs_selftest_raster(bgs_ctx* ctx, const bgs_raster_selftest* in, float* host
     if (!instances.empty()) cs.up(inst_buf.ptr, instances.data(), instances.size() * sizeof(uint2));
     if (in->depth) cs.up(depth_buf.ptr, in->depth, depth_floats * sizeof(float));
     if (in->order) cs.up(order_buf.ptr, in->order, (size_t)nblocks * sizeof(uint16_t));
-    if (cs.ok) {
-        const bool exits = in->mode != 0u;
-        if (cs.check(launch_raster_scan(st, fp, inst, fp_buf.ptr, rec_buf.ptr, lists_buf.ptr, cap, in->sup_edge, ctl, reinterpret_cast<float4*>(scan_buf.ptr),
-                                        /*srgb8_default=*/nullptr, /*out_format=*/0u, FrameCleanup{}, /*tile_trace=*/nullptr,
-                                        exits && in->heavy_count ? heavy_in_buf.ptr : nullptr, exits ? heavy_out_buf.ptr : nullptr,
-                                        in->order ? order_buf.ptr : nullptr, cost_buf.ptr)))
-            cs.check(launch_raster(st, fp, inst, rec_buf.ptr, inst_buf.ptr, ranges_buf.ptr, reinterpret_cast<float4*>(sort_buf.ptr), in->clear, ctl));
-    }
+    const bool exits = in->mode != 0u;
+    RasterScanLaunch scan;
+    scan.inst = inst; scan.d_fp = fp_buf.ptr; scan.tiles_x = tiles_x; scan.tiles_y = tiles_y;
+    scan.records = rec_buf.ptr; scan.coarse = lists_buf.ptr; scan.coarse_cap = cap; scan.sup_edge = in->sup_edge;
+    scan.ctl = ctl; scan.framebuffer = reinterpret_cast<float4*>(scan_buf.ptr);
+    scan.heavy_in = exits && in->heavy_count ? heavy_in_buf.ptr : nullptr;
+    scan.heavy_out = exits ? heavy_out_buf.ptr : nullptr;
+    scan.order = in->order ? order_buf.ptr : nullptr;
+    scan.cost_out = cost_buf.ptr;
+    RasterLaunch sort;
+    sort.fp = &fp; sort.inst = inst; sort.records = rec_buf.ptr; sort.instances = inst_buf.ptr; sort.ranges = ranges_buf.ptr;
+    sort.framebuffer = reinterpret_cast<float4*>(sort_buf.ptr); sort.clear_color = in->clear; sort.ctl = ctl;
+    if (cs.ok && cs.check(scan.launch(st))) cs.check(sort.launch(st));
     cs.launched();
     cs.down(host_scan, scan_buf.ptr, (size_t)image_floats * sizeof(float));
     cs.down(host_sort, sort_buf.ptr, (size_t)image_floats * sizeof(float));

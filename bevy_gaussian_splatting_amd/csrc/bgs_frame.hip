@@ -477,7 +477,6 @@ int collect_stats(bgs_ctx* ctx) {
     if (ctx->profiling >= 1) {
         const uint8_t kind = R.result_kind;
         const auto [render, scan, kept] = FramePlan::decode_ev_kind(kind);
-        const int last = render ? 6 : 2;
         uint32_t used = 0;
         float acc[BGS_STAGE_COUNT] = {0, 0, 0, 0, 0, 0}, acc_total = 0.0f;
         for (auto& L : ctx->lanes) {
@@ -486,22 +485,22 @@ int collect_stats(bgs_ctx* ctx) {
                 const uint32_t slot = (L.ev_head + EV_RING - f) % EV_RING;
                 if (L.ev_kind[slot] != kind) continue;
                 hipEvent_t* const ev = L.ev_ring[slot];
-                auto ms = [&](int a, int b) { float t = 0; (void)hipEventElapsedTime(&t, ev[a], ev[b]); return t; };
+                auto ms = [&](StageMark a, StageMark b) { float t = 0; (void)hipEventElapsedTime(&t, ev[a], ev[b]); return t; };
                 if (ctx->profiling >= 2) {
                     // (a kept order: the compaction is the whole front end, there is no depth sort)
-                    acc[BGS_STAGE_KEYGEN] += kept ? ms(0, 2) : ms(0, 1);
-                    acc[BGS_STAGE_DEPTH_SORT] += kept ? 0.0f : ms(1, 2);
+                    acc[BGS_STAGE_KEYGEN] += kept ? ms(MARK_BEGIN, MARK_SORT) : ms(MARK_BEGIN, MARK_FRONT);
+                    acc[BGS_STAGE_DEPTH_SORT] += kept ? 0.0f : ms(MARK_FRONT, MARK_SORT);
                     if (render && scan) {
-                        acc[BGS_STAGE_PROJECT] += ms(2, 3);
-                        acc[BGS_STAGE_RASTER] += ms(3, 6);
+                        acc[BGS_STAGE_PROJECT] += ms(MARK_SORT, MARK_PROJECT);
+                        acc[BGS_STAGE_RASTER] += ms(MARK_PROJECT, MARK_RASTER);
                     } else if (render) {
-                        acc[BGS_STAGE_PROJECT] += ms(2, 3);
-                        acc[BGS_STAGE_TILE_SORT] += ms(3, 4);
-                        acc[BGS_STAGE_RANGES] += ms(4, 5);
-                        acc[BGS_STAGE_RASTER] += ms(5, 6);
+                        acc[BGS_STAGE_PROJECT] += ms(MARK_SORT, MARK_PROJECT);
+                        acc[BGS_STAGE_TILE_SORT] += ms(MARK_PROJECT, MARK_TILE_SORT);
+                        acc[BGS_STAGE_RANGES] += ms(MARK_TILE_SORT, MARK_RANGES);
+                        acc[BGS_STAGE_RASTER] += ms(MARK_RANGES, MARK_RASTER);
                     }
                 }
-                acc_total += ms(0, last);
+                acc_total += ms(MARK_BEGIN, last_mark(render));
                 ++used;
             }
             L.frames_timed = 0;
@@ -673,61 +672,6 @@ FramePlan plan_frame(const bgs_ctx& ctx, const Lane& L, const FrameInputs& in) {
     return p;
 }
 
-// What the launches of a captured frame depend on besides FrameParams: the plan's choices and the buffers they were
-// bound to. Nothing that changes from frame to frame (the splitter slot, its epoch, a kept order's chunk: the front node's
-// update carries them). `front`: the prepared KeygenLaunch or EntriesLaunch, whose kernel and grid the node keeps.
-template <class Front>
-GraphKey graph_key(const FramePlan& p, const FrameInputs& in, const Lane& L, const Front& front, uint32_t coarse_cap) {
-    GraphKey key;
-    std::memset(&key, 0, sizeof key);
-    const FrameParams& fp = p.fp;
-    const void* planes[6] = {in.cloud->ptrs.position_visibility, in.cloud->ptrs.packed, nullptr, nullptr, nullptr, nullptr};
-    std::memcpy(key.cloud, planes, sizeof planes);
-    const void* bufs[11] = {L.entries[0].ptr, L.entries[1].ptr, L.culled.ptr, L.records.ptr, L.coarse.ptr, L.fb.ptr, L.fb8.ptr,
-                            L.scratch.ptr, L.d_fp.ptr, L.h_ctl_dev, L.bucket_slots.ptr};   // (L.rects lives and dies with L.entries: ensure_entries)
-    std::memcpy(key.bufs, bufs, sizeof bufs);
-    key.n = p.n; key.places = p.places; key.sort_mode = in.settings.sort_mode;
-    key.project = p.project.key(); key.raster = p.raster.key(); key.srgb8 = p.out_format;
-    key.debug_flags = in.debug_flags;
-    key.width = fp.width; key.height = fp.height;
-    key.sort_blocks = p.bucket ? 0 : p.sort_blocks;  // the bucket sort's grid is fixed
-    key.bin_blocks = p.bin_blocks * 4096 + p.binning_blocks;   // (the bin kernel's shape follows the pipeline depth, as keygen's does: key.front_threads)
-    key.front_blocks = (int32_t)front.blocks; key.front_func = front.func; key.front_threads = front.threads;   // (kept: entries_blocks(n) of the compaction)
-    key.wide_bin = p.wide_bin ? 1u : 0u;
-    key.split_sub = p.split_sub_out;   // (round 5's advisor: a replay across a 524 k-pair step of the hint left a table of the captured sub under the new sub's label)
-    key.sup_edge = p.sup_edge;
-    key.scratch = L.layout;
-    key.coarse_cap = coarse_cap;
-    key.sort_path = p.bucket ? (p.bucket_sub | (p.wide ? 0x100u : 0u)) : 0u;   // (the bucket sort's grid and instantiation and keygen's dynamic LDS follow it)
-    return key;
-}
-
-// Replay the graph G of this key (its front node updated to this frame), or capture `issue` into a new one.
-template <class Front, class Issue>
-int launch_graph(bgs_ctx* ctx, Lane& L, FrameGraph& G, const GraphKey& key, Front& front, Issue&& issue) {
-    if (G.exec && std::memcmp(&G.key, &key, sizeof key) == 0) {
-        HIP_TRY(ctx, front.update_node(G.exec, G.front_node));
-        ctx->graph_replays += 1;
-    } else {
-        graph_destroy(G);
-        HIP_TRY(ctx, hipStreamBeginCapture(L.stream, hipStreamCaptureModeThreadLocal));
-        const hipError_t ie = issue();
-        const hipError_t ce = hipStreamEndCapture(L.stream, &G.graph);
-        size_t roots = 1;
-        if (ie != hipSuccess || ce != hipSuccess || !G.graph ||
-            hipGraphInstantiate(&G.exec, G.graph, nullptr, nullptr, 0) != hipSuccess ||
-            hipGraphGetRootNodes(G.graph, &G.front_node, &roots) != hipSuccess || roots != 1) {
-            graph_destroy(G);
-            (void)hipGetLastError();
-            return fail(ctx, BGS_EHIP, "capturing the frame into a hipGraph failed");
-        }
-        G.key = key;
-        ctx->graph_captures += 1;
-    }
-    HIP_TRY(ctx, hipGraphLaunch(G.exec, L.stream));
-    return BGS_OK;
-}
-
 // The buffers a planned frame needs (allocated or grown); *coarse_cap: the entries per supertile list it gets.
 int ensure_frame_buffers(bgs_ctx* ctx, Lane& L, const FramePlan& p, const FrameInputs& in, uint32_t* coarse_cap) {
     int rc;
@@ -751,63 +695,114 @@ int ensure_frame_buffers(bgs_ctx* ctx, Lane& L, const FramePlan& p, const FrameI
     return BGS_OK;
 }
 
-// Enqueue one frame on lane L: plan it, allocate, bind, commit its context changes, issue it, and keep its inputs and
-// plan in the lane. Returns without waiting; the caller decides when to finish the lane.
-int enqueue_frame(bgs_ctx* ctx, Lane& L, const FrameInputs& in) {
-    // ---- 1. the frame's choices
-    const FramePlan p = plan_frame(*ctx, L, in);
+// Step 3 of enqueue_frame: the frame's device memory (FrameBindings, bgs_context.h). The one place that does arithmetic on
+// the lane's scratch region and that says which buffer is which argument of which stage. No HIP call, no change of state.
+FrameBindings bind_frame(const Lane& L, const FramePlan& p, const FrameInputs& in, uint32_t coarse_cap, uint4* tile_trace) {
+    FrameBindings b;
     const FrameParams& fp = p.fp;
-    const uint32_t n = p.n, places = p.places, flags = in.debug_flags;
-    const bool render = p.render, scan = p.scan, bucket = p.bucket;
-
-    // ---- 2. buffers
-    uint32_t coarse_cap = 1;  // entries per supertile list
-    int rc = ensure_frame_buffers(ctx, L, p, in, &coarse_cap);
-    if (rc != BGS_OK) return rc;
-
-    // ---- 3. bindings
-    hipStream_t st = L.stream;
-    const bool need_memset = !L.scratch_clean;  // else the previous frame's rasteriser left it zeroed
-    if (need_memset) L.ctl_parity = 0;
     const ScratchLayout& lay = L.layout;
     uint8_t* const scratch = L.scratch.ptr;
-    Control* ctl = (Control*)(scratch + (L.ctl_parity ? lay.off_ctl1 : 0));
-    uint32_t* depth_status = (uint32_t*)(scratch + lay.off_depth_status);
-    unsigned long long* scan_status = (unsigned long long*)(scratch + lay.off_scan_status);
-    uint32_t* tile_status = (uint32_t*)(scratch + lay.off_tile_status);
-    uint2* ranges = (uint2*)(scratch + lay.off_ranges);
-    uint32_t* bin_status = (uint32_t*)(scratch + lay.off_bin_status);
-    uint32_t* part_status = (uint32_t*)(scratch + lay.off_part_status);
-    TileFeedback& F = L.feedback;
-    uint8_t* const heavy_out = p.heavy ? F.heavy[F.heavy_parity].ptr : nullptr;
-    const uint8_t* const heavy_in = (p.heavy && F.heavy_done && F.heavy_done != heavy_out && F.heavy_done_grid == tile_grid_word(fp)) ? F.heavy_done : nullptr;
-    uint16_t* const cost_out = p.cost ? F.cost[F.cost_parity].ptr : nullptr;
-    const uint16_t* const cost_in = p.refresh ? F.cost_done : nullptr;
-    uint16_t* const tile_order = p.ordered ? F.order.ptr : nullptr;
-    uint2* const draw_list = L.entries[places & 1u].ptr;  // the passes ping-pong from entries[0]
-    // SortMode::Rayon / Std sort ascending on the inverted key; the last step of either path un-inverts it
-    const uint32_t final_xor = (fp.sort_mode == BGS_SORT_RAYON || fp.sort_mode == BGS_SORT_STD) ? 0xFFFFFFFFu : 0u;
+    Control* const ctl = b.ctl = (Control*)(scratch + (L.ctl_parity ? lay.off_ctl1 : 0));
+    b.part_status = (uint32_t*)(scratch + lay.off_part_status);
+    b.depth_status = (uint32_t*)(scratch + lay.off_depth_status);
+    b.ranges = (uint2*)(scratch + lay.off_ranges);
+    b.draw_list = L.entries[p.places & 1u].ptr;
+    b.final_xor = (fp.sort_mode == BGS_SORT_RAYON || fp.sort_mode == BGS_SORT_STD) ? 0xFFFFFFFFu : 0u;
+    const TileFeedback& F = L.feedback;
+    b.cost_in = p.refresh ? F.cost_done : nullptr;
+    b.tile_order = p.ordered ? F.order.ptr : nullptr;
+    b.bucket_slots = L.bucket_slots.ptr;
+    b.split_keys = L.d_split_keys.ptr;
+    b.split_keys_staging = L.h_split_keys.ptr;
+    b.d_fp = L.d_fp.ptr;
+    b.fb = L.fb.ptr;
+    b.fb8 = L.fb8.ptr;
+    if (!p.bucket && p.places > 0) {
+        // only the V' drawable entries are sorted; the culled tail is already in its final order
+        OnesweepLaunch& d = b.depth;
+        d.lists[0] = L.entries[0].ptr; d.lists[1] = L.entries[1].ptr;
+        d.n_ptr = &ctl->draw_count; d.max_n = p.n;
+        d.hist = ctl->hist_depth; d.status = b.depth_status; d.status_stride = lay.pass_stride;
+        d.ctl = ctl; d.first_ticket = TICKET_DEPTH; d.passes = p.places; d.final_xor = b.final_xor; d.large_tiles = p.large;
+        d.prepare(p.sort_blocks);
+    }
+    if (p.render && p.scan) {
+        ProjectLaunch& v = b.project;
+        v.inst = p.project; v.d_fp = b.d_fp; v.cloud = in.cloud->ptrs; v.draw_list = b.draw_list; v.culled = L.culled.ptr;
+        v.ctl = ctl; v.records = L.records.ptr; v.rects = L.rects.ptr;
+        v.prepare(p.n, p.bin_blocks);
+        BinLaunch& bin = b.bin;
+        bin.rects = L.rects.ptr; bin.ctl = ctl; bin.bin_status = (uint32_t*)(scratch + lay.off_bin_status);
+        bin.coarse = L.coarse.ptr; bin.coarse_cap = coarse_cap; bin.sup_edge = p.sup_edge;
+        bin.tiles_x = (uint32_t)fp.tiles_x; bin.tiles_y = (uint32_t)fp.tiles_y; bin.wide = p.wide_bin;
+        bin.prepare(p.n, p.binning_blocks);
+        RasterScanLaunch& r = b.raster_scan;
+        r.inst = p.raster; r.d_fp = b.d_fp; r.tiles_x = bin.tiles_x; r.tiles_y = bin.tiles_y;
+        r.records = L.records.ptr; r.coarse = L.coarse.ptr; r.coarse_cap = coarse_cap; r.sup_edge = p.sup_edge;
+        r.ctl = ctl; r.framebuffer = b.fb; r.srgb8_default = b.fb8;
+        r.out_format = (in.debug_flags & BGS_DEBUG_SEPARATE_ENCODE) ? 0u : p.out_format;
+        r.tile_trace = tile_trace;
+        // (p.heavy, p.cost and p.ordered are of BINNING_SCAN renders only: plan_frame)
+        r.heavy_out = p.heavy ? F.heavy[F.heavy_parity].ptr : nullptr;
+        r.heavy_in = (p.heavy && F.heavy_done && F.heavy_done != r.heavy_out && F.heavy_done_grid == tile_grid_word(fp)) ? F.heavy_done : nullptr;
+        r.cost_out = p.cost ? F.cost[F.cost_parity].ptr : nullptr;
+        r.order = b.tile_order;
+        if (p.raster_cleans) {
+            FrameCleanup& cl = r.cleanup;
+            cl.part_status = b.part_status;
+            cl.depth_status = b.depth_status;
+            cl.bin_status = bin.bin_status;
+            cl.other_ctl = (Control*)(scratch + (L.ctl_parity ? 0 : lay.off_ctl1));
+            cl.host_ctl = L.h_ctl_dev;
+            cl.pass_stride = lay.pass_stride;
+            cl.places = p.bucket ? 0u : p.places;
+            cl.depth_tile = sort_tile_size(p.large);
+            cl.sorted = b.draw_list;
+            cl.key_xor = b.final_xor;
+            cl.split_sub = p.split_sub_out;
+            if (b.tile_order) cl.order_stats = reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(b.tile_order) + tile_order_stats_offset(p.ntiles));
+        }
+    } else if (p.render) {
+        const uint32_t capacity = (uint32_t)std::min<uint64_t>(L.inst[0].capacity, MAX_INSTANCE_CAPACITY);
+        ProjectEmitLaunch& v = b.project_emit;
+        v.fp = &fp; v.inst = p.project; v.cloud = in.cloud->ptrs; v.draw_list = b.draw_list; v.culled = L.culled.ptr;
+        v.ctl = ctl; v.scan_status = (unsigned long long*)(scratch + lay.off_scan_status);
+        v.records = L.records.ptr; v.instances = L.inst[0].ptr; v.capacity = capacity;
+        v.prepare(p.emit_blocks);
+        OnesweepLaunch& t = b.tile_sort;
+        t.lists[0] = L.inst[0].ptr; t.lists[1] = L.inst[1].ptr;
+        t.n_ptr = &ctl->instance_count; t.max_n = capacity;
+        t.hist = ctl->hist_tile; t.status = (uint32_t*)(scratch + lay.off_tile_status); t.status_stride = (size_t)lay.inst_tiles * RADIX_BASE;
+        t.ctl = ctl; t.first_ticket = TICKET_TILE; t.passes = 2u; t.large_tiles = true;
+        t.prepare(p.tile_sort_blocks);
+        RasterLaunch& r = b.raster;
+        r.fp = &fp; r.inst = p.raster; r.records = L.records.ptr; r.instances = L.inst[0].ptr; r.ranges = b.ranges;
+        r.framebuffer = b.fb; r.clear_color = in.view.clear_color; r.ctl = ctl;
+    }
+    return b;
+}
 
-    KeygenLaunch kg{};
-    kg.fp = fp;
+// The front end of a sorting frame: keygen on the frame's bindings, with the splitter table of a bucket frame's slot (a long
+// one goes through the lane's pinned staging: the lane's previous frame is complete, nobody reads it). false: nothing to launch.
+bool prepare_keygen(const bgs_ctx& ctx, const FramePlan& p, const FrameInputs& in, const FrameBindings& b, uint2* entries, uint2* culled, KeygenLaunch& kg) {
+    kg.fp = p.fp;
     kg.pos = in.cloud->ptrs.position_visibility;
-    kg.entries = L.entries[0].ptr;
-    kg.culled = p.culled_tail ? L.culled.ptr : nullptr;
-    kg.ctl = ctl;
-    kg.part_status = part_status;
-    kg.places = places;
-    kg.ticket_slot = 7;
-    kg.fp_out = L.d_fp.ptr;
-    kg.zero_word = reinterpret_cast<uint32_t*>(heavy_out);   // keygen, the frame's first kernel, zeroes the heavy-tile list's count
-    kg.bucket_slots = L.bucket_slots.ptr;
-    kg.bucket_status = depth_status;  // the depth passes' look-back words are free in a bucket-sort frame
-    if (bucket) {
+    kg.entries = entries;
+    kg.culled = p.culled_tail ? culled : nullptr;
+    kg.ctl = b.ctl;
+    kg.part_status = b.part_status;
+    kg.places = p.places;
+    kg.ticket_slot = TICKET_FRONT;
+    kg.fp_out = b.d_fp;
+    kg.zero_word = reinterpret_cast<uint32_t*>(b.raster_scan.heavy_out);   // keygen, the frame's first kernel, zeroes the heavy-tile list's count
+    kg.bucket_slots = b.bucket_slots;
+    kg.bucket_status = b.depth_status;  // the depth passes' look-back words are free in a bucket-sort frame
+    if (p.bucket) {
         if (p.split_slot >= 0) {
-            const SplitterKeys& tk = ctx->state.split_slots[p.split_slot].table;
+            const SplitterKeys& tk = ctx.state.split_slots[p.split_slot].table;
             const uint32_t nkeys = BUCKET_COUNT * p.bucket_sub - 1u;
-            if (p.bucket_sub <= BUCKET_SUB_KERNARG) std::memcpy(kg.split.key, tk.key, nkeys * sizeof(uint32_t));
-            else std::memcpy(L.h_split_keys.ptr, tk.key, nkeys * sizeof(uint32_t));   // (the lane's previous frame is complete: nobody reads the staging)
-            kg.split.device_keys = L.d_split_keys.ptr;
+            std::memcpy(p.bucket_sub <= BUCKET_SUB_KERNARG ? kg.split.key : b.split_keys_staging, tk.key, nkeys * sizeof(uint32_t));
+            kg.split.device_keys = b.split_keys;
         } else {  // BGS_DEBUG_GUESSED_SPLITTERS: equal steps over the 32-bit range (badly balanced)
             for (uint32_t i = 0; i < BUCKET_COUNT; ++i) kg.split.key[i] = (i + 1u) << 24;
         }
@@ -815,132 +810,167 @@ int enqueue_frame(bgs_ctx* ctx, Lane& L, const FrameInputs& in) {
         kg.split.wide = p.wide ? 1u : 0u;
     }
     kg.wide = p.wide_bin;
-    const bool have_keygen = !p.kept && kg.prepare(p.front_blocks);
-    // a kept order: the compaction in keygen's place, leaving what keygen leaves (entries_kernels.hip)
-    EntriesLaunch ek;   // (filled for a kept order only: a sorting frame's enqueue does not touch it)
-    bool have_compact = false;
-    if (p.kept) {
-        ek.fp = fp;
-        ek.entries = reinterpret_cast<const uint2*>((uintptr_t)in.view.entries_device_ptr);
-        ek.draw_list = draw_list;
-        ek.tail = kg.culled;
-        ek.ctl = ctl;
-        ek.part_status = part_status;
-        ek.ticket_slot = kg.ticket_slot;
-        ek.fp_out = L.d_fp.ptr;
-        ek.zero_word = kg.zero_word;
-        have_compact = ek.prepare(in.grid_cap);
-    }
-    FrameCleanup cl{};
-    if (p.raster_cleans) {
-        cl.part_status = part_status;
-        cl.depth_status = depth_status;
-        cl.bin_status = bin_status;
-        cl.other_ctl = (Control*)(scratch + (L.ctl_parity ? 0 : lay.off_ctl1));
-        cl.host_ctl = L.h_ctl_dev;
-        cl.pass_stride = lay.pass_stride;
-        cl.places = bucket ? 0u : places;
-        cl.depth_tile = sort_tile_size(p.large);
-        cl.sorted = draw_list;
-        cl.key_xor = final_xor;
-        cl.split_sub = p.split_sub_out;
-        if (tile_order) cl.order_stats = reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(tile_order) + tile_order_stats_offset(p.ntiles));
-    }
+    return kg.prepare(p.front_blocks);
+}
 
-    // ---- 4. the context's and the lane's state
-    ctx->state.frame_enqueued(places, p.split_slot, ctx->seq + 1);   // (split_slot: of a bucket frame only)
-    F.enqueued(p);
-    if (bucket) ctx->bucket_frames += 1;
-    else if (places > 0) ctx->onesweep_frames += 1;
+// The front end of a kept-order frame: the compaction in keygen's place, leaving what keygen leaves (entries_kernels.hip)
+bool prepare_compact(const FramePlan& p, const FrameInputs& in, const FrameBindings& b, uint2* culled, EntriesLaunch& ek) {
+    ek.fp = p.fp;
+    ek.entries = reinterpret_cast<const uint2*>((uintptr_t)in.view.entries_device_ptr);
+    ek.draw_list = b.draw_list;
+    ek.tail = p.culled_tail ? culled : nullptr;
+    ek.ctl = b.ctl;
+    ek.part_status = b.part_status;
+    ek.ticket_slot = TICKET_FRONT;
+    ek.fp_out = b.d_fp;
+    ek.zero_word = reinterpret_cast<uint32_t*>(b.raster_scan.heavy_out);
+    return ek.prepare(in.grid_cap);
+}
+
+// The stage events of one frame on its stream: all of them, the first and the last only (profiling level 1), or none
+struct StageMarks {
+    hipEvent_t* ev; hipStream_t st; int prof; StageMark last;
+    void operator()(StageMark m) const { if (prof >= 2 || (prof == 1 && (m == MARK_BEGIN || m == last))) (void)hipEventRecord(ev[m], st); }
+};
+
+// Step 4 of enqueue_frame: what enqueueing the frame changes in the context's and the lane's state, and the ring slot of
+// a timed frame's events (untimed frames do not consume one).
+StageMarks commit_frame(bgs_ctx* ctx, Lane& L, const FramePlan& p) {
+    ctx->state.frame_enqueued(p.places, p.split_slot, ctx->seq + 1);   // (split_slot: of a bucket frame only)
+    L.feedback.enqueued(p);
+    if (p.bucket) ctx->bucket_frames += 1;
+    else if (p.places > 0) ctx->onesweep_frames += 1;
     if (p.cost) ctx->cost_frames += 1;
     if (p.ordered) ctx->ordered_frames += 1;
     if (p.refresh) ctx->order_refreshes += 1;
     const bool timed_frame = (ctx->frame_counter++ % ctx->profiling_stride) == 0;
     const int prof = timed_frame ? ctx->profiling : 0;
-    const int last_mark = render ? 6 : 2;
-    if (prof) {  // untimed frames do not consume a ring slot
+    if (prof) {
         L.ev_head = (L.ev_head + 1) % EV_RING;
         L.ev_kind[L.ev_head] = p.ev_kind();
         L.frames_timed += 1;
     }
-    hipEvent_t* const ev = L.ev_ring[L.ev_head];
-    auto mark = [&](int i) {
-        if (prof >= 2 || (prof == 1 && (i == 0 || i == last_mark))) (void)hipEventRecord(ev[i], st);
-    };
+    return {L.ev_ring[L.ev_head], L.stream, prof, last_mark(p.render)};
+}
 
-    // ---- 5. the launches of one frame, in stream order (issued directly, or once into a stream capture)
-    auto issue = [&]() -> hipError_t {
-        mark(0);
-        if (cost_in) launch_tile_order(st, cost_in, tile_order, p.ntiles, p.raster);   // (counted with the frame's first stage)
-        if (have_keygen) {
-            if (bucket && p.bucket_sub > BUCKET_SUB_KERNARG) {
-                const hipError_t ce = hipMemcpyAsync(L.d_split_keys.ptr, L.h_split_keys.ptr, (BUCKET_COUNT * p.bucket_sub - 1u) * sizeof(uint32_t),
-                                                     hipMemcpyHostToDevice, st);
-                if (ce != hipSuccess) return ce;
-            }
-            hipError_t e = kg.launch(st);
-            if (e != hipSuccess) return e;
+// Step 5 of enqueue_frame: the launches of one frame, in stream order (issued directly, or once into a stream capture).
+// front: the prepared keygen or compaction, null if there is nothing to launch (an empty cloud).
+template <class Front>
+hipError_t issue_frame(hipStream_t st, const FramePlan& p, const FrameBindings& b, Front* front, const StageMarks& mark) {
+    mark(MARK_BEGIN);
+    if (b.cost_in) launch_tile_order(st, b.cost_in, b.tile_order, p.ntiles, p.raster);   // (counted with the frame's first stage)
+    if (front) {
+        if (p.bucket && p.bucket_sub > BUCKET_SUB_KERNARG) {
+            const hipError_t ce = hipMemcpyAsync(b.split_keys, b.split_keys_staging, (BUCKET_COUNT * p.bucket_sub - 1u) * sizeof(uint32_t),
+                                                 hipMemcpyHostToDevice, st);
+            if (ce != hipSuccess) return ce;
         }
-        if (have_compact) {
-            const hipError_t e = ek.launch(st);
-            if (e != hipSuccess) return e;
-        }
-        mark(1);
-        int cur = 0;
-        if (bucket) {
-            const hipError_t e = launch_bucket_sort(st, L.bucket_slots.ptr, draw_list, ctl, final_xor, BUCKET_COUNT * p.bucket_sub, p.wide);
-            if (e != hipSuccess) return e;
-        }
-        for (uint32_t q = 0; q < (bucket ? 0u : places); ++q) {
-            // only the V' drawable entries are sorted; the culled tail is already in its final order
-            launch_onesweep_pass(st, L.entries[cur].ptr, L.entries[cur ^ 1].ptr, &ctl->draw_count, n, ctl->hist_depth[q],
-                                 depth_status + (size_t)q * lay.pass_stride, &ctl->ticket[q][0], &ctl->error,
-                                 q * RADIX_BITS, q + 1 == places ? final_xor : 0u, p.large, p.sort_blocks);
-            cur ^= 1;
-        }
-        mark(2);
-        if (render && scan) {
-            hipError_t e = launch_project_bin(st, fp, p.project, L.d_fp.ptr, in.cloud->ptrs, draw_list, L.culled.ptr, ctl, bin_status, L.records.ptr,
-                                              L.rects.ptr, L.coarse.ptr, coarse_cap, p.sup_edge, /*ticket_slot=*/4, p.bin_blocks, p.binning_blocks, p.wide_bin);
-            if (e != hipSuccess) return e;
-            mark(3);
-            e = launch_raster_scan(st, fp, p.raster, L.d_fp.ptr, L.records.ptr, L.coarse.ptr, coarse_cap, p.sup_edge, ctl, L.fb.ptr, L.fb8.ptr,
-                                   (flags & BGS_DEBUG_SEPARATE_ENCODE) ? 0u : p.out_format, cl, ctx->tile_trace, heavy_in, heavy_out, tile_order, cost_out);
-            if (e != hipSuccess) return e;
-            mark(6);
-        } else if (render) {
-            const uint32_t capacity = (uint32_t)std::min<uint64_t>(L.inst[0].capacity, MAX_INSTANCE_CAPACITY);
-            hipError_t e = launch_project_emit(st, fp, p.project, in.cloud->ptrs, draw_list, L.culled.ptr, ctl, scan_status, L.records.ptr, L.inst[0].ptr,
-                                               capacity, /*ticket_slot=*/4, p.emit_blocks);
-            if (e != hipSuccess) return e;
-            mark(3);
-            for (uint32_t q = 0; q < 2; ++q)
-                launch_onesweep_pass(st, L.inst[q].ptr, L.inst[q ^ 1].ptr, &ctl->instance_count, capacity, ctl->hist_tile[q],
-                                     tile_status + (size_t)q * lay.inst_tiles * RADIX_BASE, &ctl->ticket[5 + q][0],
-                                     &ctl->error, q * RADIX_BITS, 0u, true, p.tile_sort_blocks);
-            mark(4);
-            launch_tile_ranges(st, L.inst[0].ptr, ctl, ranges);
-            mark(5);
-            e = launch_raster(st, fp, p.raster, L.records.ptr, L.inst[0].ptr, ranges, L.fb.ptr, in.view.clear_color, ctl);
-            if (e != hipSuccess) return e;
-            mark(6);
-        }
-        // BINNING_SCAN frames get their sRGB8 image from the rasteriser itself (BGS_DEBUG_SEPARATE_ENCODE: from the
-        // separate encode pass, for A/B runs)
-        if (p.want_srgb8 && !(render && scan && !(flags & BGS_DEBUG_SEPARATE_ENCODE)))
-            launch_encode_srgb8(st, L.fb.ptr, L.fb8.ptr, (uint32_t)fp.width * (uint32_t)fp.height, L.d_fp.ptr, p.out_format);
-        return hipGetLastError();
-    };
-    const uint64_t replays_before = ctx->graph_replays;
-    if (p.graph_ok && !need_memset && prof == 0 && have_keygen) {
-        if ((rc = launch_graph(ctx, L, L.graph[0][L.ctl_parity], graph_key(p, in, L, kg, coarse_cap), kg, issue)) != BGS_OK) return rc;
-    } else if (p.graph_ok && !need_memset && prof == 0 && have_compact) {
-        if ((rc = launch_graph(ctx, L, L.graph[1][L.ctl_parity], graph_key(p, in, L, ek, coarse_cap), ek, issue)) != BGS_OK) return rc;
+        const hipError_t e = front->launch(st);
+        if (e != hipSuccess) return e;
+    }
+    mark(MARK_FRONT);
+    if (p.bucket) {
+        const hipError_t e = launch_bucket_sort(st, b.bucket_slots, b.draw_list, b.ctl, b.final_xor, BUCKET_COUNT * p.bucket_sub, p.wide);
+        if (e != hipSuccess) return e;
+    }
+    b.depth.launch(st);
+    mark(MARK_SORT);
+    if (p.render && p.scan) {
+        hipError_t e = b.project.launch(st);
+        if (e != hipSuccess) return e;
+        b.bin.launch(st);
+        mark(MARK_PROJECT);
+        e = b.raster_scan.launch(st);
+        if (e != hipSuccess) return e;
+        mark(MARK_RASTER);
+    } else if (p.render) {
+        hipError_t e = b.project_emit.launch(st);
+        if (e != hipSuccess) return e;
+        mark(MARK_PROJECT);
+        b.tile_sort.launch(st);
+        mark(MARK_TILE_SORT);
+        launch_tile_ranges(st, b.raster.instances, b.ctl, b.ranges);
+        mark(MARK_RANGES);
+        e = b.raster.launch(st);
+        if (e != hipSuccess) return e;
+        mark(MARK_RASTER);
+    }
+    // BINNING_SCAN frames get their sRGB8 image from the rasteriser itself (BGS_DEBUG_SEPARATE_ENCODE: from the
+    // separate encode pass, for A/B runs)
+    if (p.want_srgb8 && !(p.render && p.scan && !(p.fp.debug & BGS_DEBUG_SEPARATE_ENCODE)))
+        launch_encode_srgb8(st, b.fb, b.fb8, (uint32_t)p.fp.width * (uint32_t)p.fp.height, b.d_fp, p.out_format);
+    return hipGetLastError();
+}
+
+// What the launches of a captured frame depend on besides FrameParams: the plan's choices and the buffers they were
+// bound to. Nothing that changes from frame to frame (the splitter slot, its epoch, a kept order's chunk: the front node's
+// update carries them). `front`: the prepared KeygenLaunch or EntriesLaunch, whose kernel and grid the node keeps.
+template <class Front>
+GraphKey graph_key(const FramePlan& p, const FrameInputs& in, const Lane& L, const FrameBindings& b, const Front& front) {
+    GraphKey key;
+    std::memset(&key, 0, sizeof key);
+    const FrameParams& fp = p.fp;
+    const void* planes[6] = {in.cloud->ptrs.position_visibility, in.cloud->ptrs.packed, nullptr, nullptr, nullptr, nullptr};
+    std::memcpy(key.cloud, planes, sizeof planes);
+    const void* bufs[11] = {L.entries[0].ptr, L.entries[1].ptr, L.culled.ptr, L.records.ptr, L.coarse.ptr, L.fb.ptr, L.fb8.ptr,
+                            L.scratch.ptr, L.d_fp.ptr, L.h_ctl_dev, L.bucket_slots.ptr};   // (L.rects lives and dies with L.entries: ensure_entries)
+    std::memcpy(key.bufs, bufs, sizeof bufs);
+    key.n = p.n; key.places = p.places; key.sort_mode = in.settings.sort_mode;
+    key.project = p.project.key(); key.raster = p.raster.key(); key.srgb8 = p.out_format;
+    key.debug_flags = in.debug_flags;
+    key.width = fp.width; key.height = fp.height;
+    key.sort_blocks = p.bucket ? 0 : p.sort_blocks;  // the bucket sort's grid is fixed
+    key.bin_blocks = p.bin_blocks * 4096 + p.binning_blocks;   // (the bin kernel's shape follows the pipeline depth, as keygen's does: key.front_threads)
+    key.front_blocks = (int32_t)front.blocks; key.front_func = front.func; key.front_threads = front.threads;   // (kept: entries_blocks(n) of the compaction)
+    key.wide_bin = p.wide_bin ? 1u : 0u;
+    key.split_sub = p.split_sub_out;   // (round 5's advisor: a replay across a 524 k-pair step of the hint left a table of the captured sub under the new sub's label)
+    key.sup_edge = p.sup_edge;
+    key.scratch = L.layout;
+    key.coarse_cap = b.raster_scan.coarse_cap;
+    key.sort_path = p.bucket ? (p.bucket_sub | (p.wide ? 0x100u : 0u)) : 0u;   // (the bucket sort's grid and instantiation and keygen's dynamic LDS follow it)
+    return key;
+}
+
+// Replay the graph G of this key (its front node updated to this frame), or capture the frame's launches into a new one.
+template <class Front>
+int launch_graph(bgs_ctx* ctx, Lane& L, FrameGraph& G, const GraphKey& key, Front& front, const FramePlan& p, const FrameBindings& b, const StageMarks& mark) {
+    if (G.exec && std::memcmp(&G.key, &key, sizeof key) == 0) {
+        HIP_TRY(ctx, front.update_node(G.exec, G.front_node));
+        ctx->graph_replays += 1;
     } else {
-        if (need_memset) HIP_TRY(ctx, hipMemsetAsync(scratch, 0, lay.bytes, st));
+        graph_destroy(G);
+        HIP_TRY(ctx, hipStreamBeginCapture(L.stream, hipStreamCaptureModeThreadLocal));
+        const hipError_t ie = issue_frame(L.stream, p, b, &front, mark);
+        const hipError_t ce = hipStreamEndCapture(L.stream, &G.graph);
+        size_t roots = 1;
+        if (ie != hipSuccess || ce != hipSuccess || !G.graph ||
+            hipGraphInstantiate(&G.exec, G.graph, nullptr, nullptr, 0) != hipSuccess ||
+            hipGraphGetRootNodes(G.graph, &G.front_node, &roots) != hipSuccess || roots != 1) {
+            graph_destroy(G);
+            (void)hipGetLastError();
+            return fail(ctx, BGS_EHIP, "capturing the frame into a hipGraph failed");
+        }
+        G.key = key;
+        ctx->graph_captures += 1;
+    }
+    HIP_TRY(ctx, hipGraphLaunch(G.exec, L.stream));
+    return BGS_OK;
+}
+
+// The frame on its lane's stream: as the captured graph of its kind (0 sorting, 1 kept order) and Control parity, or issued
+// directly behind the memset of a scratch region that is not known to be clean; then what follows every frame.
+template <class Front>
+int submit_frame(bgs_ctx* ctx, Lane& L, const FramePlan& p, const FrameInputs& in, const FrameBindings& b, Front* front, bool need_memset,
+                 const StageMarks& mark) {
+    hipStream_t st = L.stream;
+    int rc;
+    if (p.graph_ok && !need_memset && mark.prof == 0 && front) {
+        if ((rc = launch_graph(ctx, L, L.graph[p.kept ? 1 : 0][L.ctl_parity], graph_key(p, in, L, b, *front), *front, p, b, mark)) != BGS_OK) return rc;
+    } else {
+        if (need_memset) HIP_TRY(ctx, hipMemsetAsync(L.scratch.ptr, 0, L.layout.bytes, st));
         // no keygen (empty cloud): the kernels behind it still read the frame's parameters
-        if (!have_keygen && !p.kept) HIP_TRY(ctx, hipMemcpyAsync(L.d_fp.ptr, &fp, sizeof fp, hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, issue());
+        if (!front && !p.kept) HIP_TRY(ctx, hipMemcpyAsync(b.d_fp, &p.fp, sizeof p.fp, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, issue_frame(st, p, b, front, mark));
     }
     // the Control block travels back with the frame; it is looked at when the lane is completed.
     // A BINNING_SCAN frame's rasteriser has already written the counters to L.h_ctl and left the
@@ -949,43 +979,62 @@ int enqueue_frame(bgs_ctx* ctx, Lane& L, const FrameInputs& in) {
     if (p.raster_cleans) {
         L.ctl_parity ^= 1u;
     } else {
-        if (places == 4 && n > 0) launch_splitters(st, draw_list, ctl, final_xor, p.split_sub_out);
-        HIP_TRY(ctx, hipMemcpyAsync(L.h_ctl.ptr, ctl, sizeof(Control), hipMemcpyDeviceToHost, st));
+        if (p.places == 4 && p.n > 0) launch_splitters(st, b.draw_list, b.ctl, b.final_xor, p.split_sub_out);
+        HIP_TRY(ctx, hipMemcpyAsync(L.h_ctl.ptr, b.ctl, sizeof(Control), hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(ctx, hipEventRecord(L.done, st));
+    return BGS_OK;
+}
 
-    // ---- 6. the lane keeps the frame's inputs and plan
-    L.last_sorted = draw_list;
-    L.last_sorted_n = n;
-    L.last_ctl = render ? ctl : nullptr;
-    L.last_replay = ctx->graph_replays != replays_before;
-    L.last_strips = render && scan && p.raster.mode != 0 && heavy_in != nullptr;   // (launch_raster_scan's grid)
-    {   // the persistent kernels' grids, as the launchers above made them (capped_grid, kernels.h)
-        Lane::Grids g(++ctx->grid_stamps, n, in.grid_cap);
-        g.tail = p.culled_tail && (have_keygen || have_compact);
-        if (have_keygen) {
-            g.launched(g.FRONT, keygen_tile_splats(n), kg.blocks);
-            g.front_chainless = bucket && !p.culled_tail;
-        } else if (have_compact) {
-            g.launched(g.FRONT, ENTRIES_TILE, ek.blocks);
-        }
-        if (!bucket && places > 0 && n > 0) g.launched(g.DEPTH, sort_tile_size(p.large), capped_grid(n, sort_tile_size(p.large), p.sort_blocks));
-        if (render && n > 0) {
-            g.launched(g.PROJECT, 256u, capped_grid(n, 256u, scan ? p.bin_blocks : p.emit_blocks));
-            if (scan) g.launched(g.BIN, 1024u, capped_grid(n, 1024u, p.binning_blocks));
-            else g.launched(g.TILE_SORT, sort_tile_size(true), capped_grid(std::min<uint64_t>(L.inst[0].capacity, MAX_INSTANCE_CAPACITY), sort_tile_size(true), p.tile_sort_blocks));
-        }
-        L.grids = g;
-    }
-    L.fb_valid = !(p.out_format & OUT_SKIP_F32) || (flags & BGS_DEBUG_SEPARATE_ENCODE);
+// Step 6 of enqueue_frame: the lane keeps the frame's inputs and plan, and what was launched (g: with the front kernel's grid)
+void keep_frame(bgs_ctx* ctx, Lane& L, const FramePlan& p, const FrameInputs& in, const FrameBindings& b, Lane::Grids g, bool replayed) {
+    L.last_sorted = b.draw_list;
+    L.last_sorted_n = p.n;
+    L.last_ctl = p.render ? b.ctl : nullptr;
+    L.last_replay = replayed;
+    L.last_strips = b.raster_scan.strips();
+    g.launched(g.DEPTH, b.depth);
+    g.launched(g.PROJECT, b.project);
+    g.launched(g.PROJECT, b.project_emit);
+    g.launched(g.BIN, b.bin);
+    if (b.project_emit.blocks) g.launched(g.TILE_SORT, b.tile_sort);   // (an empty frame's tile passes find nothing: not reported)
+    L.grids = g;
+    L.fb_valid = !(p.out_format & OUT_SKIP_F32) || (in.debug_flags & BGS_DEBUG_SEPARATE_ENCODE);
     L.fb8_is_f16 = (p.out_format & OUT_RGBA16F) != 0u;
     L.fb8_valid = p.want_srgb8;
     if (p.want_srgb8) L.fb8_out = in.srgb8_target ? in.srgb8_target : L.fb8.ptr;
     L.pending = true;
-    L.pending_coarse_cap = coarse_cap;
+    L.pending_coarse_cap = b.raster_scan.coarse_cap;   // (of a BINNING_SCAN render)
     L.in = in;
     L.plan = p;
     L.seq = ++ctx->seq;
+}
+
+// Enqueue one frame on lane L: plan it, allocate, bind, commit its context changes, issue it, and keep its inputs and
+// plan in the lane. Returns without waiting; the caller decides when to finish the lane.
+int enqueue_frame(bgs_ctx* ctx, Lane& L, const FrameInputs& in) {
+    const FramePlan p = plan_frame(*ctx, L, in);                                     // 1. the frame's choices
+    uint32_t coarse_cap = 1;  // entries per supertile list
+    int rc = ensure_frame_buffers(ctx, L, p, in, &coarse_cap);                       // 2. buffers
+    if (rc != BGS_OK) return rc;
+    const bool need_memset = !L.scratch_clean;  // else the previous frame's rasteriser left it zeroed
+    if (need_memset) L.ctl_parity = 0;
+    const FrameBindings b = bind_frame(L, p, in, coarse_cap, ctx->tile_trace);       // 3. bindings, and the front launch on them
+    KeygenLaunch kg{};
+    EntriesLaunch ek;   // (filled for a kept order only: a sorting frame's enqueue does not touch it)
+    const bool have_keygen = !p.kept && prepare_keygen(*ctx, p, in, b, L.entries[0].ptr, L.culled.ptr, kg);
+    const bool have_compact = p.kept && prepare_compact(p, in, b, L.culled.ptr, ek);
+    const StageMarks mark = commit_frame(ctx, L, p);                                 // 4. the context's and the lane's state
+    const uint64_t replays_before = ctx->graph_replays;
+    rc = p.kept ? submit_frame(ctx, L, p, in, b, have_compact ? &ek : nullptr, need_memset, mark)   // 5. the launches
+                : submit_frame(ctx, L, p, in, b, have_keygen ? &kg : nullptr, need_memset, mark);
+    if (rc != BGS_OK) return rc;
+    Lane::Grids g(++ctx->grid_stamps, p.n, in.grid_cap);                             // 6. what the lane keeps
+    g.tail = p.culled_tail && (have_keygen || have_compact);
+    if (have_keygen) g.launched(g.FRONT, kg);
+    else if (have_compact) g.launched(g.FRONT, ek);
+    g.front_chainless = have_keygen && p.bucket && !p.culled_tail;
+    keep_frame(ctx, L, p, in, b, g, ctx->graph_replays != replays_before);
     return BGS_OK;
 }
 

@@ -142,6 +142,7 @@ bool EntriesLaunch::prepare(uint32_t max_blocks) {
     blocks = entries_blocks(fp.n);
     if (max_blocks && blocks > max_blocks) blocks = max_blocks;
     threads = ENTRIES_THREADS;
+    per_tile = ENTRIES_TILE;
     argv[0] = &fp; argv[1] = &entries; argv[2] = &draw_list; argv[3] = &tail; argv[4] = &ctl;
     argv[5] = &part_status; argv[6] = &ticket_slot; argv[7] = &fp_out; argv[8] = &zero_word;
     return true;

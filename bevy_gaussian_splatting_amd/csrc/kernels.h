@@ -1,5 +1,10 @@
 // kernels.h — host-callable launchers of the HIP kernels (one per stage of the hot path).
 // Every launcher only enqueues work on `stream`; none synchronises.
+// A stage with more than a handful of arguments is a LAUNCH STRUCT: an aggregate of named fields (optional inputs default
+// to null / zero, so a caller names only what it uses), a prepare() that fixes the launch geometry without launching
+// anything — `blocks` workgroups, `per_tile` items per tile of a persistent kernel; 0 blocks: nothing to launch — and a
+// launch(stream) that enqueues what prepare() described. A frame (bgs_frame.hip: bind_frame) and the diag hooks
+// (bgs_diag.hip) fill the same structs; the grid report (bgs_debug_frame_grids) is read off them.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -68,14 +73,19 @@ struct FrameCleanup {
 // (the onesweep tile geometry, SORT_THREADS .. sort_tile_size, and KEYGEN_TILE: bgs_device.h)
 
 // The grid of a persistent launch: one workgroup per tile of `per_block` items, at most max_blocks of them — the rest of
-// the tiles are taken by ticket (or stride) by workgroups that come back. The launchers below and the grid report
-// (bgs_debug_frame_grids) share this one formula; grid_under_cap is where a grid cap (bgs_set_grid_cap, 0 = none) meets a
-// launch's own most workgroups (plan_frame and the two diag hooks that launch with the frames' default grid).
+// the tiles are taken by ticket (or stride) by workgroups that come back. Only the launch structs' prepare() call it;
+// grid_under_cap is where a grid cap (bgs_set_grid_cap, 0 = none) meets a launch's own most workgroups (plan_frame and the
+// two diag hooks that launch with the frames' default grid).
 inline int grid_under_cap(int max_blocks, uint32_t cap) { return cap && (int)cap < max_blocks ? (int)cap : max_blocks; }
 inline uint32_t capped_grid(uint64_t items, uint32_t per_block, int max_blocks) {
     const uint64_t tiles = (items + per_block - 1u) / per_block, most = (uint64_t)(max_blocks > 0 ? max_blocks : 1);
     return (uint32_t)(tiles < most ? tiles : most);
 }
+
+// Control::ticket slots (the dynamic tile counters of the persistent kernels): whose is which in a frame, and in every hook
+// that launches one of those kernels alone. The depth passes take TICKET_DEPTH + q (q < 4), the tile-id passes of
+// BINNING_SORT TICKET_TILE + q (q < 2).
+enum TicketSlot : uint32_t { TICKET_DEPTH = 0u, TICKET_PROJECT = 4u, TICKET_TILE = 5u, TICKET_FRONT = 7u };
 
 // keygen + fused global digit histograms (radix_sort_a, src/sort/radix.wgsl:71-107) + stable
 // partition: drawable entries -> `entries` (index order), culled-sentinel entries -> `culled`
@@ -100,7 +110,7 @@ struct KeygenLaunch {
     bool wide = false;        // the frame is alone on the chip (pipeline depth 1): chainless tiles as 1024-thread workgroups
     // filled by prepare(): the launch geometry and the argument vector (points into this object)
     const void* func;
-    uint32_t blocks, threads;
+    uint32_t blocks, threads, per_tile;   // (per_tile: the splats of one tile, i.e. of one ticket)
     void* argv[13];
     uint32_t lds_bytes;   // dynamic LDS of the launch (the per-bucket counters of a bucket frame)
     bool prepare(int max_blocks);  // false: nothing to launch (n == 0)
@@ -141,7 +151,7 @@ struct EntriesLaunch {
     uint32_t* zero_word;
     // filled by prepare(): the launch geometry and the argument vector (points into this object)
     const void* func;
-    uint32_t blocks, threads;
+    uint32_t blocks, threads, per_tile;
     void* argv[9];
     bool prepare(uint32_t max_blocks = 0u);  // false: nothing to launch (n == 0); max_blocks: a grid cap (bgs_set_grid_cap), 0 = none
     hipError_t launch(hipStream_t stream);
@@ -152,16 +162,26 @@ struct EntriesLaunch {
 void launch_histogram(hipStream_t stream, const uint2* pairs, uint32_t n, uint32_t* hist /*[4][256]*/,
                       uint32_t passes);
 
-// One stable 8-bit LSD pass (Onesweep: chained-scan look-back, LDS-ranked scatter).
-//   n_ptr      device word holding the pair count
-//   hist       256 global digit counts for this pass (un-scanned)
-//   status     zeroed look-back words [ceil(max_n / tile)][256]
-//   ticket     zeroed dynamic tile counter
-//   key_xor    XOR-ed into the key on output (un-inverts SORT_RAYON keys in the final pass)
-void launch_onesweep_pass(hipStream_t stream, const uint2* in, uint2* out, const uint32_t* n_ptr,
-                          uint32_t max_n, const uint32_t* hist, uint32_t* status, uint32_t* ticket,
-                          uint32_t* error_flag, uint32_t shift, uint32_t key_xor, bool large_tiles,
-                          int max_blocks);
+// `passes` stable 8-bit LSD passes (Onesweep: chained-scan look-back, LDS-ranked scatter), least significant digit first:
+// pass q reads lists[q & 1] and writes the other list, so the result is in lists[passes & 1].
+//   n_ptr      device word holding the pair count (at most max_n, which sizes the grid)
+//   hist       per pass the 256 global digit counts (un-scanned): ctl->hist_depth or ctl->hist_tile
+//   status     zeroed look-back words, [ceil(max_n / tile)][256] per pass, status_stride words apart
+//   ctl        its error word, and ticket[first_ticket + q]: the zeroed dynamic tile counter of pass q
+//   final_xor  XOR-ed into the key on output of the last pass (un-inverts SORT_RAYON keys)
+struct OnesweepLaunch {
+    uint2* lists[2] = {nullptr, nullptr};
+    const uint32_t* n_ptr = nullptr;
+    const uint32_t (*hist)[RADIX_BASE] = nullptr;
+    uint32_t* status = nullptr;
+    size_t status_stride = 0;
+    Control* ctl = nullptr;
+    uint32_t max_n = 0, first_ticket = TICKET_DEPTH, passes = 0, final_xor = 0;
+    bool large_tiles = false;
+    uint32_t blocks = 0, per_tile = 0;   // of every pass
+    void prepare(int max_blocks) { per_tile = sort_tile_size(large_tiles); blocks = passes ? capped_grid(max_n, per_tile, max_blocks) : 0u; }
+    void launch(hipStream_t stream) const;
+};
 
 // Bucket sort of the drawable pairs keygen placed (fp.sort_path == 1): one launch instead of the digit
 // passes, workgroup = bucket: each bucket (<= BUCKET_CAP pairs) is sorted by (key, index) in LDS and written
@@ -174,45 +194,82 @@ hipError_t launch_bucket_sort(hipStream_t stream, const uint2* bucket_slots, uin
 // ctl->splitters = the 255 quantile keys of the sorted draw list (for frames without a cleaning rasteriser).
 void launch_splitters(hipStream_t stream, const uint2* sorted, Control* ctl, uint32_t key_xor, uint32_t sub = 1u);
 
-// The launchers of the templated kernels take the instantiation as the frame plan chose it (ProjectInst, RasterInst:
+// The launch structs of the templated kernels take the instantiation as the frame plan chose it (ProjectInst, RasterInst:
 // frame_params.h) and look it up; one that does not exist is hipErrorInvalidValue and no launch.
 
 // Vertex stage in front-to-back order + ordered tile-instance emission
-// (vs_points once per splat, src/render/gaussian.wgsl:184-436). inst: project_instantiation(fp, cloud.format).
-hipError_t launch_project_emit(hipStream_t stream, const FrameParams& fp, const ProjectInst& inst, const CloudPtrs& cloud,
-                               const uint2* draw_list, const uint2* culled, Control* ctl, unsigned long long* scan_status,
-                               void* records, uint2* instances, uint32_t capacity, uint32_t ticket_slot,
-                               int max_blocks);
+// (vs_points once per splat, src/render/gaussian.wgsl:184-436). inst: project_instantiation(fp, cloud.format). fp: the
+// host's copy, which the kernel takes by value (it must outlive launch()).
+struct ProjectEmitLaunch {
+    const FrameParams* fp = nullptr;
+    ProjectInst inst{};
+    CloudPtrs cloud{};
+    const uint2 *draw_list = nullptr, *culled = nullptr;
+    Control* ctl = nullptr;
+    unsigned long long* scan_status = nullptr;
+    void* records = nullptr;
+    uint2* instances = nullptr;
+    uint32_t capacity = 0, ticket_slot = TICKET_PROJECT, blocks = 0, per_tile = 0;
+    void prepare(int max_blocks) { per_tile = 256u; blocks = capped_grid(fp->n, per_tile, max_blocks); }
+    hipError_t launch(hipStream_t stream) const;
+};
 
-// BINNING_SCAN: the vertex stage in front-to-back order (project_kernel: rank -> record + packed tile rectangle, no
-// ordering between ranks) and the ORDERED coarse binning (bin_kernel: every rank is appended, in rank order, to the list
-// of each supertile (sup_edge x sup_edge tiles) its tile rectangle overlaps; one pass, no sort, no atomics on the data
-// path: the <= 256 supertiles are the "digits" of the same chained-scan look-back the radix sort uses), two launches.
-// inst: project_instantiation(fp, cloud.format). d_fp: the device copy of `fp` the kernels read (written by this frame's
-// keygen). rects: 4 bytes per rank.
-// wide_bin: the frame is alone on the chip (pipeline depth 1): bin_kernel as 1024-thread workgroups (else 256).
-hipError_t launch_project_bin(hipStream_t stream, const FrameParams& fp, const ProjectInst& inst, const FrameParams* d_fp,
-                              const CloudPtrs& cloud, const uint2* draw_list, const uint2* culled, Control* ctl, uint32_t* bin_status,
-                              void* records, uint32_t* rects, uint32_t* coarse, uint32_t coarse_cap, uint32_t sup_edge,
-                              uint32_t ticket_slot, int project_blocks, int bin_blocks, bool wide_bin);
-// bin_kernel alone, as launch_project_bin launches it behind project_kernel (and bgs_selftest_bin on rectangles of its
-// own): `blocks` workgroups of 1024 (wide_bin) or 256 threads; sup_mul = supertile_mul(edge), sup_x x sup_y supertiles.
-void launch_bin(hipStream_t stream, const uint32_t* rects, Control* ctl, uint32_t* bin_status, uint32_t* coarse,
-                uint32_t coarse_cap, uint32_t sup_mul, uint32_t sup_x, uint32_t sup_y, uint32_t ticket_slot,
-                uint32_t blocks, bool wide_bin);
+// BINNING_SCAN: the vertex stage in front-to-back order (ProjectLaunch, project_kernel: rank -> record + packed tile
+// rectangle, no ordering between ranks) and the ORDERED coarse binning (BinLaunch, bin_kernel: every rank is appended, in
+// rank order, to the list of each supertile (sup_edge x sup_edge tiles) its tile rectangle overlaps; one pass, no sort, no
+// atomics on the data path: the <= 256 supertiles are the "digits" of the same chained-scan look-back the radix sort
+// uses), two launches. inst: project_instantiation(fp, cloud.format). d_fp: the device copy of the frame's parameters
+// the kernel reads (written by this frame's keygen). rects: 4 bytes per rank. n: the ranks the host knows of (fp.n).
+struct ProjectLaunch {
+    ProjectInst inst{};
+    const FrameParams* d_fp = nullptr;
+    CloudPtrs cloud{};
+    const uint2 *draw_list = nullptr, *culled = nullptr;
+    Control* ctl = nullptr;
+    void* records = nullptr;
+    uint32_t* rects = nullptr;
+    uint32_t blocks = 0, per_tile = 0;
+    void prepare(uint32_t n, int max_blocks) { per_tile = 256u; blocks = capped_grid(n, per_tile, max_blocks); }
+    hipError_t launch(hipStream_t stream) const;
+};
+// wide: the frame is alone on the chip (pipeline depth 1): 1024-thread workgroups (else 256). A hook that brings its own
+// grid sets `blocks` instead of calling prepare() (bgs_selftest_bin).
+struct BinLaunch {
+    const uint32_t* rects = nullptr;
+    Control* ctl = nullptr;
+    uint32_t *bin_status = nullptr, *coarse = nullptr;
+    uint32_t coarse_cap = 0, sup_edge = 0, tiles_x = 0, tiles_y = 0, ticket_slot = TICKET_PROJECT, blocks = 0, per_tile = 0;
+    bool wide = false;
+    void prepare(uint32_t n, int max_blocks);
+    void launch(hipStream_t stream) const;
+};
 
 // Tile rasteriser for BINNING_SCAN: walks the supertile's ordered list, keeps the ranks whose
 // rectangle contains this tile (order-preserving ballot compaction), stages their records in LDS
-// and composites front-to-back until the tile saturates. With want_srgb8 it also writes the frame as
+// and composites front-to-back until the tile saturates. With out_format it also writes the frame as
 // Rgba8UnormSrgb (to d_fp->srgb8_target, else srgb8_default): no separate encode pass for this path.
 // inst: the instantiation of raster_scan_kernel (raster_instantiation; its mode: 0 plain, 1 dense + mid-round exit, 2 sparse +
 // mid-round exit). tile_trace: what a traced instantiation fills (else unused). heavy_in / heavy_out, order, cost_out: the
-// tile feedback below, each may be null.
-hipError_t launch_raster_scan(hipStream_t stream, const FrameParams& fp, const RasterInst& inst, const FrameParams* d_fp,
-                              const void* records, const uint32_t* coarse, uint32_t coarse_cap,
-                              uint32_t sup_edge, Control* ctl, float4* framebuffer, uint32_t* srgb8_default,
-                              uint32_t out_format, const FrameCleanup& cleanup, uint4* tile_trace,
-                              const uint8_t* heavy_in, uint8_t* heavy_out, const uint16_t* order, uint16_t* cost_out);
+// tile feedback below, each may be null. cleanup: all-null = none. Not persistent: a workgroup per four tiles, and the
+// strip workgroups behind them when strips().
+struct RasterScanLaunch {
+    RasterInst inst{};
+    const FrameParams* d_fp = nullptr;
+    const void* records = nullptr;
+    const uint32_t* coarse = nullptr;
+    uint32_t tiles_x = 0, tiles_y = 0, coarse_cap = 0, sup_edge = 0, out_format = 0;
+    Control* ctl = nullptr;
+    float4* framebuffer = nullptr;
+    uint32_t* srgb8_default = nullptr;
+    FrameCleanup cleanup{};
+    uint4* tile_trace = nullptr;
+    const uint8_t* heavy_in = nullptr;
+    uint8_t* heavy_out = nullptr;
+    const uint16_t* order = nullptr;
+    uint16_t* cost_out = nullptr;
+    bool strips() const { return inst.mode != 0 && heavy_in != nullptr; }
+    hipError_t launch(hipStream_t stream) const;
+};
 // TileCost: what every tile of a frame cost its wave — records blended, records staged, staging rounds and candidate
 // groups scanned, weighted into eighths of a blended record (render_kernels.hip WORK_*; u16 per tile) — left by the
 // rasteriser (cost_out) for the frames behind it, and the order made of it for a frame's raster workgroups
@@ -251,10 +308,18 @@ constexpr uint32_t OUT_SKIP_F32 = 4u;  // do not write the f32 target (bgs_set_p
 void launch_tile_ranges(hipStream_t stream, const uint2* instances, const Control* ctl, uint2* ranges);
 
 // Per-16x16-tile front-to-back blend (fs_main + blend, src/render/gaussian.wgsl:438-505,
-// src/render/mod.rs:944-948). Of `inst` its variant, samples, depth and overlay count: raster_kernel has no modes and no trace.
-hipError_t launch_raster(hipStream_t stream, const FrameParams& fp, const RasterInst& inst, const void* records,
-                         const uint2* instances, const uint2* ranges, float4* framebuffer,
-                         const float clear_color[4], const Control* ctl);
+// src/render/mod.rs:944-948). Of `inst` its variant, samples, depth and overlay count: raster_kernel has no modes and no
+// trace. fp: the host's copy, taken by value by the kernel; clear_color: four floats. Both must outlive launch().
+struct RasterLaunch {
+    const FrameParams* fp = nullptr;
+    RasterInst inst{};
+    const void* records = nullptr;
+    const uint2 *instances = nullptr, *ranges = nullptr;
+    float4* framebuffer = nullptr;
+    const float* clear_color = nullptr;
+    const Control* ctl = nullptr;
+    hipError_t launch(hipStream_t stream) const;
+};
 
 // Rgba8UnormSrgb image of the f32 framebuffer (the reference's render-target format).
 // The destination is d_fp->srgb8_target when that is non-zero, else default_out.

@@ -371,17 +371,12 @@ __global__ __launch_bounds__(256) void project_emit_kernel(FrameParams fp, Cloud
     if (tid == 0) publish_color_max(ctl, fmaxf(fmaxf(s_cmag[0], s_cmag[1]), fmaxf(s_cmag[2], s_cmag[3])));
 }
 
-hipError_t launch_project_emit(hipStream_t stream, const FrameParams& fp, const ProjectInst& inst, const CloudPtrs& cloud,
-                               const uint2* draw_list, const uint2* culled, Control* ctl,
-                               unsigned long long* scan_status,
-                               void* records, uint2* instances, uint32_t capacity, uint32_t ticket_slot,
-                               int max_blocks) {
-    if (fp.n == 0) return hipSuccess;
-    const uint32_t blocks = capped_grid(fp.n, 256u, max_blocks);
+hipError_t ProjectEmitLaunch::launch(hipStream_t stream) const {
+    if (blocks == 0) return hipSuccess;
     float4* rec = (float4*)records;
     const bool found = with_project_inst(inst, [&](auto FMT, auto SURFEL, auto ANY_MODE) {
         hipLaunchKernelGGL((project_emit_kernel<FMT, SURFEL, ANY_MODE>), dim3(blocks), dim3(256), 0, stream,
-                           fp, cloud, draw_list, culled, ctl, scan_status, rec, instances, capacity,
+                           *fp, cloud, draw_list, culled, ctl, scan_status, rec, instances, capacity,
                            ticket_slot);
     });
     return found ? hipSuccess : hipErrorInvalidValue;
@@ -581,29 +576,22 @@ __global__ __launch_bounds__(64u * WAVES) void bin_kernel(const uint32_t* __rest
     }
 }
 
-hipError_t launch_project_bin(hipStream_t stream, const FrameParams& fp, const ProjectInst& inst, const FrameParams* d_fp,
-                              const CloudPtrs& cloud, const uint2* draw_list, const uint2* culled, Control* ctl, uint32_t* bin_status,
-                              void* records, uint32_t* rects, uint32_t* coarse, uint32_t coarse_cap, uint32_t sup_edge,
-                              uint32_t ticket_slot, int project_blocks, int bin_blocks, bool wide_bin) {
-    if (fp.n == 0) return hipSuccess;
-    const uint32_t blocks = capped_grid(fp.n, 256u, project_blocks);
-    const uint32_t sup = sup_edge, sup_mul = supertile_mul(sup_edge);
-    const uint32_t sup_x = ((uint32_t)fp.tiles_x + sup - 1u) / sup, sup_y = ((uint32_t)fp.tiles_y + sup - 1u) / sup;
+hipError_t ProjectLaunch::launch(hipStream_t stream) const {
+    if (blocks == 0) return hipSuccess;
     float4* rec = (float4*)records;
     const bool found = with_project_inst(inst, [&](auto FMT, auto SURFEL, auto ANY_MODE) {
         hipLaunchKernelGGL((project_kernel<FMT, SURFEL, ANY_MODE>), dim3(blocks), dim3(256), 0, stream,
                            d_fp, cloud, draw_list, culled, ctl, rec, rects);
     });
-    if (!found) return hipErrorInvalidValue;
-    const uint32_t bblocks = capped_grid(fp.n, BIN_RANKS, bin_blocks);
-    launch_bin(stream, rects, ctl, bin_status, coarse, coarse_cap, sup_mul, sup_x, sup_y, ticket_slot, bblocks, wide_bin);
-    return hipSuccess;
+    return found ? hipSuccess : hipErrorInvalidValue;
 }
 
-void launch_bin(hipStream_t stream, const uint32_t* rects, Control* ctl, uint32_t* bin_status, uint32_t* coarse,
-                uint32_t coarse_cap, uint32_t sup_mul, uint32_t sup_x, uint32_t sup_y, uint32_t ticket_slot,
-                uint32_t blocks, bool wide_bin) {
-    if (wide_bin)
+void BinLaunch::prepare(uint32_t n, int max_blocks) { per_tile = BIN_RANKS; blocks = capped_grid(n, per_tile, max_blocks); }
+
+void BinLaunch::launch(hipStream_t stream) const {
+    if (blocks == 0) return;
+    const uint32_t sup_mul = supertile_mul(sup_edge), sup_x = (tiles_x + sup_edge - 1u) / sup_edge, sup_y = (tiles_y + sup_edge - 1u) / sup_edge;
+    if (wide)
         hipLaunchKernelGGL(bin_kernel<16u>, dim3(blocks), dim3(1024), 0, stream, rects, ctl, bin_status, coarse, coarse_cap,
                            sup_mul, sup_x, sup_y, ticket_slot);
     else
@@ -2267,18 +2255,14 @@ void launch_tile_order_runs(hipStream_t stream, const uint16_t* cost, uint16_t* 
 }
 
 // The instantiation is the caller's choice (raster_instantiation, frame_params.h); one that does not exist (RasterInst::exists)
-// is refused, nothing launched. The strip workgroups behind the regular grid come with a mid-round-exit mode and heavy_in.
-hipError_t launch_raster_scan(hipStream_t stream, const FrameParams& fp, const RasterInst& inst, const FrameParams* d_fp,
-                              const void* records, const uint32_t* coarse, uint32_t coarse_cap,
-                              uint32_t sup_edge, Control* ctl, float4* framebuffer, uint32_t* srgb8_default,
-                              uint32_t out_format, const FrameCleanup& cleanup, uint4* tile_trace,
-                              const uint8_t* heavy_in, uint8_t* heavy_out, const uint16_t* order, uint16_t* cost_out) {
-    const uint32_t ntiles = (uint32_t)(fp.tiles_x * fp.tiles_y);
+// is refused, nothing launched. The strip workgroups behind the regular grid come with a mid-round-exit mode and heavy_in
+// (strips()).
+hipError_t RasterScanLaunch::launch(hipStream_t stream) const {
+    const uint32_t ntiles = tiles_x * tiles_y;
     if (ntiles == 0) return hipSuccess;
     const float4* rec = (const float4*)records;
-    const uint32_t sup = sup_edge, sup_mul = supertile_mul(sup_edge);
-    const uint32_t sup_x = ((uint32_t)fp.tiles_x + sup - 1u) / sup;
-    const uint32_t grid = (ntiles + 3u) / 4u + (inst.mode != 0 && heavy_in ? HEAVY_CAP : 0u);
+    const uint32_t sup_mul = supertile_mul(sup_edge), sup_x = (tiles_x + sup_edge - 1u) / sup_edge;
+    const uint32_t grid = (ntiles + 3u) / 4u + (strips() ? HEAVY_CAP : 0u);
     const bool found = with_raster_inst(inst, [&](auto VARIANT, auto SAMPLES, auto DEPTH, auto OVERLAY, auto MODE, auto TRACE) {
         hipLaunchKernelGGL((raster_scan_kernel<VARIANT, TRACE, MODE, SAMPLES, DEPTH, OVERLAY>), dim3(grid), dim3(256), 0, stream, d_fp, rec, coarse,
                            coarse_cap, sup_mul, sup_x, ctl, framebuffer, srgb8_default, out_format, cleanup, TRACE ? tile_trace : (uint4*)nullptr,
@@ -2288,15 +2272,13 @@ hipError_t launch_raster_scan(hipStream_t stream, const FrameParams& fp, const R
 }
 
 // (the instantiations of raster_kernel: what exists of `inst` with mode 0 and no trace)
-hipError_t launch_raster(hipStream_t stream, const FrameParams& fp, const RasterInst& inst, const void* records,
-                         const uint2* instances, const uint2* ranges, float4* framebuffer,
-                         const float clear_color[4], const Control* ctl) {
-    const uint32_t ntiles = (uint32_t)(fp.tiles_x * fp.tiles_y);
+hipError_t RasterLaunch::launch(hipStream_t stream) const {
+    const uint32_t ntiles = (uint32_t)(fp->tiles_x * fp->tiles_y);
     if (ntiles == 0) return hipSuccess;
     const float4 clear = make_float4(clear_color[0], clear_color[1], clear_color[2], clear_color[3]);
     const float4* rec = (const float4*)records;
     const bool found = with_raster_inst({inst.variant, inst.samples, inst.depth, inst.overlay}, [&](auto VARIANT, auto SAMPLES, auto DEPTH, auto OVERLAY, auto, auto) {
-        hipLaunchKernelGGL((raster_kernel<VARIANT, SAMPLES, DEPTH, OVERLAY>), dim3(ntiles), dim3(256), 0, stream, fp, rec, instances, ranges,
+        hipLaunchKernelGGL((raster_kernel<VARIANT, SAMPLES, DEPTH, OVERLAY>), dim3(ntiles), dim3(256), 0, stream, *fp, rec, instances, ranges,
                            framebuffer, clear, ctl);
     });
     return found ? hipSuccess : hipErrorInvalidValue;

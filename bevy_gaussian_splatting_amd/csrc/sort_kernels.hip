@@ -502,6 +502,7 @@ bool KeygenLaunch::prepare(int max_blocks) {
                          : reinterpret_cast<const void*>(&keygen_kernel<4, true, 1024, true>);
     }
 #undef BGS_KG_PICK
+    per_tile = per_block;
     blocks = (fp.n + per_block - 1) / per_block;
     // (tiles without chains depend on nobody: one workgroup per tile, dispatched as slots come free)
     if (!unordered && blocks > (uint32_t)max_blocks) blocks = (uint32_t)max_blocks;
@@ -723,18 +724,21 @@ const uint2* __restrict__ in,
     }
 }
 
-void launch_onesweep_pass(hipStream_t stream, const uint2* in, uint2* out, const uint32_t* n_ptr,
-                          uint32_t max_n, const uint32_t* hist, uint32_t* status, uint32_t* ticket,
-                          uint32_t* error_flag, uint32_t shift, uint32_t key_xor, bool large_tiles,
-                          int max_blocks) {
-    if (max_n == 0) return;
-    const uint32_t blocks = capped_grid(max_n, sort_tile_size(large_tiles), max_blocks);
-    if (large_tiles)
-        hipLaunchKernelGGL(onesweep_kernel<SORT_KPT_LARGE>, dim3(blocks), dim3(256), 0, stream, in, out,
-                           n_ptr, hist, status, ticket, error_flag, shift, key_xor);
-    else
-        hipLaunchKernelGGL(onesweep_kernel<SORT_KPT_SMALL>, dim3(blocks), dim3(256), 0, stream, in, out,
-                           n_ptr, hist, status, ticket, error_flag, shift, key_xor);
+void OnesweepLaunch::launch(hipStream_t stream) const {
+    if (blocks == 0) return;
+    for (uint32_t q = 0; q < passes; ++q) {
+        const uint2* in = lists[q & 1u];
+        uint2* out = lists[(q & 1u) ^ 1u];
+        uint32_t* pass_status = status + (size_t)q * status_stride;
+        uint32_t* ticket = &ctl->ticket[first_ticket + q][0];
+        const uint32_t shift = q * RADIX_BITS, key_xor = q + 1u == passes ? final_xor : 0u;
+        if (large_tiles)
+            hipLaunchKernelGGL(onesweep_kernel<SORT_KPT_LARGE>, dim3(blocks), dim3(256), 0, stream, in, out,
+                               n_ptr, hist[q], pass_status, ticket, &ctl->error, shift, key_xor);
+        else
+            hipLaunchKernelGGL(onesweep_kernel<SORT_KPT_SMALL>, dim3(blocks), dim3(256), 0, stream, in, out,
+                               n_ptr, hist[q], pass_status, ticket, &ctl->error, shift, key_xor);
+    }
 }
 
 // ---------------------------------------------------------------------------------------
