@@ -4,9 +4,11 @@
 // RCCL: types and prototypes only — librccl is opened at run time (bgs_comm_*), libbgs does not link it. A ROCm install
 // without the RCCL development headers still builds the whole library (round 5's advisor: the render path was lost with
 // the header): the handful of declarations the gather needs, with the values of NCCL's stable ABI.
-#if __has_include(<rccl/rccl.h>)
+// -DBGS_NO_RCCL_HEADER takes the fallback on a host that has the header too (tests/test_comm_host.py builds it).
+#if __has_include(<rccl/rccl.h>) && !defined(BGS_NO_RCCL_HEADER)
 #include <rccl/rccl.h>
 #else
+#define NCCL_UNIQUE_ID_BYTES 128
 extern "C" {
 typedef struct ncclComm* ncclComm_t;
 typedef struct { char internal[128]; } ncclUniqueId;
@@ -49,11 +51,22 @@ std::string rccl_error() {
 const RcclApi* rccl_api() {
     std::lock_guard<std::mutex> lock(g_rccl_mutex);
     if (g_rccl.handle) return &g_rccl;
-    // a process that already holds an RCCL (torch's bundled one, say) gets that one: same SONAME
-    const char* names[] = {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
     void* h = nullptr;
-    for (const char* nm : names) if ((h = dlopen(nm, RTLD_NOW | RTLD_GLOBAL)) != nullptr) break;
-    if (!h) { g_rccl.error = std::string("librccl not found: ") + (dlerror() ? dlerror() : "dlopen failed"); return nullptr; }
+    // BGS_RCCL_LIBRARY: a host that ships its own RCCL build; the tests' stand-in. The only name tried,
+    // and private to this handle: its symbols neither reach nor come from an RCCL the process already holds.
+    const char* own = std::getenv("BGS_RCCL_LIBRARY");
+    if (own && own[0]) {
+        h = dlopen(own, RTLD_NOW | RTLD_LOCAL);
+    } else {
+        // a process that already holds an RCCL (torch's bundled one, say) gets that one: same SONAME
+        const char* names[] = {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
+        for (const char* nm : names) if ((h = dlopen(nm, RTLD_NOW | RTLD_GLOBAL)) != nullptr) break;
+    }
+    if (!h) {   // (dlerror() hands its message out once: a second call returns NULL)
+        const char* why = dlerror();
+        g_rccl.error = std::string("librccl not found: ") + (why ? why : "dlopen failed");
+        return nullptr;
+    }
     RcclApi a;
     a.GetUniqueId = (decltype(a.GetUniqueId))dlsym(h, "ncclGetUniqueId");
     a.CommInitRank = (decltype(a.CommInitRank))dlsym(h, "ncclCommInitRank");
