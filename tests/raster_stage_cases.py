@@ -21,7 +21,8 @@ entries), reads the raw record words, and applies per pixel and per sample the f
             alpha = min(a exp(-min(us^2 + vs^2, 2 |mean - pc|^2) / 2), 0.999f); no discard;
 It does not batch, knows nothing of keep / interior / strip verdicts, queues or rounds: those may only skip work that adds
 nothing. It does not model surfel_negligible_in_tile: what that drops is at most 2^-23 of the record's opacity, which is added
-to the bound of every surfel record's alpha (not under the overlay, where nothing is dropped).
+to the bound of every surfel record's alpha (not under the overlay, where nothing is dropped). The integer reference does
+model it (negligible_figure), and tests/test_raster_stage_host.py checks that promise pixel by pixel.
 
 THE ERROR BOUND. e = 2^-24 (1 + 2^-10) per rounded binary32 operation (the factor covers second-order terms). Derived from
 the operations the kernels perform, in the order they perform them:
@@ -393,6 +394,19 @@ def work_constants(path=None):
 
 
 KEEP_SLACK, KEEP_MARGIN = 1.0001, 1e-5   # raster_tile's slack; how far from it a float64 figure must lie to be decided (binary32: ~1e-6)
+# surfel_negligible_in_tile's verdict (s3 >= limit && s2 >= limit) is decided where each side that the verdict hangs on lies
+# NEG_MARGIN x its conditioning clear of the limit, RELATIVE to the larger of the two. The device forms a side from the
+# record's words in about ten rounded binary32 operations (aspect, dx0, U0, b, two fmas of P0, the constant C1, the fma of the
+# centre value, the half-range, the subtraction; then a square, an fma and a product): each of lx, ly, hz, dx, dy carries at
+# most 10 e of the summed magnitudes of its terms, a square doubles it, the quotient adds hz's share: (2 x 10 + 2 x 10 + 3) e
+# = 2.6e-6 of a side whose terms do not cancel; v_rcp_f32 (1 ulp = 2 e) and, on the limit, v_log_f32 (1 ulp of a number of
+# about 25: 1.2e-7 relative) and the conversion of cmax are inside the factor of four that 1e-5 leaves, as KEEP_MARGIN leaves
+# one. Where the terms DO cancel (p's centre value is a difference of viewport-size coordinates; mean - b is one too) the
+# error is relative to the terms, not to the result: negligible_terms reports that ratio (>= 1) per side and the margin is
+# multiplied by it.
+NEG_MARGIN = 1e-5
+SURFEL_CULL_LOG2 = 23.0
+STAGE_C1, STAGE_C2 = float(np.float32(0.84932180028801907)), float(np.float32(1.2011224087864498))   # stage_surfel's constants, as binary32 holds them
 
 
 def keep_figure(case, rec, tx, ty):
@@ -410,17 +424,86 @@ def keep_figure(case, rec, tx, ty):
     return max(fu, fv) if np.isfinite(fu) and np.isfinite(fv) else -np.inf
 
 
+def surfel_stage(case, rec, tx, ty):
+    """stage_surfel in float64 from a record's raw words: the affine parts of p = P0 + Px xl + Py yl (p.xy scaled by C1) and of the
+    screen-space deltas D = D0 + dD (xl, yl) (scaled by C2) over the tile's pixels xl, yl in [0, 15], with the magnitudes of
+    what each P0 component and each D0 was summed from."""
+    f = rec.astype(np.float64)
+    cx, cy, m00, m11, radius, mx, my = f[0:7]
+    Av, Bv, Cv = f[7:10], f[10:13], f[13:16]
+    aspect = float(np.float32(case.viewport[0]) / np.float32(case.viewport[1]))
+    U0, V0 = m00 * ((tx * TILE + 0.5) - cx), m11 * ((ty * TILE + 0.5) - cy)
+    ax, bx = m00 * radius, U0 * radius + mx
+    ay, by = m11 * radius * aspect, V0 * radius * aspect + my
+    k = (STAGE_C1, STAGE_C1, 1.0)
+    P0 = [k[i] * (Av[i] * bx + Bv[i] * by + Cv[i]) for i in range(3)]
+    M0 = [k[i] * (abs(Av[i]) * (abs(U0 * radius) + abs(mx)) + abs(Bv[i]) * (abs(V0 * radius * aspect) + abs(my)) + abs(Cv[i])) for i in range(3)]
+    Px = [k[i] * Av[i] * ax for i in range(3)]
+    Py = [k[i] * Bv[i] * ay for i in range(3)]
+    D0 = (STAGE_C2 * (mx - bx), STAGE_C2 * (my - by))
+    MD = (STAGE_C2 * (2 * abs(mx) + abs(U0 * radius)), STAGE_C2 * (2 * abs(my) + abs(V0 * radius * aspect)))
+    dD = (-STAGE_C2 * ax, -STAGE_C2 * ay)
+    return {"P0": P0, "Px": Px, "Py": Py, "D0": D0, "dD": dD, "M0": M0, "MD": MD}
+
+
+def negligible_terms(case, rec, tx, ty):
+    """surfel_negligible_in_tile and frame_surfel_limit in float64, by the kernel's own interval construction: over the tile's
+    pixel centres (centre H = 7.5, half-range H (|Px| + |Py|) of the affine part) |p.x|, |p.y| are at least lx, ly, |p.z| at most hz,
+    the deltas at least dx, dy; s3 = (lx^2 + ly^2) / hz^2, s2 = dx^2 + dy^2 (exp2 units), limit = 23 + log2(max(1, cmax)).
+    Returns (s3, s2, limit, cond3, cond2): cond is the ratio of a side's rounding error to its value in units of a side without
+    cancellation (NEG_MARGIN). A NaN side stays NaN (the kernel keeps such a record)."""
+    H = 7.5
+    st = surfel_stage(case, rec, tx, ty)
+    with np.errstate(all="ignore"):
+        c = [st["P0"][i] + H * (st["Px"][i] + st["Py"][i]) for i in range(3)]
+        e = [H * (abs(st["Px"][i]) + abs(st["Py"][i])) for i in range(3)]
+        M = [st["M0"][i] + 2.0 * e[i] for i in range(3)]
+        lx, ly, hz = max(abs(c[0]) - e[0], 0.0), max(abs(c[1]) - e[1], 0.0), abs(c[2]) + e[2]
+        s3 = np.float64(lx * lx + ly * ly) / np.float64(hz * hz)
+        num = lx * lx + ly * ly
+        cond3 = max(1.0, (lx * M[0] + ly * M[1]) / num if num > 0.0 else 1.0, M[2] / hz if hz > 0.0 else 1.0)
+        d, Md = [], []
+        for j in range(2):
+            d.append(max(abs(st["D0"][j] + H * st["dD"][j]) - H * abs(st["dD"][j]), 0.0))
+            Md.append(st["MD"][j] + 2.0 * H * abs(st["dD"][j]))
+        s2 = d[0] * d[0] + d[1] * d[1]
+        cond2 = max(1.0, (d[0] * Md[0] + d[1] * Md[1]) / s2 if s2 > 0.0 else 1.0)
+        cmax = float(np.uint32(case.color_max_bits).view(np.float32))
+        limit = SURFEL_CULL_LOG2 + np.log2(cmax if cmax > 1.0 else 1.0)   # fmaxf(1, NaN) is 1
+    return float(s3), float(s2), float(limit), float(cond3), float(cond2)
+
+
+def negligible_figure(case, rec, tx, ty):
+    """The smaller of (s3 - limit, s2 - limit) of negligible_terms: the record is dropped from the tile where this is >= 0 (not
+    under the overlay, which drops nothing). -inf where a side is NaN: every compare is false and the record is kept."""
+    s3, s2, limit, _, _ = negligible_terms(case, rec, tx, ty)
+    return -np.inf if np.isnan(s3) or np.isnan(s2) else min(s3 - limit, s2 - limit)
+
+
+def negligible_decided(case, rec, tx, ty):
+    """Is the verdict NEG_MARGIN clear: a side clearly below the limit keeps the record whatever the other says; otherwise both
+    must be clearly above."""
+    s3, s2, limit, c3, c2 = negligible_terms(case, rec, tx, ty)
+    if np.isnan(s3) or np.isnan(s2):
+        return False
+    below = lambda s, c: limit - s > NEG_MARGIN * c * max(s, limit)
+    above = lambda s, c: s - limit > NEG_MARGIN * c * max(s, limit)
+    return below(s3, c3) or below(s2, c2) or (above(s3, c3) and above(s2, c2))
+
+
 def cost_reference(case, tx, ty, states):
     """What the regular wave of tile (tx, ty) must report, from the scan loop of raster_tile restated in integers:
         every group of 64 candidates that is queued costs WORK_GROUP; a group is queued when its hits fit the 64-entry queue;
         the queue is staged as one round when it holds FLUSH_AT = 32 or more, when the next group does not fit, or at the
         list's end: WORK_ROUND + WORK_STAGED per staged record + WORK_BLENDED per record that is kept (the quad reaches the
-        tile's samples, and under a depth buffer z >= the tile's smallest depth); the tile stops after a round that leaves every
-        pixel below the cut-off (bit 15) or when list and queue are empty.
+        tile's samples, a surfel drawn without the overlay is not negligible in the tile (negligible_figure < 0), and under a
+        depth buffer z >= the tile's smallest depth); the tile stops after a round that leaves every pixel below the cut-off
+        (bit 15) or when list and queue are empty.
     Returns {"work" (mode 0: without a mid-round exit), "saturated", "rounds", "countable"}; countable: every keep verdict lies
-    KEEP_MARGIN clear of the slack and every round-end saturation verdict is decided (`states`: render_reference's, for this
-    case). The verdict and the rounds are the same in modes 1 and 2: a mid-round exit leaves only when every pixel is below
-    the cut-off, which the round's end then finds too."""
+    KEEP_MARGIN clear of the slack, every surfel's negligible verdict NEG_MARGIN clear of the limit (negligible_decided) and
+    every round-end saturation verdict is decided (`states`: render_reference's, for this case). The verdict and the rounds
+    are the same in modes 1 and 2: a mid-round exit leaves only when every pixel is below the cut-off, which the round's end
+    then finds too."""
     W = work_constants()
     s = (ty // case.sup_edge) * case.sup_x + tx // case.sup_edge
     total = min(int(case.totals[s]), case.cap)
@@ -429,14 +512,18 @@ def cost_reference(case, tx, ty, states):
     dmin = None
     if case.depth is not None:
         dmin = case.depth[ty * TILE:(ty + 1) * TILE, tx * TILE:(tx + 1) * TILE].min()
-    countable = case.variant != SURFEL
+    countable = True
     kept = []
     for rank in ranks:
-        fig = keep_figure(case, case.records[int(rank)], tx, ty)
+        rec = case.records[int(rank)]
+        fig = keep_figure(case, rec, tx, ty)
         countable &= abs(fig - KEEP_SLACK) > KEEP_MARGIN
         k = fig <= KEEP_SLACK
+        if k and case.variant == SURFEL and not case.overlay:   # (a quad that misses the tile is not asked)
+            countable &= negligible_decided(case, rec, tx, ty)
+            k = negligible_figure(case, rec, tx, ty) < 0.0
         if dmin is not None:
-            k = k and bool(np.float32(case.records[int(rank)][11]) >= dmin)
+            k = k and bool(np.float32(rec[20 if case.variant == SURFEL else 11]) >= dmin)
         kept.append(k)
     work = rounds = qn = base = done = 0
     saturated = False
@@ -523,6 +610,210 @@ def surfel_record(cx, cy, half, sx, sy, rgb=(1.0, 1.0, 1.0), a=0.5, z=0.5):
     r[7:10], r[10:13], r[13:16] = np.cross(T1, T2), np.cross(T2, T0), np.cross(T0, T1)
     r[16:19], r[19], r[20] = rgb, a, z
     return r
+
+
+def surfel_record_from_rows(cx, cy, half, T0, T1, T2, mean, rgb=(1.0, 1.0, 1.0), a=0.5, z=0.5):
+    """A RecordSurfel from the three rows of a surfel's local-to-pixel matrix: the square quad of half extent `half` around
+    (cx, cy), radius = half, the cross products A = T1 x T2, B = T2 x T0, C = T0 x T1 formed in float64 and rounded once."""
+    r = np.zeros(24, np.float32)
+    r[0:4] = (cx, cy, 1.0 / half, 1.0 / half)
+    r[4], r[5], r[6] = half, mean[0], mean[1]
+    T0, T1, T2 = (np.asarray(t, np.float64) for t in (T0, T1, T2))
+    r[7:10], r[10:13], r[13:16] = np.cross(T1, T2), np.cross(T2, T0), np.cross(T0, T1)
+    r[16:19], r[19], r[20] = rgb, a, z
+    return r
+
+
+def tilted_surfel_record(cx, cy, half, sx, sy, tilt, spin, mean_offset=(0.0, 0.0), focal=256.0, rgb=(1.0, 1.0, 1.0), a=0.5, z=0.5):
+    """A RecordSurfel of a surfel that does NOT face the camera. The camera is a pinhole of `focal` pixels whose axis meets the
+    image at pixel (0, 0): K = diag(focal, focal, 1). The surfel's centre lies at depth 1 on the ray of mean = (cx, cy) +
+    mean_offset: c = (mean.x / focal, mean.y / focal, 1). Its first tangent is the in-plane direction e = (cos spin, sin spin, 0)
+    tilted by `tilt` towards the viewing axis, d_u = cos tilt e + sin tilt z, its second the in-plane direction orthogonal to
+    e, d_v = (-sin spin, cos spin, 0); a standard deviation of sx (sy) pixels at depth 1 is a length of sx / focal (sy / focal):
+    t_u = sx d_u / focal, t_v = sy d_v / focal. A point (s, t) of the surfel, in standard deviations, is c + s t_u + t t_v, and
+    its homogeneous pixel is K [t_u t_v c] (s, t, 1): the rows of that matrix are
+        T0 = (sx d_u.x, sy d_v.x, mean.x),  T1 = (sx d_u.y, sy d_v.y, mean.y),  T2 = (sx d_u.z / focal, 0, 1),
+    written so that focal is divided by only where it does not cancel. The pixel pc sees the surfel at (s, t) = p.xy / p.z
+    with p = (pc.x T2 - T0) x (pc.y T2 - T1) = pc.x A + pc.y B + C. With a tilt p.z = C.z + A.z pc.x + B.z pc.y varies over the
+    image, A.z = -sx sy sin tilt cos spin / focal and B.z = -sx sy sin tilt sin spin / focal, and vanishes on the surfel
+    plane's horizon, the line pc . (cos spin, sin spin) = focal / tan tilt: the default focal keeps it about 100 px from the
+    origin at a tilt of 1.2. The quad stays the square around (cx, cy) and pc = pixel + mean_offset, so the screen-space side
+    is 2 |pixel - (cx, cy)|^2 whatever the offset. tilt = 0 and no offset give surfel_record's words bit for bit."""
+    ct, st_, cs, ss = np.cos(tilt), np.sin(tilt), np.cos(spin), np.sin(spin)
+    mean = (cx + mean_offset[0], cy + mean_offset[1])
+    du = (ct * cs, ct * ss, st_)
+    dv = (0.0 - ss, cs)   # (0 - sin: no negative zero at spin 0)
+    T0 = (sx * du[0], sy * dv[0], mean[0])
+    T1 = (sx * du[1], sy * dv[1], mean[1])
+    T2 = (sx * du[2] / focal, 0.0, 1.0)
+    return surfel_record_from_rows(cx, cy, half, T0, T1, T2, mean, rgb, a, z)
+
+
+def surfel_sides(case, rec, tx, ty):
+    """(p [3 grids], s3, s2) of a surfel record over the pixel centres of tile (tx, ty) in float64, by _record_terms' own
+    expressions: s3 = |p.xy / p.z|^2 (inf or NaN where p.z == 0), s2 = 2 |mean - pc|^2."""
+    f = rec.astype(np.float64)
+    ys, xs = np.meshgrid(ty * TILE + np.arange(TILE) + 0.5, tx * TILE + np.arange(TILE) + 0.5, indexing="ij")
+    aspect = float(np.float32(case.viewport[0]) / np.float32(case.viewport[1]))
+    ex, ey = f[2] * (xs - f[0]) * f[4], f[3] * (ys - f[1]) * f[4] * aspect
+    pcx, pcy = ex + f[5], ey + f[6]
+    p = [f[7 + i] * pcx + f[10 + i] * pcy + f[13 + i] for i in range(3)]
+    with np.errstate(all="ignore"):
+        s3 = (p[0] / p[2]) ** 2 + (p[1] / p[2]) ** 2
+    return p, s3, 2.0 * (ex * ex + ey * ey)
+
+
+def _fma32(a, b, c):
+    """fmaf of binary32 operands: the product is exact in float64, the sum rounds to float64 and then to binary32 (one rounding
+    wherever the sum fits 53 bits, which is every use here: operands of a few bits each)."""
+    return np.float32(np.float64(a) * np.float64(b) + np.float64(c))
+
+
+def stage_surfel32(case, rec, tx, ty):
+    """stage_surfel operation by operation in binary32 (the kernel's own order, fmaf where it has one): the staged words
+    P0 [3], Px [3], Py [3], with `inner` = the three sums before the constant C1 multiplies them."""
+    f = rec.astype(np.float32)
+    one = np.float32
+    ox, oy = one(tx * TILE + 0.5), one(ty * TILE + 0.5)
+    aspect = one(case.viewport[0]) / one(case.viewport[1])
+    U0, V0 = f[2] * (ox - f[0]), f[3] * (oy - f[1])
+    radius = f[4]
+    ax, bx = f[2] * radius, _fma32(U0, radius, f[5])
+    ay, by = f[2 + 1] * radius * aspect, _fma32(V0 * radius, aspect, f[6])
+    A, B, C = f[7:10], f[10:13], f[13:16]
+    C1 = one(STAGE_C1)
+    inner = [_fma32(A[i], bx, _fma32(B[i], by, C[i])) for i in range(3)]
+    P0 = [C1 * inner[0], C1 * inner[1], inner[2]]
+    Px = [C1 * A[0] * ax, C1 * A[1] * ax, A[2] * ax]
+    Py = [C1 * B[0] * ay, C1 * B[1] * ay, B[2] * ay]
+    return {"U0": U0, "V0": V0, "ax": ax, "bx": bx, "ay": ay, "by": by, "inner": inner, "P0": P0, "Px": Px, "Py": Py}
+
+
+def pixel_p32(st, qx, qy):
+    """p at pixel (qx, qy) of the tile from stage_surfel32's words, as blend_px forms it: fma(Py, qy, fma(Px, qx, P0))."""
+    return [_fma32(st["Py"][i], np.float32(qy), _fma32(st["Px"][i], np.float32(qx), st["P0"][i])) for i in range(3)]
+
+
+SPINS = (0.5, 2.2, -1.1, 3.9)   # one per quadrant: (A.z, B.z) take every pair of signs, |cos|, |sin| >= 0.45
+
+
+def _tilt_interior_records():
+    """Four quads that hold tile (0, 0) of a 32 x 32 target with room to spare, their surfels tilted by 0.6 and 1.2, spun into
+    the four quadrants, means a few pixels off the quad centres."""
+    spec = ((9.1, 7.3, 40, 14, 11, 0.6, (3.0, -2.0)), (8.3, 8.9, 50, 17, 12, 1.2, (-2.5, 1.5)),
+            (7.2, 8.4, 45, 12, 15, 1.2, (1.5, 3.0)), (8.8, 6.9, 42, 16, 10, 0.6, (-3.0, -1.0)))
+    return np.array([tilted_surfel_record(cx, cy, half, sx, sy, tilt, SPINS[i], off, rgb=PRIMARIES[i], a=0.4)
+                     for i, (cx, cy, half, sx, sy, tilt, off) in enumerate(spec)], np.float32)
+
+
+def surfel_tilted_cases():
+    """The designed surfel cases again with planes that do not face the camera (tilted_surfel_record): p.z varies from pixel
+    to pixel, A.z and B.z differ in sign and size, the mean is off the quad centre, the viewport's aspect is not 1."""
+    out = []
+    full = rect(0, 1, 0, 1)
+    # a. interior quads: the hand-written interior update at 1 and 4 samples, blend_px / blend_px_ms in the sort rasteriser and at 2, 8
+    recs = _tilt_interior_records()
+    for S in (1, 2, 4, 8):
+        lists, totals = make_lists([[(i, full) for i in range(4)]])
+        out.append(Case(f"surfel_tilt_interior_s{S}", 32, 32, recs, lists, totals, samples=S, variant=SURFEL,
+                        notes={"interior": {(0, 0): [True] * 4}, "tilted": [0, 1, 2, 3]}))
+    for S in (1, 4):
+        # b. surfel_cover_strips' and surfel_cover_room_to_spare's quads (the strips first: test_strip_cases reads record 4 as
+        # the quad smaller than a pixel). The small quads carry surfels larger than themselves behind a short focal length, so
+        # that A.z, B.z stay well above rounding; tilt 0.6 keeps their horizon 90 px away.
+        small = lambda i, cx, cy, half: tilted_surfel_record(cx, cy, half, 3.0, 2.5, 0.6, SPINS[i % 4], (0.4, -0.3), focal=64.0, rgb=PRIMARIES[i], a=0.5)
+        recs = np.array([small(0, 8.2, 1.3, 1.1), small(1, 7.7, 14.6, 1.0), small(2, 8.1, 8.0, 0.7), small(3, 16.0, 16.0, 0.3),
+                         small(4, 5.5 + 0.01, 9.5 - 0.02, 0.25),
+                         tilted_surfel_record(9.1, 7.3, 40, 14, 11, 1.2, SPINS[1], (2.0, 1.0), rgb=PRIMARIES[5], a=0.3),
+                         tilted_surfel_record(5.3, 5.1, 4.3, 4.5, 3.6, 0.6, SPINS[2], (-0.5, 0.7), focal=64.0, rgb=PRIMARIES[1], a=0.5),
+                         tilted_surfel_record(8.3, 8.9, 50, 17, 12, 0.6, SPINS[3], (-2.0, 2.5), rgb=PRIMARIES[2], a=0.3)], np.float32)
+        lists, totals = make_lists([[(i, full) for i in range(8)]])
+        out.append(Case(f"surfel_tilt_edge_and_strips_s{S}", 32, 32, recs, lists, totals, samples=S, variant=SURFEL,
+                        notes={"interior": {(0, 0): [False] * 5 + [True, False, True]}, "tilted": list(range(8)),
+                               "strips": {0: [True, False, False, False], 1: [False, False, False, True], 2: [False, True, True, False]},
+                               "misses_tile": {3: [(0, 0), (1, 0), (0, 1), (1, 1)] if S == 1 else [(1, 0), (0, 1)]}}))
+        # c. case a's records under viewports of aspect 1.5 and 2 / 3, neither of the target's size
+        for name, vp in (("3_2", (48.0, 32.0)), ("2_3", (32.0, 48.0))):
+            lists, totals = make_lists([[(i, full) for i in range(4)]])
+            out.append(Case(f"surfel_tilt_aspect_{name}_s{S}", 32, 32, _tilt_interior_records(), lists, totals, samples=S, variant=SURFEL, viewport=vp,
+                            notes={"interior": {(0, 0): [True] * 4}, "tilted": [0, 1, 2, 3]}))
+        # d. one standard deviation of 0.5 px (under 1 / sqrt 2: along it the screen-space side 2 d^2 is the smaller) and one of
+        # 12 px (along it the surfel's own side is): min(s3, s2) takes either on a good part of tile (0, 0)
+        recs = np.array([tilted_surfel_record(8.3, 7.6, 40, 12.0, 0.5, 1.2, 0.6, (0.3, -0.2), rgb=PRIMARIES[3], a=0.6),
+                         tilted_surfel_record(7.4, 8.7, 44, 0.55, 9.0, 0.6, 2.5, (-0.4, 0.25), rgb=PRIMARIES[4], a=0.6)], np.float32)
+        lists, totals = make_lists([[(i, full) for i in range(2)]])
+        out.append(Case(f"surfel_tilt_filter_crossover_s{S}", 32, 32, recs, lists, totals, samples=S, variant=SURFEL,
+                        notes={"interior": {(0, 0): [True, True]}, "tilted": [0, 1], "crossover_tile": (0, 0)}))
+        # e. surfel_cover_alternating_kinds_* with tilted planes: runs of interior and of other records, p.z varying in both
+        for first in (True, False):
+            recs, kinds = [], []
+            for i in range(64):
+                interior = (i % 2 == 0) == first
+                kinds.append(interior)
+                if interior:
+                    recs.append(tilted_surfel_record(8.1 + 0.01 * i, 7.9, 60, 20 + 0.1 * i, 25 - 0.1 * i, 0.6 if i % 4 < 2 else 1.2, SPINS[(i // 2) % 4],
+                                                     (2.0 - 0.05 * i, -1.5 + 0.04 * i), rgb=PRIMARIES[i % 6], a=0.08))
+                else:
+                    recs.append(tilted_surfel_record(2.0 + (i % 7) * 2.0 + 0.1, 3.0 + (i % 5) * 2.5 + 0.05, 3.1, 3.3, 2.7, 0.6, SPINS[(i // 2) % 4],
+                                                     (0.3, -0.4), focal=64.0, rgb=PRIMARIES[i % 6], a=0.5))
+            lists, totals = make_lists([[(i, rect(0, 0, 0, 0)) for i in range(64)]])
+            out.append(Case(f"surfel_tilt_alternating_kinds_{'interior' if first else 'other'}_first_s{S}", 16, 16, np.array(recs, np.float32), lists, totals,
+                            samples=S, variant=SURFEL, notes={"interior": {(0, 0): kinds}, "tilted": list(range(64))}))
+    return out
+
+
+def surfel_negligible_cases():
+    """What surfel_negligible_in_tile takes out of a tile: two thin ellipses (20 x 0.6 px standard deviations) in 64 x 64 quads
+    on 4 x 4 tiles, one facing the camera along x, one tilted by 1.2 and a little turned. The tiles along an ellipse blend it,
+    the tiles a few standard deviations to its side do not (rows 0 and 3; in row 2 the two tiles next to the quad centre keep it,
+    the screen-space side being below the limit there);`notes["blended"]` says which, per tile and record. The quad centres are placed so
+    that the outer tiles of row 2 lie between the limits of cmax = 1 (23) and cmax = 6 (25.58): tiles (0, 2) and (3, 2) drop
+    record 0 and tile (0, 2) record 1 at cmax 1 and blend them at cmax 6 (`notes["flips"]`). Under the overlay nothing is
+    dropped."""
+    recs = np.array([tilted_surfel_record(32.3, 29.05, 32, 20.0, 0.6, 0.0, 0.0, (0.5, -0.25), focal=512.0, rgb=PRIMARIES[0], a=0.6),
+                     tilted_surfel_record(32.3, 28.75, 32, 20.0, 0.6, 1.2, 0.15, (0.5, -0.25), focal=512.0, rgb=PRIMARIES[2], a=0.6)], np.float32)
+    rows_1 = {0: [(False, False)] * 4, 1: [(True, True)] * 4, 2: [(False, False), (True, True), (True, True), (False, False)], 3: [(False, False)] * 4}
+    rows_6 = dict(rows_1)
+    rows_6[2] = [(True, True), (True, True), (True, True), (True, False)]
+    blended = lambda rows: {(tx, ty): list(rows[ty][tx]) for ty in range(4) for tx in range(4)}
+    out = []
+    for name, S, cmax, overlay, rows in (("cmax_1_s1", 1, 1.0, 0, rows_1), ("cmax_1_s4", 4, 1.0, 0, rows_1), ("cmax_6_s1", 1, 6.0, 0, rows_6),
+                                         ("overlay_s1", 1, 1.0, 1, None)):
+        lists, totals = make_lists([[(i, rect(0, 3, 0, 3)) for i in range(2)]])
+        notes = {"tilted": [1], "blended": blended(rows) if rows else {(tx, ty): [True, True] for ty in range(4) for tx in range(4)}}
+        if name == "cmax_6_s1":
+            notes["flips"] = [(0, 0, 2), (0, 3, 2), (1, 0, 2)]   # (record, tx, ty) dropped at cmax 1, blended here
+        out.append(Case(f"surfel_negligible_{name}", 64, 64, recs, lists, totals, samples=S, variant=SURFEL, overlay=overlay,
+                        color_max_bits=float_bits(cmax), notes=notes))
+    return out
+
+
+def surfel_grazing_cases():
+    """Rays that graze a surfel's plane inside the tile: p.z passes through 0, v_rcp_f32 returns huge values, inf and (times a
+    zero) NaN, and min(s3, s2) must come out as the screen-space side. 16 x 16, one tile, 1 and 4 samples. Not designed cases:
+    next to the horizon the reference's bound grows as the kernel's error does, and a pixel whose bound exceeds 2^-10 (the
+    whole-frame render tolerance) is left out of the float64 comparison — `notes["horizon"]`; never out of the bit comparison.
+      i.  two surfels tilted by 1.45 whose horizons cross the tile obliquely between pixel centres, one in a quad that holds
+          the tile (the interior update), one in a 12 px quad (blend_px).
+      ii. power-of-two words, every staged operation on the way to p.z exact. Record 0, rows T0 = (2, 0, 7), T1 = (0, 2, 8),
+          T2 = (1/4, 0, 1) in a quad around (8.5, 8.5): pc = the pixel's index - (1, 0), p.z = 4 - pc.x / 2 = 0 on column 9 while
+          p.x = 2 pc.x - 14 = 2 there: an inf quotient, s3 = inf; named pixel (9, 8), one pixel from the quad centre. p is the
+          cofactor matrix of [T0 T1 T2] applied to (pc, 1), so p.xyz = 0 needs a singular matrix: record 1 has T0 = (1, 0, 4) =
+          4 T2, the surfel's plane through the eye, p = (pc.x - 4) (2, 2, -1/2) with pc.x = column: 0 x inf = NaN on column 4;
+          named pixel (4, 8), the quad centre (4.5, 8.5). One record cannot hold both: where the matrix is singular p.z = 0
+          only where all of p is. The constant C1 scales p.xy by a binary32 number: a zero stays a zero and a power of two times
+          it is exact, so record 1's p.x, p.y are exact zeros on the device as well."""
+    out = []
+    for S in (1, 4):
+        recs = np.array([tilted_surfel_record(8.3, 7.6, 40, 6.0, 5.0, 1.45, 0.3, (0.3, -0.2), focal=78.0, rgb=PRIMARIES[0], a=0.5),
+                         tilted_surfel_record(7.2, 8.4, 6.0, 5.0, 4.0, 1.45, -0.4, (-0.25, 0.3), focal=62.4, rgb=PRIMARIES[2], a=0.5)], np.float32)
+        lists, totals = make_lists([[(i, rect(0, 0, 0, 0)) for i in range(2)]])
+        out.append(Case(f"surfel_grazing_oblique_s{S}", 16, 16, recs, lists, totals, samples=S, variant=SURFEL, notes={"interior": {(0, 0): [True, False]}}))
+        recs = np.array([surfel_record_from_rows(8.5, 8.5, 16.0, (2.0, 0.0, 7.0), (0.0, 2.0, 8.0), (0.25, 0.0, 1.0), (7.0, 8.0), PRIMARIES[3], 0.5),
+                         surfel_record_from_rows(4.5, 8.5, 16.0, (1.0, 0.0, 4.0), (0.0, 2.0, 8.0), (0.25, 0.0, 1.0), (4.0, 8.0), PRIMARIES[4], 0.5)], np.float32)
+        out.append(Case(f"surfel_grazing_exact_s{S}", 16, 16, recs, lists.copy(), totals.copy(), samples=S, variant=SURFEL,
+                        notes={"interior": {(0, 0): [True, True]}, "inf_pixel": (0, 9, 8), "nan_pixel": (1, 4, 8)}))   # (record, x, y)
+    return out
 
 
 def surfel_coverage_cases():
@@ -867,6 +1158,50 @@ def mixed_case(variant, S, depth, overlay, mode, seed=5):
                 samples=S, variant=variant, overlay=overlay, modes=(mode,), depth=d, random=True)
 
 
+def mixed_tilted_records(n=200, seed=5, w=64, h=48):
+    """mixed_records' surfels again, none of them facing the camera by design: tilts uniform in [0, 1.3], any spin, the mean up
+    to 2 px off the quad centre, behind a focal length of 512 px (the horizon of a tilt of 1.3 is 142 px from the origin; the
+    target's far corner, offsets included, is 86)."""
+    rng = np.random.default_rng(seed)
+    recs, rects = [], []
+    for i in range(n):
+        cx, cy = rng.uniform(-4, w + 4), rng.uniform(-4, h + 4)
+        hx, hy = np.exp(rng.uniform(np.log(0.6), np.log(30.0), 2))
+        rgb = rng.uniform(0.0, 1.0, 3)
+        a = rng.uniform(0.05, 1.0)
+        z = rng.uniform(0.05, 0.95)
+        tilt, spin = rng.uniform(0.0, 1.3), rng.uniform(0.0, 2.0 * np.pi)
+        off = rng.uniform(-2.0, 2.0, 2)
+        hh = max(hx, hy)
+        recs.append(tilted_surfel_record(cx, cy, hh, hx / 3.0, hy / 3.0, tilt, spin, (off[0], off[1]), focal=512.0, rgb=rgb, a=a, z=z))
+        rects.append(honest_rect(w, h, cx, cy, hh + 1.0, hh + 1.0))
+    return np.array(recs, np.float32), np.array(rects, np.uint32)
+
+
+def tilted_instantiations():
+    """(samples, depth, overlay) of every surfel instantiation."""
+    return [(S, depth, overlay) for S in (1, 2, 4, 8) for depth in (False, True) for overlay in (0, 1)]
+
+
+def mixed_tilted_case(S, depth, overlay, seed=5):
+    w, h = 64, 48
+    recs, rects = mixed_tilted_records(seed=seed, w=w, h=h)
+    per = [[] for _ in range(4)]
+    for i, rc in enumerate(rects):   # as mixed_case: 2 x 2 supertiles of 2 x 2 tiles
+        if rc == RECT_EMPTY:
+            continue
+        x0, x1, y0, y1 = int(rc) & 255, (int(rc) >> 8) & 255, (int(rc) >> 16) & 255, int(rc) >> 24
+        for sy in range(y0 // 2, y1 // 2 + 1):
+            for sx in range(x0 // 2, x1 // 2 + 1):
+                per[sy * 2 + sx].append((i, rc))
+    lists, totals = make_lists(per)
+    d = None
+    if depth:
+        d = np.random.default_rng(seed + 77).uniform(0.2, 0.8, (h, w, S)).astype(np.float32)
+    return Case(f"mixed_tilted_s{S}{'_depth' if depth else ''}{'_overlay' if overlay else ''}", w, h, recs, lists, totals, sup_edge=2,
+                samples=S, variant=SURFEL, overlay=overlay, depth=d, random=True)
+
+
 def nan_case():
     """A record whose cx is NaN in the middle of a list, and the same list without it."""
     recs = _grid_records(30)
@@ -879,4 +1214,4 @@ def nan_case():
 
 def designed_cases():
     return (list_total_cases() + list_edge_cases() + queue_cases() + coverage_cases() + exact_edge_cases() + saturation_cases() +
-            strip_workgroup_cases() + depth_cases() + shape_cases() + surfel_coverage_cases())
+            strip_workgroup_cases() + depth_cases() + shape_cases() + surfel_coverage_cases() + surfel_tilted_cases() + surfel_negligible_cases())

@@ -37,7 +37,7 @@ def reference(case):
 def run(plugin, case, mode, heavy=None, order=None):
     out = plugin.selftest_raster(case.width, case.height, case.samples, case.variant, case.records, case.lists, case.totals,
                                  case.sup_edge, case.cap, mode=mode, overlay=case.overlay, clear=case.clear,
-                                 color_max_bits=case.color_max_bits, depth=case.depth, heavy_tiles=heavy, order=order)
+                                 color_max_bits=case.color_max_bits, viewport=case.viewport, depth=case.depth, heavy_tiles=heavy, order=order)
     assert out["error"] == 0
     assert (out["scan_guard"] == 0xFFFFFFFF).all() and (out["sort_guard"] == 0xFFFFFFFF).all(), "a rasteriser wrote behind its image"
     return out
@@ -105,8 +105,6 @@ _COSTS = {}
 
 def assert_cost_words(case, mode, out):
     """The integer reference (raster_stage_cases.cost_reference) on every countable tile of a plain launch."""
-    if case.variant == C.SURFEL:   # (surfel_negligible_in_tile decides what a surfel tile blends: not restated, nothing is countable)
-        return
     if case.name not in _COSTS:
         _COSTS[case.name] = C.cost_references(case)
     msgs, heavy = [], []
@@ -126,7 +124,7 @@ def assert_cost_words(case, mode, out):
         if out["heavy_count"] != len(heavy) or got != heavy or np.nonzero(out["heavy_flags"])[0].tolist() != heavy:
             msgs.append(f"mode {mode}: heavy count {out['heavy_count']} list {got} flags {np.nonzero(out['heavy_flags'])[0].tolist()}, the reference names {heavy}")
     counted = sum(w["countable"] for w in _COSTS[case.name])
-    print(f"{case.name} mode {mode}: cost words of {counted} of {len(_COSTS[case.name])} tiles counted"
+    print(f"{case.name} mode {mode}: cost words of {counted} of {len(_COSTS[case.name])} {'surfel ' if case.variant == C.SURFEL else ''}tiles counted"
           + ("" if mode == 0 else f", heavy set {'compared' if counted == len(_COSTS[case.name]) else 'not compared (a tile is not countable)'}"))
     for m in msgs[:12]:
         print(f"  {case.name} {m}")
@@ -193,6 +191,35 @@ def test_strip_workgroups_and_a_reversed_order_change_no_bit(plugin, case):
 @pytest.mark.parametrize("inst", C.instantiations(), ids=str)
 def test_every_instantiation_on_the_mixed_case(plugin, inst):
     check_case(plugin, C.mixed_case(*inst))
+
+
+@pytest.mark.parametrize("inst", C.tilted_instantiations(), ids=str)
+def test_every_surfel_instantiation_on_the_mixed_tilted_case(plugin, inst):
+    """Random surfels that do not face the camera (tilts up to 1.3, means off the quad centres) through every surfel instantiation."""
+    check_case(plugin, C.mixed_tilted_case(*inst))
+
+
+@pytest.mark.parametrize("case", C.surfel_grazing_cases(), ids=lambda c: c.name)
+def test_grazing_rays_leave_finite_pixels_and_the_screen_space_side(plugin, case):
+    """p.z through 0 inside the tile: huge, inf and NaN quotients, of which min(s3, s2) must keep the screen-space side. The two
+    rasterisers agree bit for bit and write finite pixels; at the named pixels (an inf quotient, a 0 x inf NaN) the device is
+    within twice the reference's bound, which drops the NaN with fmin; elsewhere a pixel is left to the bit comparison alone
+    only where the reference's own bound exceeds 2^-10, the whole-frame render tolerance."""
+    ref, bound, und = reference(case)[:3]
+    assert not und.any()
+    out = run(plugin, case, 0)
+    assert_same_bits(f"{case.name}: scan vs sort", out["scan"], out["sort"])
+    assert np.isfinite(out["scan"]).all() and np.isfinite(out["sort"]).all()
+    horizon = bound.max(axis=2) > 2.0 ** -10
+    for key in ("inf_pixel", "nan_pixel"):
+        if key in case.notes:
+            _, x, y = case.notes[key]
+            err = np.abs(out["scan"][y, x].astype(np.float64) - ref[y, x])
+            print(f"{case.name} {key} ({x}, {y}): device {out['scan'][y, x]} reference {ref[y, x]} error / bound {(err / bound[y, x]).max():.3f}")
+            assert not horizon[y, x] and (err <= 2.0 * bound[y, x]).all()
+    print(f"{case.name}: {int(horizon.sum())} pixels next to a horizon left to the bit comparison")
+    assert_within_bound(case, "grazing", out["scan"], ref, bound, horizon, plugin, 0)
+    assert_cost_words(case, 0, out)
 
 
 def test_a_nan_record_inside_a_list_changes_no_bit(plugin):
